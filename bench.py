@@ -7,6 +7,14 @@ backward -> [RCCL all-reduce of the 640 M gradients] -> global-norm clip -> Adam
 weights / accumulation; weak scaling (256 samples per GPU), value = bs256-steps completed by all ranks per second.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--mode train|sample] [--batch B] [--dtype bf16|fp32]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints the result line (`ms_per_step` = wall-clock milliseconds of
+one timed step).  `--full` adds everything else the benchmark measures, after the headline's timed region: the
+exclusive-kernel roofline leg (`roofline`, `kernel_families`; `--no-profile` drops it), the other single-GPU BASELINE
+configs (`secondary`; `--no-secondary`) and the CPU baseline (`cpu_baseline`; `--no-cpu-baseline`).
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (float32 / float64; the
+640 M-element parameter and gradient arenas as a fixed, seeded sample), before any `--full` leg runs.
 
 --gpus N > 1: `python bench.py --gpus N` starts the N ranks itself (the parent never touches the GPU: it only starts one
 child process per GPU with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set and relays rank 0's JSON line); under
@@ -173,6 +181,38 @@ def _traffic_for(build_id, kernel, workload_key):
     return None, f"no profiles/*pmc_traffic*.json for build {build_id} / workload {workload_key}"
 
 
+DUMP_SAMPLE = 1 << 21                   # positions drawn from each 640 M-element arena for --dump-outputs (8 MiB as float32)
+
+
+def _arena_sample(flat):
+    """A fixed, seeded sample of a flat device arena: the same sorted positions on every run of the same workload (and the
+    same positions in the parameter and the gradient arena, which share one layout)."""
+    import numpy as np
+    import torch
+    n = flat.numel()
+    if n <= DUMP_SAMPLE:
+        return flat.detach().float().cpu().numpy()
+    idx = np.unique(np.random.default_rng(0).integers(0, n, DUMP_SAMPLE))
+    return flat.detach()[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+
+
+def dump_outputs(path, kind, out, run, stepper):
+    """--dump-outputs: what the last timed step handed its caller, as <path>/<name>.npy (about 17 MB in all).
+    train: loss, grad_norm, nan_flag and samples of the updated fp32 masters and of the gradients; fwd_bwd: loss, nan_flag
+    and the gradient sample; sample: the latents after the last denoising step."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if kind == "sample":
+        arrays = {"x": run.x.detach().float().cpu().numpy()}
+    else:
+        arrays = {k: out[k].detach().reshape(-1).double().cpu().numpy() for k in ("loss", "grad_norm", "nan_flag") if k in out}
+        arrays["grads_sample"] = _arena_sample(stepper.arena.flat)
+        if kind == "train":
+            arrays["params_sample"] = _arena_sample(stepper.params.flat)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -248,6 +288,9 @@ def main():
     ap.add_argument("--dtype", default=None, choices=["bf16", "fp32"])
     ap.add_argument("--grad-bucket-dtype", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--no-graph", action="store_true", help="sample mode: eager loop instead of hipGraph replay")
+    ap.add_argument("--full", action="store_true", help="after the headline: roofline leg, secondary configs and CPU baseline "
+                                                        "(each can be dropped again with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="skip the HIP-event roofline leg")
     ap.add_argument("--profile-steps", type=int, default=3, help="steps of the exclusive-kernel roofline leg")
@@ -261,7 +304,7 @@ def main():
                                                              "MAX reduce really execute - the exchange is the identity, its cost is not")
     ap.add_argument("--no-ddp-tune", action="store_true", help="data parallel: skip the start-up measurement that chooses between the overlapped "
                                                                "(with / without a CU reserve) and the deferred gradient exchange")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[1] / configs[4] legs of the default run")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[1] / configs[4] legs of a --full run")
     ap.add_argument("--dry-run", action="store_true", help="rendezvous check only: the ranks meet over gloo on the CPU, all-reduce a 1 "
                                                            "and rank 0 prints the world size (no GPU; tests/test_bench_cpu.py)")
     args = ap.parse_args()
@@ -455,16 +498,19 @@ def run_worker(args):
     if stepper.reducer is not None and kind != "sample" and not args.no_ddp_tune:
         stepper.reducer.autotune(one_step, trials=2 if args.rehearse else 3)      # (untimed, before the warm-up: every rank takes part)
     elapsed, out = timed(one_step, steps, warmup)
+    if args.dump_outputs and rank == 0:                  # (before any --full leg: those run more steps on the same model)
+        dump_outputs(args.dump_outputs, kind, out, run, stepper)
     if sample_mode:
         loss, flag = None, int(not bool(torch.isfinite(run.x).all().item()))
     else:
         loss, flag = float(out["loss"].item()), int(out["nan_flag"].item())
     peak = PEAK_BF16 if dtype_name == "bf16" else PEAK_F32
-    fam = families(prof_factory, args.profile_steps, peak) if not args.no_profile else None
+    fam = families(prof_factory, args.profile_steps, peak) if args.full and not args.no_profile else None
 
-    # ---- the other single-GPU BASELINE configs, same process, after the headline's timed region (N = 1 default run only) ----
+    # ---- the other single-GPU BASELINE configs, same process, after the headline's timed region (N = 1 --full run only) ----
     secondary = None
-    if world == 1 and kind == "train" and dtype_name == "bf16" and not args.no_secondary and not args.rehearse and args.batch is None:
+    if (args.full and world == 1 and kind == "train" and dtype_name == "bf16" and not args.no_secondary and not args.rehearse
+            and args.batch is None):
         secondary = {}
         build_id = _build_id()
         # configs[1]: forward + SmoothL1 + backward, exact-fp32 MFMA, batch 64
@@ -548,7 +594,7 @@ def run_worker(args):
             res["kernel_families"] = fam
         if secondary:
             res["secondary"] = secondary
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 res["cpu_baseline"] = cpu_baseline()
             except Exception as e:                      # noqa: BLE001

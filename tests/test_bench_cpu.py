@@ -54,3 +54,8 @@ def test_bench_relays_a_failed_rank():
                        timeout=300, env=e)
     assert r.returncode != 0
     assert "rank 1 (exit 3)" in r.stderr and "injected failure" in r.stderr, r.stderr[-2000:]
+
+
+def test_bench_offers_full_and_dump_outputs():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout, r.stdout
