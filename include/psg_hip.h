@@ -301,6 +301,16 @@ int psg_dropout_apply(const void* x, int64_t ldx, void* y, int64_t ldy, int64_t 
 int psg_attn_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                  void* o, int64_t ldo, float* lse, int B, int heads, int L, int S, int d, float scale,
                  float drop_p, uint64_t seed, int dtype, psg_stream_t stream);
+/* Forward with a key length per sample (the key-padding mask of a right-padded token batch, transformers'
+ * BertModel attention_mask): key s of sample b takes part in the softmax only when s < kv_len[b] (int32 [B] on the
+ * device, read by the kernels: no host synchronisation; values are clamped to [1, S]).  Key tiles past kv_len[b] are
+ * neither loaded nor computed; queries are not masked (every l < L is computed, padded ones included).  With
+ * kv_len[b] == S for every b the result is bit-identical to psg_attn_fwd.  Forward only: drop_p must be 0
+ * (PSG_ERR_ARG otherwise); lse may be NULL.  Same kernel families as psg_attn_fwd (bf16 MFMA, exact-fp32 MFMA, VALU),
+ * chosen by the forward's LDS need alone. */
+int psg_attn_fwd_varlen(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                        void* o, int64_t ldo, float* lse, int B, int heads, int L, int S, int d, float scale,
+                        float drop_p, uint64_t seed, int dtype, const int32_t* kv_len, psg_stream_t stream);
 /* Diagnostic: launches of psg_attn_fwd / psg_attn_bwd served so far by the bf16 MFMA kernels (head_dim 16 / 32 / 64 / 80 /
  * 160 / 320, 16-byte aligned rows), by the VALU kernels (other shapes) and by the exact-fp32 MFMA kernels (fp32, head_dim
  * 16 / 32 / 64 / 80 / 160 while K/V - and Q/dO for backward - fit LDS).  All paths draw the same dropout mask. */
@@ -315,6 +325,24 @@ int psg_attn_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const v
                  float* delta, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv,
                  int B, int heads, int L, int S, int d, float scale, float drop_p, uint64_t seed,
                  int dtype, psg_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Frozen BERT text encoder (src/models/text_encoder.py: transformers BertModel + projection + LayerNorm).
+ * The GEMMs are psg_conv_fwd Linears, the attention is psg_attn_fwd_varlen; these are the row kernels.
+ * Rows: 16-byte aligned starts (row strides multiples of 8 elements); gamma / beta / tables fp32.
+ * ------------------------------------------------------------------------- */
+/* y = LayerNorm(x [+ r]) * gamma + beta over each of `rows` rows of width N (multiple of 8, 8..4096): biased variance,
+ * eps inside the square root, fp32 statistics in a fixed reduction order.  x and r (may be NULL) have x_dtype, y has
+ * y_dtype (e.g. bf16 in, fp32 out for the encoder's final nn.LayerNorm). */
+int psg_layernorm(const void* x, int64_t ldx, const void* r, int64_t ldr, void* y, int64_t ldy, const float* gamma,
+                  const float* beta, int64_t rows, int N, float eps, int x_dtype, int y_dtype, psg_stream_t stream);
+/* BertEmbeddings in eval mode: row b*S+s of y = LayerNorm(word_emb[ids] + type_emb[type_ids] + pos_emb[s]) (transformers'
+ * summation order), y in `dtype`.  ids / type_ids: int64 [B*S] (type_ids NULL = all 0); tables fp32 row-major
+ * [vocab|max_pos|type_vocab][N].  An id outside [0, vocab) or type id outside [0, type_vocab) reads nothing and yields a
+ * row of NaN (the trainer's input check then skips the batch).  S > max_pos is PSG_ERR_SHAPE. */
+int psg_bert_embed_ln(const int64_t* ids, const int64_t* type_ids, const float* word_emb, const float* pos_emb,
+                      const float* type_emb, const float* gamma, const float* beta, void* y, int64_t ldy, int B, int S,
+                      int N, int vocab, int max_pos, int type_vocab, float eps, int dtype, psg_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Optimizer side — improved_diffusion_trainer.py:399-413

@@ -1,7 +1,7 @@
 """pokemon_sprite_generator_amd — MI355X-native U-Net denoising train step.
 
 Drop-in for the hot path of GabrieleConte/pokemon-sprite-generator
-(src/models/unet.py + src/training/improved_diffusion_trainer.py): the same
+(src/models/unet.py + src/training/improved_diffusion_trainer.py; the frozen VAE and BERT text encoder either side): the same
 Python surface, computed by hand-written gfx950 HIP kernels in libpsg_hip.so
 (C ABI: include/psg_hip.h).  Importing the package never touches the GPU; using
 any op without the built library raises (no CPU fallback).
@@ -14,8 +14,9 @@ from .ddp import BucketedAllReduce
 from .trainer import DiffusionStepper, DiffusionTrainer, ImprovedDiffusionTrainer
 from .inference import LatentGenerator, LinearNoiseScheduler, gradio_ddpm_sample
 from .vae import PokemonVAE, VAEDecoder, VAEEncoder
+from .text_encoder import TextEncoder
 
 __all__ = ["UNet", "UNetBlock", "ResBlock", "CrossAttentionBlock", "TimestepEmbedding", "NoiseScheduler",
            "ImprovedDiffusionTrainer", "DiffusionTrainer", "DiffusionStepper", "FusedAdamW", "GradArena", "ParamArena",
-           "BucketedAllReduce", "LatentGenerator", "LinearNoiseScheduler", "gradio_ddpm_sample", "PokemonVAE", "VAEEncoder", "VAEDecoder", "PsgError", "LIB_PATH"]
+           "BucketedAllReduce", "LatentGenerator", "LinearNoiseScheduler", "gradio_ddpm_sample", "PokemonVAE", "VAEEncoder", "VAEDecoder", "TextEncoder", "PsgError", "LIB_PATH"]
 __version__ = "0.1.0"

@@ -21,6 +21,7 @@ struct AttnP {
     float scale;
     uint32_t drop_thresh; float drop_scale; uint64_t seed;
     const uint64_t* seed_dev;
+    const int32_t* kv_len;     // psg_attn_fwd_varlen: keys s >= kv_len[b] of sample b are left out (NULL otherwise)
 };
 
 // dropout element index of P[bh][l][s]: each query row owns ceil(S/2) hash PAIRS (keys 2k, 2k+1 share one 32-bit hash),
@@ -43,7 +44,15 @@ __device__ __forceinline__ void stage_rows(float* dst, const T* base, int64_t ld
     }
 }
 
-template <typename T>
+// per-sample key bound of the forward kernels: S, or (VARLEN) kv_len[b] clamped to [1, S]
+template <bool VARLEN>
+__device__ __forceinline__ int key_end(const int32_t* kv_len, int b, int S) {
+    if (!VARLEN) return S;
+    const int n = kv_len[b];
+    return n < 1 ? 1 : (n > S ? S : n);
+}
+
+template <typename T, bool VARLEN = false>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnP p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int d = p.d, dp = d + 1;
@@ -58,12 +67,13 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnP p) {
     const T* vg = reinterpret_cast<const T*>(p.v) + (int64_t)b * p.S * p.ldv + h * d;
     T* og = reinterpret_cast<T*>(p.out) + (int64_t)b * p.L * p.ldo + h * d;
     const int tid = threadIdx.x;
+    const int Se = key_end<VARLEN>(p.kv_len, b, p.S);
 
     stage_rows<T>(Qs, qg, p.ldq, l0, AT_Q, p.L, d, p.scale);
     // scores
-    for (int s0 = 0; s0 < p.S; s0 += AT_KC) {
+    for (int s0 = 0; s0 < Se; s0 += AT_KC) {
         __syncthreads();
-        stage_rows<T>(KV, kg, p.ldk, s0, AT_KC, p.S, d, 1.0f);
+        stage_rows<T>(KV, kg, p.ldk, s0, AT_KC, Se, d, 1.0f);
         __syncthreads();
         const int kj = tid & 31, qa = tid >> 5, qb = qa + 8;
         const float* kr = KV + kj * dp;
@@ -71,7 +81,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnP p) {
         const float* q1 = Qs + qb * dp;
         float a0 = 0.f, a1 = 0.f;
         for (int e = 0; e < d; ++e) { const float kv = kr[e]; a0 += q0[e] * kv; a1 += q1[e] * kv; }
-        if (s0 + kj < p.S) { Ss[qa * Sp + s0 + kj] = a0; Ss[qb * Sp + s0 + kj] = a1; }
+        if (s0 + kj < Se) { Ss[qa * Sp + s0 + kj] = a0; Ss[qb * Sp + s0 + kj] = a1; }
     }
     __syncthreads();
     // row softmax: wave w handles rows 4w..4w+3
@@ -81,18 +91,18 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnP p) {
             const int l = l0 + r;
             float* row = Ss + r * Sp;
             float mx = -INFINITY;
-            for (int s = lane; s < p.S; s += 64) mx = fmaxf(mx, row[s]);
+            for (int s = lane; s < Se; s += 64) mx = fmaxf(mx, row[s]);
             mx = wave_max(mx);
             float sum = 0.f;
-            for (int s = lane; s < p.S; s += 64) { const float e = __expf(row[s] - mx); row[s] = e; sum += e; }
+            for (int s = lane; s < Se; s += 64) { const float e = __expf(row[s] - mx); row[s] = e; sum += e; }
             sum = wave_sum(sum);
             const float inv = 1.0f / sum;
-            for (int s = lane; s < p.S; s += 64) {
+            for (int s = lane; s < Se; s += 64) {
                 float pv = row[s] * inv;
                 if (p.drop_thresh && l < p.L) pv = drop_keep(eff_seed(p.seed, p.seed_dev), attn_idx(p, bh, l, s), p.drop_thresh) ? pv * p.drop_scale : 0.f;
                 row[s] = pv;
             }
-            if (lane == 0 && l < p.L) p.lse[(int64_t)bh * p.L + l] = mx + __logf(sum);
+            if (lane == 0 && l < p.L && (!VARLEN || p.lse)) p.lse[(int64_t)bh * p.L + l] = mx + __logf(sum);
         }
     }
     // O = P V
@@ -101,11 +111,11 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnP p) {
     float acc[AT_MAXC];
 #pragma unroll
     for (int c = 0; c < AT_MAXC; ++c) acc[c] = 0.f;
-    for (int s0 = 0; s0 < p.S; s0 += AT_KC) {
+    for (int s0 = 0; s0 < Se; s0 += AT_KC) {
         __syncthreads();
-        stage_rows<T>(KV, vg, p.ldv, s0, AT_KC, p.S, d, 1.0f);
+        stage_rows<T>(KV, vg, p.ldv, s0, AT_KC, Se, d, 1.0f);
         __syncthreads();
-        const int jn = min(AT_KC, p.S - s0);
+        const int jn = min(AT_KC, Se - s0);
         for (int j = 0; j < jn; ++j) {
             const float pv = Ss[qi * Sp + s0 + j];
             const float* vr = KV + j * dp + dd0;
@@ -333,11 +343,14 @@ struct AttnMP {
     float scale;
     uint32_t drop_thresh; float drop_scale; uint64_t seed;
     const uint64_t* seed_dev;
+    const int32_t* kv_len;     // psg_attn_fwd_varlen: keys s >= kv_len[b] of sample b are left out (NULL otherwise)
 };
 int attn_mfma_applicable(int L, int S, int d, int dtype, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo);
 int attn_mfma_init_attrs();
 int attn_mfma_fwd(const AttnMP& p, hipStream_t s);
 int attn_mfma_bwd(const AttnMP& p, hipStream_t s);
+int attn_mfma_fwd_applicable(int S, int d, int dtype, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo);
+int attn_mfma_fwd_varlen(const AttnMP& p, hipStream_t s);
 
 // attention_f32.hip (exact-fp32 matrix-core path)
 struct AttnFP {
@@ -349,11 +362,14 @@ struct AttnFP {
     float scale;
     uint32_t drop_thresh; float drop_scale; uint64_t seed;
     const uint64_t* seed_dev;
+    const int32_t* kv_len;     // psg_attn_fwd_varlen: keys s >= kv_len[b] of sample b are left out (NULL otherwise)
 };
 int attn_f32_applicable(int L, int S, int d, int dtype, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo);
 int attn_f32_init_attrs();
 int attn_f32_fwd(const AttnFP& p, hipStream_t s);
 int attn_f32_bwd(const AttnFP& p, hipStream_t s);
+int attn_f32_fwd_applicable(int S, int d, int dtype, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo);
+int attn_f32_fwd_varlen(const AttnFP& p, hipStream_t s);
 
 static AttnFP to_f32(const AttnP& a) {
     AttnFP m;
@@ -362,7 +378,7 @@ static AttnFP to_f32(const AttnP& a) {
     m.lse = a.lse; m.delta = a.delta;
     m.ldq = a.ldq; m.ldk = a.ldk; m.ldv = a.ldv; m.ldo = a.ldo; m.lddo = a.lddo; m.lddq = a.lddq; m.lddk = a.lddk; m.lddv = a.lddv;
     m.B = a.B; m.H = a.H; m.L = a.L; m.S = a.S; m.d = a.d; m.scale = a.scale;
-    m.drop_thresh = a.drop_thresh; m.drop_scale = a.drop_scale; m.seed = a.seed; m.seed_dev = a.seed_dev;
+    m.drop_thresh = a.drop_thresh; m.drop_scale = a.drop_scale; m.seed = a.seed; m.seed_dev = a.seed_dev; m.kv_len = a.kv_len;
     return m;
 }
 
@@ -373,7 +389,7 @@ static AttnMP to_mfma(const AttnP& a) {
     m.lse = a.lse; m.delta = a.delta;
     m.ldq = a.ldq; m.ldk = a.ldk; m.ldv = a.ldv; m.ldo = a.ldo; m.lddo = a.lddo; m.lddq = a.lddq; m.lddk = a.lddk; m.lddv = a.lddv;
     m.B = a.B; m.H = a.H; m.L = a.L; m.S = a.S; m.d = a.d; m.scale = a.scale;
-    m.drop_thresh = a.drop_thresh; m.drop_scale = a.drop_scale; m.seed = a.seed; m.seed_dev = a.seed_dev;
+    m.drop_thresh = a.drop_thresh; m.drop_scale = a.drop_scale; m.seed = a.seed; m.seed_dev = a.seed_dev; m.kv_len = a.kv_len;
     return m;
 }
 
@@ -391,6 +407,10 @@ int psg_attn_init_attrs(void) {
     SET_LDS(attn_dq_kernel<float>); SET_LDS(attn_dq_kernel<bf16_t>);
     SET_LDS(attn_dkv_kernel<float>); SET_LDS(attn_dkv_kernel<bf16_t>);
 #undef SET_LDS
+    void (*const varlen_f32)(const AttnP) = attn_fwd_kernel<float, true>;
+    void (*const varlen_bf16)(const AttnP) = attn_fwd_kernel<bf16_t, true>;
+    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(varlen_f32), hipFuncAttributeMaxDynamicSharedMemorySize, big));
+    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(varlen_bf16), hipFuncAttributeMaxDynamicSharedMemorySize, big));
     return PSG_OK;
 }
 
@@ -436,6 +456,37 @@ int psg_attn_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const v
     if (dtype == PSG_F32) hipLaunchKernelGGL(attn_fwd_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(attn_fwd_kernel<bf16_t>, grid, dim3(256), lds, (hipStream_t)stream, p);
     PSG_LAUNCH_CHECK("attn_fwd");
+    return PSG_OK;
+}
+
+int psg_attn_fwd_varlen(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
+                        int64_t ldo, float* lse, int B, int heads, int L, int S, int d, float scale, float drop_p, uint64_t seed,
+                        int dtype, const int32_t* kv_len, psg_stream_t stream) {
+    PSG_REQUIRE(q && k && v && o && kv_len, PSG_ERR_ARG, "attn_fwd_varlen: null pointer");
+    int rc = attn_check("attn_fwd_varlen", B, heads, L, S, d, dtype, ldq, ldk, ldv, ldo);
+    if (rc) return rc;
+    PSG_REQUIRE(drop_p == 0.f, PSG_ERR_ARG, "attn_fwd_varlen: forward-only entry, drop_p must be 0 (got %g)", (double)drop_p);
+    const size_t lds = fwd_lds(S, d);
+    PSG_REQUIRE(lds <= 150 * 1024, PSG_ERR_SHAPE, "attn_fwd_varlen: LDS need %zu too large", lds);
+    AttnP p = {};
+    p.q = q; p.k = k; p.v = v; p.out = o; p.lse = lse; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
+    p.B = B; p.H = heads; p.L = L; p.S = S; p.d = d; p.scale = scale;
+    p.drop_scale = 1.0f; p.seed = seed; p.kv_len = kv_len;
+    dim3 grid((L + AT_Q - 1) / AT_Q, B * heads);
+    // (the FLOP count is the padded problem's: the key lengths live on the device)
+    ProfScope prof(PROF_ATTN, 4.0 * (double)B * heads * L * S * d, (hipStream_t)stream, (double)B * heads * d * (2.0 * L + 2.0 * S) * (dtype == PSG_BF16 ? 2.0 : 4.0));
+    if ((g_attn_allow & 1) && attn_mfma_fwd_applicable(S, d, dtype, ldq, ldk, ldv, ldo) && aligned16(q) && aligned16(k) && aligned16(v) && aligned8(o)) {
+        ++g_attn_paths[0];
+        return attn_mfma_fwd_varlen(to_mfma(p), (hipStream_t)stream);
+    }
+    if ((g_attn_allow & 2) && f32_mfma_on() && attn_f32_fwd_applicable(S, d, dtype, ldq, ldk, ldv, ldo) && aligned16(q) && aligned16(k) && aligned16(v) && aligned16(o)) {
+        ++g_attn_paths[2];
+        return attn_f32_fwd_varlen(to_f32(p), (hipStream_t)stream);
+    }
+    ++g_attn_paths[1];
+    if (dtype == PSG_F32) hipLaunchKernelGGL((attn_fwd_kernel<float, true>), grid, dim3(256), lds, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, true>), grid, dim3(256), lds, (hipStream_t)stream, p);
+    PSG_LAUNCH_CHECK("attn_fwd_varlen");
     return PSG_OK;
 }
 

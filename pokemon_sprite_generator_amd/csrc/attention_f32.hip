@@ -26,6 +26,7 @@ struct AttnFP {
     float scale;
     uint32_t drop_thresh; float drop_scale; uint64_t seed;
     const uint64_t* seed_dev;
+    const int32_t* kv_len;                         // forward with per-sample key lengths (NULL otherwise)
 };
 
 __device__ __forceinline__ int acc_row32(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
@@ -85,7 +86,8 @@ __device__ __forceinline__ void acc_cols(const char* img, int stride, int row0, 
 }
 
 // ------------------------------------------------------------------------------------------------ forward
-template <int ND>
+// VARLEN: sample b's keys end at kv_len[b] (clamped to [1, S]); key tiles past it are neither staged nor computed
+template <int ND, bool VARLEN = false>
 __global__ __launch_bounds__(256, 1) void attn_fwd_f32(const AttnFP p) {
     constexpr int D = ND * 16, HD = D / 2, NDT = (D + 31) / 32, STR = D * 4 + 16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -98,11 +100,14 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_f32(const AttnFP p) {
     const float* kg = p.k + (int64_t)b * p.S * p.ldk + hd * D;
     const float* vg = p.v + (int64_t)b * p.S * p.ldv + hd * D;
     float* og = p.out + (int64_t)b * p.L * p.ldo + hd * D;
-    stage_f32(Ks, kg, p.ldk, 0, Sp, p.S, D, STR, tid, (int)blockDim.x);
-    stage_f32(Vs, vg, p.ldv, 0, Sp, p.S, D, STR, tid, (int)blockDim.x);
+    int Se = p.S;
+    if (VARLEN) { const int n = p.kv_len[b]; Se = n < 1 ? 1 : (n > p.S ? p.S : n); }
+    const int Spe = (Se + 31) & ~31;
+    stage_f32(Ks, kg, p.ldk, 0, Spe, Se, D, STR, tid, (int)blockDim.x);
+    stage_f32(Vs, vg, p.ldv, 0, Spe, Se, D, STR, tid, (int)blockDim.x);
     __syncthreads();
     const int fr = lane & 31, fh = lane >> 5;
-    const int nkt = Sp >> 5;
+    const int nkt = Spe >> 5;
     for (int qt = wave; qt * 32 < p.L; qt += (int)(blockDim.x >> 6)) {
         const int l = qt * 32 + fr;
         const bool lok = l < p.L;
@@ -128,7 +133,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_f32(const AttnFP p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int key = kt * 32 + acc_row32(r, fh);
-                st[r] = key < p.S ? st[r] * p.scale : -INFINITY;
+                st[r] = key < Se ? st[r] * p.scale : -INFINITY;
                 mx = fmaxf(mx, st[r]);
             }
             mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
@@ -158,7 +163,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_f32(const AttnFP p) {
         const float ltot = lsum + __shfl_xor(lsum, 32, 64);
         const float inv = 1.0f / ltot;
         if (lok) {
-            if (fh == 0) p.lse[(int64_t)bh * p.L + l] = m + __logf(ltot);
+            if (fh == 0 && (!VARLEN || p.lse)) p.lse[(int64_t)bh * p.L + l] = m + __logf(ltot);
 #pragma unroll
             for (int t = 0; t < NDT; ++t)
 #pragma unroll
@@ -373,7 +378,13 @@ int attn_f32_applicable(int L, int S, int d, int dtype, int64_t ldq, int64_t ldk
         default: hipLaunchKernelGGL(KERNEL<10>, __VA_ARGS__); break;     \
     }
 
+template <int ND> static int varlen_attr() {
+    void (*const k)(const AttnFP) = attn_fwd_f32<ND, true>;
+    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)F32_LDS_CAP));
+    return PSG_OK;
+}
 int attn_f32_init_attrs() {
+    { const int rc = varlen_attr<1>() | varlen_attr<2>() | varlen_attr<4>() | varlen_attr<5>() | varlen_attr<10>(); if (rc) return rc; }
 #define SET_LDS(K) PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)F32_LDS_CAP))
     SET_LDS(attn_fwd_f32<1>); SET_LDS(attn_fwd_f32<2>); SET_LDS(attn_fwd_f32<4>); SET_LDS(attn_fwd_f32<5>); SET_LDS(attn_fwd_f32<10>);
     SET_LDS(attn_dq_f32<1>); SET_LDS(attn_dq_f32<2>); SET_LDS(attn_dq_f32<4>); SET_LDS(attn_dq_f32<5>); SET_LDS(attn_dq_f32<10>);
@@ -385,6 +396,24 @@ int attn_f32_init_attrs() {
 int attn_f32_fwd(const AttnFP& p, hipStream_t s) {
     F32_DISPATCH(attn_fwd_f32, dim3(p.B * p.H), dim3(64 * f32_waves(p.L)), f32_lds(p.S, p.d), s, p);
     PSG_LAUNCH_CHECK("attn_fwd_f32");
+    return PSG_OK;
+}
+int attn_f32_fwd_applicable(int S, int d, int dtype, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo) {
+    if (dtype != PSG_F32 || !f32_nd(d)) return 0;
+    if (((ldq | ldk | ldv | ldo) & 3) != 0) return 0;
+    return f32_lds(S, d) <= F32_LDS_CAP;
+}
+int attn_f32_fwd_varlen(const AttnFP& p, hipStream_t s) {
+    const dim3 grid(p.B * p.H), block(64 * f32_waves(p.L));
+    const size_t lds = f32_lds(p.S, p.d);
+    switch (p.d) {
+        case 16: hipLaunchKernelGGL((attn_fwd_f32<1, true>), grid, block, lds, s, p); break;
+        case 32: hipLaunchKernelGGL((attn_fwd_f32<2, true>), grid, block, lds, s, p); break;
+        case 64: hipLaunchKernelGGL((attn_fwd_f32<4, true>), grid, block, lds, s, p); break;
+        case 80: hipLaunchKernelGGL((attn_fwd_f32<5, true>), grid, block, lds, s, p); break;
+        default: hipLaunchKernelGGL((attn_fwd_f32<10, true>), grid, block, lds, s, p); break;
+    }
+    PSG_LAUNCH_CHECK("attn_fwd_f32_varlen");
     return PSG_OK;
 }
 int attn_f32_bwd(const AttnFP& p, hipStream_t s) {

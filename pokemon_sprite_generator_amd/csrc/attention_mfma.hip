@@ -36,6 +36,7 @@ struct AttnMP {     // mirrored in attention.hip
     float scale;
     uint32_t drop_thresh; float drop_scale; uint64_t seed;
     const uint64_t* seed_dev;
+    const int32_t* kv_len;                         // forward with per-sample key lengths (NULL otherwise)
 };
 
 typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -95,7 +96,9 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* img, int stride, int row0,
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
-template <int ND>
+// VARLEN (psg_attn_fwd_varlen): sample b's keys end at kv_len[b] (clamped to [1, S]) instead of S - only the key tiles below
+// that bound are staged and computed, and the key-tail mask of the last one moves with it
+template <int ND, bool VARLEN = false>
 __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_fwd_mfma(const AttnMP p) {
     constexpr int NDT = (ND + 1) / 2;
     constexpr int D32 = NDT * 32;
@@ -112,12 +115,15 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_fwd_mfma(const At
     const bf16_t* kg = p.k + (int64_t)b * p.S * p.ldk + hd * d;
     const bf16_t* vg = p.v + (int64_t)b * p.S * p.ldv + hd * d;
     bf16_t* og = p.out + (int64_t)b * p.L * p.ldo + hd * d;
-    stage_tile(Ks, kg, p.ldk, 0, Sp, p.S, d, d, STR, tid, (int)blockDim.x);
-    stage_tile(Vs, vg, p.ldv, 0, Sp, p.S, d, d, STR, tid, (int)blockDim.x);
+    int Se = p.S;
+    if (VARLEN) { const int n = p.kv_len[b]; Se = n < 1 ? 1 : (n > p.S ? p.S : n); }
+    const int Spe = (Se + 31) & ~31;
+    stage_tile(Ks, kg, p.ldk, 0, Spe, Se, d, d, STR, tid, (int)blockDim.x);
+    stage_tile(Vs, vg, p.ldv, 0, Spe, Se, d, d, STR, tid, (int)blockDim.x);
     __syncthreads();
 
     const int fr = lane & 31, fh = lane >> 5;
-    const int nkt = Sp >> 5;
+    const int nkt = Spe >> 5;
     for (int qt = wave; qt * 32 < p.L; qt += (int)(blockDim.x >> 6)) {
         const int l = qt * 32 + fr;
         const bool lok = l < p.L;
@@ -146,14 +152,14 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_fwd_mfma(const At
                 st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], st, 0, 0, 0);
             }
             float mx = -INFINITY;
-            if (kt * 32 + 32 <= p.S) {                     // (wave-uniform) a full key tile: nothing to mask
+            if (kt * 32 + 32 <= Se) {                     // (wave-uniform) a full key tile: nothing to mask
 #pragma unroll
                 for (int r = 0; r < 16; ++r) { st[r] = st[r] * p.scale; mx = fmaxf(mx, st[r]); }
             } else {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = kt * 32 + acc_row(r, fh);
-                    st[r] = key < p.S ? st[r] * p.scale : -INFINITY;
+                    st[r] = key < Se ? st[r] * p.scale : -INFINITY;
                     mx = fmaxf(mx, st[r]);
                 }
             }
@@ -191,7 +197,7 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_fwd_mfma(const At
         const float ltot = lsum + __shfl_xor(lsum, 32, 64);
         const float inv = 1.0f / ltot;
         if (lok) {
-            if (fh == 0) p.lse[(int64_t)bh * p.L + l] = m + __logf(ltot);
+            if (fh == 0 && (!VARLEN || p.lse)) p.lse[(int64_t)bh * p.L + l] = m + __logf(ltot);
 #pragma unroll
             for (int t = 0; t < NDT; ++t)
 #pragma unroll
@@ -554,7 +560,13 @@ int attn_mfma_applicable(int L, int S, int d, int dtype, int64_t ldq, int64_t ld
         default: hipLaunchKernelGGL(KERNEL<20>, __VA_ARGS__); break;                                  \
     }
 
+template <int ND> static int varlen_attr() {
+    void (*const k)(const AttnMP) = attn_fwd_mfma<ND, true>;
+    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MFMA_LDS_CAP));
+    return PSG_OK;
+}
 int attn_mfma_init_attrs() {
+    { const int rc = varlen_attr<1>() | varlen_attr<2>() | varlen_attr<4>() | varlen_attr<5>() | varlen_attr<10>() | varlen_attr<20>(); if (rc) return rc; }
 #define SET_LDS(K) PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MFMA_LDS_CAP))
     SET_LDS(attn_fwd_mfma<1>); SET_LDS(attn_fwd_mfma<2>); SET_LDS(attn_fwd_mfma<4>); SET_LDS(attn_fwd_mfma<5>); SET_LDS(attn_fwd_mfma<10>); SET_LDS(attn_fwd_mfma<20>);
     SET_LDS(attn_dq_mfma<1>); SET_LDS(attn_dq_mfma<2>); SET_LDS(attn_dq_mfma<4>); SET_LDS(attn_dq_mfma<5>); SET_LDS(attn_dq_mfma<10>); SET_LDS(attn_dq_mfma<20>);
@@ -567,6 +579,25 @@ int attn_mfma_fwd(const AttnMP& p, hipStream_t s) {
     const int d = p.d;
     ND_DISPATCH(attn_fwd_mfma, dim3(p.B * p.H), dim3(64 * attn_waves(p.L)), fwd_lds_m(p.S, d), s, p);
     PSG_LAUNCH_CHECK("attn_fwd_mfma");
+    return PSG_OK;
+}
+int attn_mfma_fwd_applicable(int S, int d, int dtype, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo) {
+    if (dtype != PSG_BF16 || !nd_supported(d)) return 0;
+    if (((ldq | ldk | ldv | ldo) & 7) != 0) return 0;
+    return fwd_lds_m(S, d) <= MFMA_LDS_CAP;
+}
+int attn_mfma_fwd_varlen(const AttnMP& p, hipStream_t s) {
+    const dim3 grid(p.B * p.H), block(64 * attn_waves(p.L));
+    const size_t lds = fwd_lds_m(p.S, p.d);
+    switch (p.d) {
+        case 16: hipLaunchKernelGGL((attn_fwd_mfma<1, true>), grid, block, lds, s, p); break;
+        case 32: hipLaunchKernelGGL((attn_fwd_mfma<2, true>), grid, block, lds, s, p); break;
+        case 64: hipLaunchKernelGGL((attn_fwd_mfma<4, true>), grid, block, lds, s, p); break;
+        case 80: hipLaunchKernelGGL((attn_fwd_mfma<5, true>), grid, block, lds, s, p); break;
+        case 160: hipLaunchKernelGGL((attn_fwd_mfma<10, true>), grid, block, lds, s, p); break;
+        default: hipLaunchKernelGGL((attn_fwd_mfma<20, true>), grid, block, lds, s, p); break;
+    }
+    PSG_LAUNCH_CHECK("attn_fwd_mfma_varlen");
     return PSG_OK;
 }
 int attn_mfma_bwd(const AttnMP& p, hipStream_t s) {

@@ -1,0 +1,249 @@
+// Row kernels of the frozen BERT text encoder (reference: src/models/text_encoder.py, a transformers BertModel):
+//   psg_layernorm      y = LN(x [+ r]) * gamma + beta over rows of width N (BERT's two post-LNs per layer, the final
+//                      nn.LayerNorm of the TextEncoder);
+//   psg_bert_embed_ln  BertEmbeddings: LN(word_emb[id] + type_emb[type] + pos_emb[s]).
+// One wave per row (N = 768: 64 lanes x 12 values), four rows per workgroup and many workgroups per CU in flight.  A lane
+// holds its chunks of 8 consecutive values in registers from the load to the store: one pass over HBM each way.
+// Statistics are fp32 and reduced in a fixed order (per-lane chunk order, then the xor butterfly, which leaves every lane
+// with the same bits): the result does not depend on the launch geometry.  Mean first, then the centred second moment
+// (two passes over registers, biased variance, eps inside the square root, as torch's layer_norm).
+#include "psg_common.h"
+
+namespace psg {
+
+constexpr int LN_ROWS = 4;          // rows (waves) per workgroup
+constexpr int LN_MAXN = 4096;       // 64 lanes x 8 chunks x 8 values
+
+template <typename T> __device__ __forceinline__ void ld8(const T* p, float (&v)[8]);
+template <> __device__ __forceinline__ void ld8<float>(const float* p, float (&v)[8]) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+    v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
+}
+template <> __device__ __forceinline__ void ld8<bf16_t>(const bf16_t* p, float (&v)[8]) {
+    const bf16x8 a = *reinterpret_cast<const bf16x8*>(p);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = (float)a[j];
+}
+template <typename T> __device__ __forceinline__ void st8(T* p, const float (&v)[8]);
+template <> __device__ __forceinline__ void st8<float>(float* p, const float (&v)[8]) {
+    const f32x4 a = {v[0], v[1], v[2], v[3]}, b = {v[4], v[5], v[6], v[7]};
+    *reinterpret_cast<f32x4*>(p) = a;
+    *reinterpret_cast<f32x4*>(p + 4) = b;
+}
+template <> __device__ __forceinline__ void st8<bf16_t>(bf16_t* p, const float (&v)[8]) {
+    bf16x8 a;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a[j] = (bf16_t)v[j];
+    *reinterpret_cast<bf16x8*>(p) = a;
+}
+
+// normalise the row a wave holds (chunk i of the lane = columns 8*(lane + 64*i) .. +7, valid while < nch) and store it
+template <int CPL, typename TO>
+__device__ __forceinline__ void ln_store(float (&v)[CPL][8], int lane, int nch, int N, const float* __restrict__ gamma,
+                                         const float* __restrict__ beta, float eps, TO* yrow) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i)
+        if (lane + 64 * i < nch)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s += v[i][j];
+    const float mean = wave_sum(s) / (float)N;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i)
+        if (lane + 64 * i < nch)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { const float c = v[i][j] - mean; q += c * c; }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)N + eps);
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nch) {
+            float g[8], bb[8], o[8];
+            ld8<float>(gamma + 8 * c, g);
+            ld8<float>(beta + 8 * c, bb);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = (v[i][j] - mean) * rstd * g[j] + bb[j];
+            st8<TO>(yrow + 8 * c, o);
+        }
+    }
+}
+
+template <typename TI, typename TO, int CPL, bool RES>
+__global__ __launch_bounds__(64 * LN_ROWS) void layernorm_kernel(const TI* __restrict__ x, int64_t ldx, const TI* __restrict__ r,
+                                                                  int64_t ldr, TO* __restrict__ y, int64_t ldy,
+                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                  int64_t rows, int N, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * LN_ROWS + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int nch = N >> 3;
+    float v[CPL][8];
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nch) {
+            ld8<TI>(x + row * ldx + 8 * c, v[i]);
+            if (RES) {
+                float t[8];
+                ld8<TI>(r + row * ldr + 8 * c, t);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[i][j] += t[j];
+            }
+        }
+    }
+    ln_store<CPL, TO>(v, lane, nch, N, gamma, beta, eps, y + row * ldy);
+}
+
+// BertEmbeddings (eval): inputs_embeds + token_type_embeddings, then + position_embeddings (transformers' order), LayerNorm.
+// Row t = b*S + s has position s.  An id outside [0, vocab) or a type id outside [0, type_vocab) reads nothing and yields a
+// NaN row: the caller's NaN check then drops the batch.
+template <typename TO, int CPL>
+__global__ __launch_bounds__(64 * LN_ROWS) void embed_ln_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ type_ids,
+                                                                 const float* __restrict__ wemb, const float* __restrict__ pemb,
+                                                                 const float* __restrict__ temb, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, TO* __restrict__ y, int64_t ldy,
+                                                                 int64_t rows, int S, int N, int vocab, int type_vocab, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * LN_ROWS + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int nch = N >> 3;
+    const int s = (int)(row % S);
+    const int64_t id = ids[row];
+    const int64_t tt = type_ids ? type_ids[row] : 0;
+    TO* yrow = y + row * ldy;
+    if (id < 0 || id >= vocab || tt < 0 || tt >= type_vocab) {      // (wave-uniform)
+        float o[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = __builtin_nanf("");
+        for (int c = lane; c < nch; c += 64) st8<TO>(yrow + 8 * c, o);
+        return;
+    }
+    const float* wr = wemb + id * N;
+    const float* tr = temb + tt * N;
+    const float* pr = pemb + (int64_t)s * N;
+    float v[CPL][8];
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nch) {
+            float a[8], t[8], p[8];
+            ld8<float>(wr + 8 * c, a);
+            ld8<float>(tr + 8 * c, t);
+            ld8<float>(pr + 8 * c, p);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[i][j] = (a[j] + t[j]) + p[j];
+        }
+    }
+    ln_store<CPL, TO>(v, lane, nch, N, gamma, beta, eps, yrow);
+}
+
+template <typename TI, typename TO, int CPL>
+static void launch_ln(const void* x, int64_t ldx, const void* r, int64_t ldr, void* y, int64_t ldy, const float* gamma,
+                      const float* beta, int64_t rows, int N, float eps, hipStream_t s) {
+    const dim3 grid((unsigned)((rows + LN_ROWS - 1) / LN_ROWS)), block(64 * LN_ROWS);
+    if (r)
+        hipLaunchKernelGGL((layernorm_kernel<TI, TO, CPL, true>), grid, block, 0, s, (const TI*)x, ldx, (const TI*)r, ldr, (TO*)y, ldy,
+                           gamma, beta, rows, N, eps);
+    else
+        hipLaunchKernelGGL((layernorm_kernel<TI, TO, CPL, false>), grid, block, 0, s, (const TI*)x, ldx, (const TI*)nullptr, (int64_t)0,
+                           (TO*)y, ldy, gamma, beta, rows, N, eps);
+}
+
+template <typename TI, typename TO>
+static void ln_dispatch(int cpl, const void* x, int64_t ldx, const void* r, int64_t ldr, void* y, int64_t ldy, const float* gamma,
+                        const float* beta, int64_t rows, int N, float eps, hipStream_t s) {
+    switch (cpl) {
+        case 1: launch_ln<TI, TO, 1>(x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s); break;
+        case 2: launch_ln<TI, TO, 2>(x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s); break;
+        case 3: launch_ln<TI, TO, 3>(x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s); break;
+        case 4: launch_ln<TI, TO, 4>(x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s); break;
+        case 5: launch_ln<TI, TO, 5>(x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s); break;
+        case 6: launch_ln<TI, TO, 6>(x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s); break;
+        case 7: launch_ln<TI, TO, 7>(x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s); break;
+        default: launch_ln<TI, TO, 8>(x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s); break;
+    }
+}
+
+template <typename TO, int CPL>
+static void launch_embed(const int64_t* ids, const int64_t* type_ids, const float* wemb, const float* pemb, const float* temb,
+                         const float* gamma, const float* beta, void* y, int64_t ldy, int64_t rows, int S, int N, int vocab,
+                         int type_vocab, float eps, hipStream_t s) {
+    hipLaunchKernelGGL((embed_ln_kernel<TO, CPL>), dim3((unsigned)((rows + LN_ROWS - 1) / LN_ROWS)), dim3(64 * LN_ROWS), 0, s, ids,
+                       type_ids, wemb, pemb, temb, gamma, beta, (TO*)y, ldy, rows, S, N, vocab, type_vocab, eps);
+}
+
+template <typename TO>
+static void embed_dispatch(int cpl, const int64_t* ids, const int64_t* type_ids, const float* wemb, const float* pemb,
+                           const float* temb, const float* gamma, const float* beta, void* y, int64_t ldy, int64_t rows, int S,
+                           int N, int vocab, int type_vocab, float eps, hipStream_t s) {
+#define PSG_EMBED_CASE(C) launch_embed<TO, C>(ids, type_ids, wemb, pemb, temb, gamma, beta, y, ldy, rows, S, N, vocab, type_vocab, eps, s)
+    switch (cpl) {
+        case 1: PSG_EMBED_CASE(1); break;
+        case 2: PSG_EMBED_CASE(2); break;
+        case 3: PSG_EMBED_CASE(3); break;
+        case 4: PSG_EMBED_CASE(4); break;
+        case 5: PSG_EMBED_CASE(5); break;
+        case 6: PSG_EMBED_CASE(6); break;
+        case 7: PSG_EMBED_CASE(7); break;
+        default: PSG_EMBED_CASE(8); break;
+    }
+#undef PSG_EMBED_CASE
+}
+
+static int row_width_check(const char* who, int N) {
+    PSG_REQUIRE(N >= 8 && N <= LN_MAXN && N % 8 == 0, PSG_ERR_SHAPE, "%s: row width N=%d must be a multiple of 8 in [8, %d]", who, N, LN_MAXN);
+    return PSG_OK;
+}
+
+}  // namespace psg
+using namespace psg;
+
+extern "C" {
+
+int psg_layernorm(const void* x, int64_t ldx, const void* r, int64_t ldr, void* y, int64_t ldy, const float* gamma,
+                  const float* beta, int64_t rows, int N, float eps, int x_dtype, int y_dtype, psg_stream_t stream) {
+    PSG_REQUIRE(x && y && gamma && beta, PSG_ERR_ARG, "layernorm: null pointer");
+    PSG_REQUIRE((x_dtype == PSG_F32 || x_dtype == PSG_BF16) && (y_dtype == PSG_F32 || y_dtype == PSG_BF16), PSG_ERR_DTYPE,
+                "layernorm: dtypes %d -> %d", x_dtype, y_dtype);
+    { const int rc = row_width_check("layernorm", N); if (rc) return rc; }
+    PSG_REQUIRE(rows > 0 && rows <= (int64_t)LN_ROWS * 0x7FFFFFFF, PSG_ERR_SHAPE, "layernorm: rows=%ld", (long)rows);
+    PSG_REQUIRE(eps >= 0.f, PSG_ERR_ARG, "layernorm: eps %g", (double)eps);
+    PSG_REQUIRE(ldx >= N && ldy >= N && (!r || ldr >= N), PSG_ERR_SHAPE, "layernorm: row stride < N");
+    PSG_REQUIRE(((ldx | ldy | (r ? ldr : 0)) & 7) == 0 && aligned16(x) && aligned16(y) && (!r || aligned16(r)) && aligned16(gamma) &&
+                aligned16(beta), PSG_ERR_ALIGN, "layernorm: rows must start on 16-byte boundaries (strides multiples of 8)");
+    const int cpl = (N / 8 + 63) / 64;
+    hipStream_t s = (hipStream_t)stream;
+    if (x_dtype == PSG_F32) {
+        if (y_dtype == PSG_F32) ln_dispatch<float, float>(cpl, x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s);
+        else ln_dispatch<float, bf16_t>(cpl, x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s);
+    } else {
+        if (y_dtype == PSG_F32) ln_dispatch<bf16_t, float>(cpl, x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s);
+        else ln_dispatch<bf16_t, bf16_t>(cpl, x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s);
+    }
+    PSG_LAUNCH_CHECK("layernorm");
+    return PSG_OK;
+}
+
+int psg_bert_embed_ln(const int64_t* ids, const int64_t* type_ids, const float* word_emb, const float* pos_emb,
+                      const float* type_emb, const float* gamma, const float* beta, void* y, int64_t ldy, int B, int S, int N,
+                      int vocab, int max_pos, int type_vocab, float eps, int dtype, psg_stream_t stream) {
+    PSG_REQUIRE(ids && word_emb && pos_emb && type_emb && gamma && beta && y, PSG_ERR_ARG, "bert_embed_ln: null pointer");
+    PSG_REQUIRE(dtype == PSG_F32 || dtype == PSG_BF16, PSG_ERR_DTYPE, "bert_embed_ln: dtype %d", dtype);
+    { const int rc = row_width_check("bert_embed_ln", N); if (rc) return rc; }
+    PSG_REQUIRE(B > 0 && S > 0 && vocab > 0 && type_vocab > 0 && max_pos > 0, PSG_ERR_SHAPE, "bert_embed_ln: non-positive dimension");
+    PSG_REQUIRE(S <= max_pos, PSG_ERR_SHAPE, "bert_embed_ln: S=%d exceeds the %d position embeddings", S, max_pos);
+    PSG_REQUIRE(eps >= 0.f, PSG_ERR_ARG, "bert_embed_ln: eps %g", (double)eps);
+    PSG_REQUIRE(ldy >= N, PSG_ERR_SHAPE, "bert_embed_ln: row stride < N");
+    PSG_REQUIRE((ldy & 7) == 0 && aligned16(y) && aligned16(word_emb) && aligned16(pos_emb) && aligned16(type_emb) && aligned16(gamma) &&
+                aligned16(beta), PSG_ERR_ALIGN, "bert_embed_ln: tables and rows must start on 16-byte boundaries");
+    const int cpl = (N / 8 + 63) / 64;
+    const int64_t rows = (int64_t)B * S;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == PSG_F32) embed_dispatch<float>(cpl, ids, type_ids, word_emb, pos_emb, type_emb, gamma, beta, y, ldy, rows, S, N, vocab, type_vocab, eps, s);
+    else embed_dispatch<bf16_t>(cpl, ids, type_ids, word_emb, pos_emb, type_emb, gamma, beta, y, ldy, rows, S, N, vocab, type_vocab, eps, s);
+    PSG_LAUNCH_CHECK("bert_embed_ln");
+    return PSG_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,274 @@
+"""Frozen BERT text encoder on the MI355X kernels (reference: src/models/text_encoder.py).
+
+The reference wraps a transformers `BertModel` (+ `projection`, Linear or Identity, + `layer_norm`) and returns the
+normalised `last_hidden_state` [B, S, hidden_dim] of a right-padded token batch.  Stage 2 calls it for every training
+and validation batch and every monitoring sample (improved_diffusion_trainer.py:155,202-208,352,461,583) with the model
+frozen; this class computes that forward on the library's kernels:
+
+  psg_bert_embed_ln        word + token-type + position embeddings, LayerNorm                   1 launch
+  per layer (post-LN):     QKV Linear over one packed [3H][H] prepared weight (fp32 bias)        7 launches
+                           psg_attn_fwd_varlen (key length per sample = attention_mask.sum(1))
+                           out-proj Linear + bias + residual, psg_layernorm
+                           FFN-1 Linear + bias + erf-GELU, FFN-2 Linear + bias + residual, psg_layernorm
+  projection Linear (hidden_dim != BERT width), final psg_layernorm written in fp32             1-2 launches
+
+Right padding makes the key-length vector exactly the reference's additive `finfo.min` mask: a padded key's probability
+is 0 there too, and outputs at padded positions (which the U-Net cross-attends to) are computed like the reference's.
+
+Parameters carry the reference module's names and shapes (`bert.embeddings.*`, `bert.encoder.layer.N.*`, `bert.pooler.*`,
+`projection.*` when present, `layer_norm.*`), so a stage-1 checkpoint's 'text_encoder_state_dict' loads unchanged.  The
+pooler is kept for checkpoint interchange only: the reference returns `last_hidden_state`, never the pooled output.
+
+Inference only (`torch.no_grad()`): `finetune_strategy` is accepted for signature compatibility and validated, but the
+parameters stay frozen here - fine-tuning the text encoder (stage 3) stays on the reference class.  `transformers` is used
+on the host only, to load a pretrained tokenizer / config / state dict (`model_name`) and to tokenize (`forward`);
+`encode_ids` needs neither it nor any host synchronisation.
+"""
+import torch
+import torch.nn as nn
+
+from . import _lib, ops
+from ._lib import ACT_GELU, ACT_NONE, check, dtype_code, ptr, stream_ptr
+from .vae import _prep, _prepared
+
+# keys of a `bert_config` dict (transformers.BertConfig attribute names)
+CONFIG_KEYS = ("hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size", "vocab_size",
+               "max_position_embeddings", "type_vocab_size", "layer_norm_eps")
+FINETUNE_STRATEGIES = ("none", "minimal", "partial", "full")
+MAX_LENGTH = 256                    # the reference tokenizer call's max_length (text_encoder.py forward)
+
+
+def config_dict(cfg):
+    """A transformers BertConfig (or a dict) -> the plain dict this class takes; rejects what the kernels do not compute."""
+    get = (lambda k: cfg[k]) if isinstance(cfg, dict) else (lambda k: getattr(cfg, k))
+    out = {k: get(k) for k in CONFIG_KEYS}
+    out["layer_norm_eps"] = float(out["layer_norm_eps"])
+    for k in CONFIG_KEYS[:-1]:
+        out[k] = int(out[k])
+    if not isinstance(cfg, dict):
+        act = getattr(cfg, "hidden_act", "gelu")
+        pet = getattr(cfg, "position_embedding_type", "absolute") or "absolute"
+        if act != "gelu" or pet != "absolute":
+            raise _lib.PsgError(f"TextEncoder computes BERT with hidden_act='gelu' and absolute positions (got {act!r}, {pet!r})")
+    if out["hidden_size"] % out["num_attention_heads"]:
+        raise _lib.PsgError("hidden_size must be a multiple of num_attention_heads")
+    return out
+
+
+def _from_pretrained(model_name):
+    """(tokenizer, config dict, BertModel state dict) from the local transformers cache - host side only."""
+    from transformers import BertModel, BertTokenizer
+    tok = BertTokenizer.from_pretrained(model_name)
+    m = BertModel.from_pretrained(model_name)
+    cfg = config_dict(m.config)
+    sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    del m
+    return tok, cfg, sd
+
+
+# containers with transformers' attribute names (state-dict keys only; nothing here runs torch math)
+class _SelfAttention(nn.Module):
+    def __init__(self, H):
+        super().__init__()
+        self.query, self.key, self.value = nn.Linear(H, H), nn.Linear(H, H), nn.Linear(H, H)
+
+
+class _DenseLN(nn.Module):
+    def __init__(self, i, o, eps):
+        super().__init__()
+        self.dense = nn.Linear(i, o)
+        self.LayerNorm = nn.LayerNorm(o, eps=eps)
+
+
+class _Attention(nn.Module):
+    def __init__(self, H, eps):
+        super().__init__()
+        self.self = _SelfAttention(H)
+        self.output = _DenseLN(H, H, eps)
+
+
+class _Intermediate(nn.Module):
+    def __init__(self, H, I):
+        super().__init__()
+        self.dense = nn.Linear(H, I)
+
+
+class _Layer(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        H, I, eps = c["hidden_size"], c["intermediate_size"], c["layer_norm_eps"]
+        self.attention = _Attention(H, eps)
+        self.intermediate = _Intermediate(H, I)
+        self.output = _DenseLN(I, H, eps)
+
+
+class _Encoder(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.layer = nn.ModuleList([_Layer(c) for _ in range(c["num_hidden_layers"])])
+
+
+class _Embeddings(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        H = c["hidden_size"]
+        self.word_embeddings = nn.Embedding(c["vocab_size"], H, padding_idx=0)
+        self.position_embeddings = nn.Embedding(c["max_position_embeddings"], H)
+        self.token_type_embeddings = nn.Embedding(c["type_vocab_size"], H)
+        self.LayerNorm = nn.LayerNorm(H, eps=c["layer_norm_eps"])
+
+
+class _Pooler(nn.Module):
+    def __init__(self, H):
+        super().__init__()
+        self.dense = nn.Linear(H, H)
+
+
+class _Bert(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.config = dict(c)
+        self.embeddings = _Embeddings(c)
+        self.encoder = _Encoder(c)
+        self.pooler = _Pooler(c["hidden_size"])
+
+
+def _linear(x, wf, bias, cout, act=ACT_NONE, residual=None, out=None):
+    """[M, Cin] rows (16-byte aligned, contiguous) -> [M, cout] in x's dtype: psg_conv_fwd as a Linear with fused epilogue."""
+    lib = ops._lib_for(x)
+    M, cin = x.shape
+    y = torch.empty((M, cout), dtype=x.dtype, device=x.device) if out is None else out
+    ops._conv_launch(lib, x.dtype, x, cin, wf, 0, y, cout, (M, 1, 1, 1, 1, 1, 1, 0), cin, cout, bias=bias,
+                     residual=residual, ld_res=cout if residual is not None else 0, act=act)
+    return y
+
+
+def layer_norm(x, weight, bias, eps, residual=None, out_dtype=None):
+    """y = LayerNorm(x [+ residual]) * weight + bias over the last dimension (psg_layernorm); x [..., N] contiguous."""
+    lib = ops._lib_for(x)
+    N = x.shape[-1]
+    rows = x.numel() // N
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    check(lib.psg_layernorm(ptr(x), N, ptr(residual), N if residual is not None else 0, ptr(y), N, ptr(weight), ptr(bias), rows, N,
+                            float(eps), dtype_code(x.dtype), dtype_code(out_dtype), stream_ptr()), "psg_layernorm")
+    return y
+
+
+def attention_varlen(qkv, kv_len, heads):
+    """Self-attention of packed projections qkv [B, S, 3E] with the keys of sample b limited to kv_len[b] (int32, device)."""
+    lib = ops._lib_for(qkv)
+    B, S, E3 = qkv.shape
+    E = E3 // 3
+    d = E // heads
+    esz = qkv.element_size()
+    o = torch.empty((B, S, E), dtype=qkv.dtype, device=qkv.device)
+    base = qkv.data_ptr()
+    check(lib.psg_attn_fwd_varlen(base, E3, base + E * esz, E3, base + 2 * E * esz, E3, ptr(o), E, None, B, heads, S, S, d,
+                                  float(d) ** -0.5, 0.0, 0, dtype_code(qkv.dtype), ptr(kv_len), stream_ptr()), "psg_attn_fwd_varlen")
+    return o
+
+
+class TextEncoder(nn.Module):
+    """src/models/text_encoder.py:TextEncoder (same constructor arguments, same state-dict keys, same forward), frozen."""
+
+    def __init__(self, model_name='google-bert/bert-base-uncased', hidden_dim=768, finetune_strategy='minimal', *,
+                 compute_dtype=torch.float32, tokenizer=None, bert_config=None):
+        super().__init__()
+        if finetune_strategy not in FINETUNE_STRATEGIES:
+            raise ValueError(f"Unknown finetune_strategy: {finetune_strategy}")
+        state = None
+        if bert_config is None:                          # pretrained weights and tokenizer from the local HF cache
+            tok, cfg, state = _from_pretrained(model_name)
+            tokenizer = tokenizer if tokenizer is not None else tok
+        else:
+            cfg = config_dict(bert_config)
+        self.model_name, self.finetune_strategy = model_name, finetune_strategy
+        self.compute_dtype = compute_dtype
+        self.tokenizer = tokenizer
+        self.bert = _Bert(cfg)
+        self.bert_hidden_size = cfg["hidden_size"]
+        self.hidden_dim = hidden_dim
+        self.projection = nn.Linear(self.bert_hidden_size, hidden_dim) if self.bert_hidden_size != hidden_dim else nn.Identity()
+        self.layer_norm = nn.LayerNorm(hidden_dim)
+        if state is not None:
+            own = self.bert.state_dict()
+            self.bert.load_state_dict({k: v for k, v in state.items() if k in own}, strict=True)
+        for p in self.parameters():
+            p.requires_grad = False
+        self.eval()
+        self._cache = {}
+
+    @classmethod
+    def from_reference(cls, enc, compute_dtype=torch.float32):
+        """A reference TextEncoder instance -> this class with its tokenizer, configuration and weights (copied)."""
+        obj = cls(hidden_dim=enc.layer_norm.normalized_shape[0], finetune_strategy=getattr(enc, "finetune_strategy", "minimal"),
+                  compute_dtype=compute_dtype, tokenizer=enc.tokenizer, bert_config=config_dict(enc.bert.config))
+        own = obj.state_dict()
+        obj.load_state_dict({k: v.detach().clone() for k, v in enc.state_dict().items() if k in own}, strict=True)
+        return obj.to(next(enc.parameters()).device)
+
+    # -- prepared weights (rebuilt when a parameter changes: load_state_dict, .to()) --------------------------------
+    def _layer_weights(self, i, dt):
+        lay = self.bert.encoder.layer[i]
+        sa, ao, it, ou = lay.attention.self, lay.attention.output.dense, lay.intermediate.dense, lay.output.dense
+        qkv = [sa.query.weight, sa.key.weight, sa.value.weight]
+        return (
+            _prepared(self._cache, ("qkv", i, dt), qkv + [sa.query.bias, sa.key.bias, sa.value.bias],
+                      lambda: (_prep(torch.cat(qkv, 0)[:, :, None, None], dt),
+                               torch.cat([sa.query.bias, sa.key.bias, sa.value.bias]).detach().float().contiguous())),
+            _prepared(self._cache, ("o", i, dt), [ao.weight], lambda: _prep(ao.weight[:, :, None, None], dt)),
+            _prepared(self._cache, ("f1", i, dt), [it.weight], lambda: _prep(it.weight[:, :, None, None], dt)),
+            _prepared(self._cache, ("f2", i, dt), [ou.weight], lambda: _prep(ou.weight[:, :, None, None], dt)),
+        )
+
+    def launches_per_call(self):
+        """Kernel launches of one encode_ids call."""
+        return 1 + 7 * len(self.bert.encoder.layer) + (1 if isinstance(self.projection, nn.Linear) else 0) + 1
+
+    @torch.no_grad()
+    def encode_ids(self, input_ids, attention_mask, token_type_ids=None):
+        """Token ids [B, S] + attention mask [B, S] (right padding: ones then zeros) -> [B, S, hidden_dim] fp32."""
+        dev = self.layer_norm.weight.device
+        if dev.type != "cuda":
+            raise _lib.PsgError("TextEncoder (MI355X build) needs its parameters on the GPU; there is no CPU fallback")
+        c = self.bert.config
+        dt = self.compute_dtype
+        H, heads, I = c["hidden_size"], c["num_attention_heads"], c["intermediate_size"]
+        lib = ops._lib_for(self.layer_norm.weight)
+        ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
+        B, S = ids.shape
+        kv_len = attention_mask.to(dev).sum(1, dtype=torch.int32).contiguous()      # stays on the device
+        tt = None if token_type_ids is None else token_type_ids.to(device=dev, dtype=torch.int64).contiguous()
+        emb = self.bert.embeddings
+        x = torch.empty((B * S, H), dtype=dt, device=dev)
+        check(lib.psg_bert_embed_ln(ptr(ids), ptr(tt), ptr(emb.word_embeddings.weight), ptr(emb.position_embeddings.weight),
+                                    ptr(emb.token_type_embeddings.weight), ptr(emb.LayerNorm.weight), ptr(emb.LayerNorm.bias), ptr(x), H,
+                                    B, S, H, c["vocab_size"], c["max_position_embeddings"], c["type_vocab_size"], c["layer_norm_eps"],
+                                    dtype_code(dt), stream_ptr()), "psg_bert_embed_ln")
+        eps = c["layer_norm_eps"]
+        for i, lay in enumerate(self.bert.encoder.layer):
+            (wqkv, bqkv), wo, w1, w2 = self._layer_weights(i, dt)
+            ao, it, ou = lay.attention.output, lay.intermediate.dense, lay.output
+            qkv = _linear(x, wqkv, bqkv, 3 * H)
+            ctx = attention_varlen(qkv.view(B, S, 3 * H), kv_len, heads).view(B * S, H)
+            h = layer_norm(_linear(ctx, wo, ao.dense.bias, H, residual=x), ao.LayerNorm.weight, ao.LayerNorm.bias, eps)
+            u = _linear(h, w1, it.bias, I, act=ACT_GELU)
+            x = layer_norm(_linear(u, w2, ou.dense.bias, H, residual=h), ou.LayerNorm.weight, ou.LayerNorm.bias, eps)
+        if isinstance(self.projection, nn.Linear):
+            wp = _prepared(self._cache, ("proj", dt), [self.projection.weight], lambda: _prep(self.projection.weight[:, :, None, None], dt))
+            x = _linear(x, wp, self.projection.bias, self.hidden_dim)
+        y = layer_norm(x, self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps, out_dtype=torch.float32)
+        return y.view(B, S, self.hidden_dim)
+
+    def tokenize(self, text_list):
+        """The reference's tokenizer call (padding to the longest text, truncation at 256 tokens), right padding enforced."""
+        if self.tokenizer is None:
+            raise _lib.PsgError("TextEncoder built from bert_config= without tokenizer=: call encode_ids with token ids")
+        self.tokenizer.padding_side = "right"          # the key-length form of the mask assumes it (BERT's default)
+        return self.tokenizer(list(text_list), return_tensors="pt", padding=True, truncation=True, max_length=MAX_LENGTH)
+
+    @torch.no_grad()
+    def forward(self, text_list):
+        inputs = self.tokenize(text_list)
+        return self.encode_ids(inputs["input_ids"], inputs["attention_mask"], inputs.get("token_type_ids"))

@@ -471,6 +471,9 @@ class ImprovedDiffusionTrainer:
         # monitoring images then carry fp32-grade error, 1e-3, not bf16's 3e-2); `mi355x.vae_dtype: bf16` trades that for speed
         self.vae_dtype = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp32": torch.float32,
                           "float32": torch.float32}[str(mi.get("vae_dtype", "fp32"))]
+        # the frozen BERT text encoder likewise (`mi355x.text_dtype`, default fp32 = the reference's precision)
+        self.text_dtype = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp32": torch.float32,
+                           "float32": torch.float32}[str(mi.get("text_dtype", "fp32"))]
         self._grad_bucket_dtype = {"fp32": torch.float32, "bf16": torch.bfloat16}[str(mi.get("grad_bucket_dtype", "fp32"))]
         # data parallel: measure the gradient-exchange mode on the first training batch (state is restored: no training happens)
         self._ddp_autotune = bool(mi.get("ddp_autotune", True))
@@ -518,6 +521,9 @@ class ImprovedDiffusionTrainer:
             from . import vae
             cls = getattr(vae, name)
             return lambda *a, **k: cls(*a, compute_dtype=self.vae_dtype, **k)
+        if name == "TextEncoder":                        # the frozen BERT text encoder as well (text_encoder.py)
+            from .text_encoder import TextEncoder
+            return lambda *a, **k: TextEncoder(*a, compute_dtype=self.text_dtype, **k)
         try:                                   # the reference package, when this class is dropped into its tree
             import importlib
             mod = importlib.import_module({"create_data_loaders": "src.data"}.get(name, "src.models"))
@@ -530,8 +536,9 @@ class ImprovedDiffusionTrainer:
         mc = self.config["model"]
         latent_dim = mc.get("latent_dim", 8)
         # Each collaborator is taken from `components=` when injected (an INSTANCE: `text_encoder`, `vae_encoder`,
-        # `vae_decoder`), else built the reference's way (:150-225): BERT text encoder from the reference package, the frozen
-        # VAE from THIS package's kernels, both loaded from the stage-1 checkpoint.  Any subset may be injected.
+        # `vae_decoder`; or a `TextEncoder` / `VAEEncoder` / `VAEDecoder` factory), else built the reference's way (:150-225) from
+        # THIS package's kernels - BERT text encoder and frozen VAE - both loaded from the stage-1 checkpoint.  Any subset may be
+        # injected.
         comps = self._components
         ckpt = {}
         if not all(k in comps for k in ("text_encoder", "vae_encoder", "vae_decoder")):
