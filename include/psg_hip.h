@@ -239,6 +239,13 @@ int64_t psg_conv_fwd_workspace_bytes(const psg_conv_desc* d);   /* 0: the launch
  * to the per-tile kernel instead (A/B runs, the bitwise test); psg_conv_pw_launches counts launches the persistent kernel took. */
 int psg_conv_set_pw(int on);
 int64_t psg_conv_pw_launches(void);
+/* Stride-1 3x3 pad-1 bf16 launches (forward and data gradient) may run in border-class order: the output positions go class
+ * by class (first / interior / last row x column), and each tile walks only the filter taps its class can reach (4, 6 or 9)
+ * - the skipped taps read only padding, so the results are the same bits.  psg_conv_set_tapclass(0) turns it off (A/B runs,
+ * the bitwise test), 1 (default) lets the tile plan decide per launch, 2 uses it on every launch it applies to;
+ * psg_conv_tapclass_launches counts the launches that ran in class order. */
+int psg_conv_set_tapclass(int on);
+int64_t psg_conv_tapclass_launches(void);
 
 /* Weight gradient — convolution_backward's wgrad for the same layers.
  * dw (fp32) = sum_m dy[m,co] * x[pix(m,kh,kw), ci], stored in the parameter's own memory order:

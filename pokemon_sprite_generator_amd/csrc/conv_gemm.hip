@@ -2,6 +2,10 @@
 // conv_gemm_kernel.h; each (dtype, tile) instantiation is its own translation unit (conv_tile.hip compiled once per tile,
 // see the Makefile) so that the eight of them build in parallel - one file with all of them took five minutes.
 #include "conv_gemm_kernel.h"
+#include <cstring>
+#include <mutex>
+#include <queue>
+#include <vector>
 
 namespace psg {
 
@@ -79,6 +83,59 @@ static ConvPlan conv_plan(const ConvP& p, int dtype, bool may_split) {
     return pl;
 }
 
+// Border-class form (TapCls in conv_gemm_kernel.h): PSG_CONV_TAPCLASS=0 / psg_conv_set_tapclass(0) turns it off, 1 (default)
+// uses it where the estimate below says it pays, 2 on every launch it applies to (per-layer A/B runs).
+static int g_tapcls = -1;
+static int64_t g_tapcls_launches = 0;
+static int tapcls_setting() {
+    if (g_tapcls < 0) { const char* e = getenv("PSG_CONV_TAPCLASS"); g_tapcls = e ? atoi(e) : 1; }
+    return g_tapcls;
+}
+
+// bf16, taps-innermost fast path, stride-1 3x3 pad 1 (forward or data gradient), at least 3 x 3 positions, unsplit
+static bool tapcls_applicable(const ConvP& p, int dtype) {
+    return dtype == PSG_BF16 && p.fast && p.ntap == 0 && p.ks == 3 && p.stride == 1 && p.pad == 1 && p.Ho >= 3 && p.Wo >= 3 &&
+           p.splits == 1 && (int64_t)p.M + 9 * 128 < (1 << 24);
+}
+
+// Makespan estimate of the plain and the border-class grid of a BM x BN plan.  The two resident workgroups of a CU share its
+// matrix pipe, so a CU is one machine that works off the K steps of its tiles; each tile goes, in dispatch order (the class
+// order is heaviest first), to the CU with the least work so far, at K steps + TAPCLS_OV of prologue / epilogue (+ TAPCLS_EPI
+// for the class form's per-row stores).  The class form is used when it shortens the estimate by TAPCLS_GAIN, and only on
+// grids of more than one round of resident workgroups: in a single round the 9-tap tiles set the time whatever the others do,
+// and the light tiles do not land beside them (4x4 layers, 64x160 tiles: 10-13 % slower in class order).  Per-layer
+// measurement (tools/tapcls_bench.py): 27x27 +1..4 %, 14x14 +2..4 %, 7x7 +3.5..4 %.
+static constexpr double TAPCLS_OV = 6.0, TAPCLS_EPI = 1.0, TAPCLS_GAIN = 0.02;
+static bool tapcls_pays(const ConvP& p, int BM, int BN) {
+    const int ntiles = (p.N + BN - 1) / BN;
+    const int mtiles = (p.M + BM - 1) / BM;
+    const int cus = avail_cus_for((double)mtiles * ntiles / 512.0);
+    if ((int64_t)mtiles * ntiles <= 2 * cus) return false;
+    struct Key { int B, Ho, Wo, N, tpt, dg, BM, BN, cus; bool operator==(const Key& o) const { return !memcmp(this, &o, sizeof(Key)); } };
+    static std::mutex mu;
+    static std::vector<std::pair<Key, bool>> memo;
+    const Key key = {p.B, p.Ho, p.Wo, p.N, p.tpt, p.transposed, BM, BN, cus};
+    std::lock_guard<std::mutex> lock(mu);
+    for (const auto& e : memo) if (e.first == key) return e.second;
+    auto span = [&](bool cls) {
+        std::priority_queue<double, std::vector<double>, std::greater<double>> q;
+        for (int i = 0; i < cus; ++i) q.push(0.0);
+        double sp = 0.0;
+        const int total = cls ? tapcls_mtiles(p, BM) : mtiles;
+        for (int mt = 0; mt < total; ) {
+            const TapCls c = tapcls_of(p, BM, mt, p.transposed != 0);
+            const int n = cls ? c.r0 / BM + (c.nrow + BM - 1) / BM - mt : total;
+            const double d = cls ? (double)p.tpt * (c.kh1 - c.kh0 + 1) * (c.kw1 - c.kw0 + 1) + TAPCLS_OV + TAPCLS_EPI : 9.0 * p.tpt + TAPCLS_OV;
+            for (int t = 0; t < n * ntiles; ++t) { const double f = q.top() + d; q.pop(); q.push(f); sp = f > sp ? f : sp; }
+            mt += n;
+        }
+        return sp;
+    };
+    const bool pays = span(true) < (1.0 - TAPCLS_GAIN) * span(false);
+    memo.push_back({key, pays});
+    return pays;
+}
+
 static int choose_and_launch(const ConvP& p0, int dtype, hipStream_t s) {
     ConvP p = p0;
     ConvPlan pl = conv_plan(p, dtype, p.ws != nullptr);
@@ -88,19 +145,22 @@ static int choose_and_launch(const ConvP& p0, int dtype, hipStream_t s) {
         else pl = conv_plan(p, dtype, false);          // workspace too small: the best UNSPLIT tile, not the split plan's tile
     }
     const int BM = pl.BM, BN = pl.BN;
+    p.tapcls = 0;
+    if (tapcls_setting() && tapcls_applicable(p, dtype) && (tapcls_setting() == 2 || tapcls_pays(p, BM, BN))) p.tapcls = 1;
 #ifdef PSG_ABL
     if (PSG_ABL & 8) { const char* e = getenv("PSG_DBG_PTR"); p.ws = (e && p.splits <= 1) ? reinterpret_cast<float*>(strtoull(e, nullptr, 0)) : (p.splits <= 1 ? nullptr : p.ws); }
 #endif
     {
         static int dbg = -1;                               // PSG_CONV_DEBUG=1: print the tile chosen for every launch
         if (dbg < 0) { const char* e = getenv("PSG_CONV_DEBUG"); dbg = e ? atoi(e) : 0; }
-        if (dbg) fprintf(stderr, "psg conv: M=%d N=%d Cin=%d ks=%d tr=%d fast=%d epi_lds=%d -> tile %dx%d splits=%d\n", p.M, p.N, p.Cin, p.ks, p.transposed,
-                         p.fast, p.epi_lds, BM, BN, p.splits);
+        if (dbg) fprintf(stderr, "psg conv: M=%d N=%d Cin=%d ks=%d tr=%d fast=%d epi_lds=%d -> tile %dx%d splits=%d tapcls=%d\n", p.M, p.N, p.Cin, p.ks, p.transposed,
+                         p.fast, p.epi_lds, BM, BN, p.splits, p.tapcls);
     }
     if (BM == 128 && BN == 128 && p.splits == 1 && conv_pw_applicable(p, dtype)) {
         const int rc = launch_conv_pw(p, s);
         if (rc != -1) return rc;
     }
+    if (p.tapcls) ++g_tapcls_launches;
     if (BN == 160 && BM == 64) return launch_conv<bf16_t, 64, 160>(p, s);
     if (BN == 160) return launch_conv<bf16_t, 128, 160>(p, s);
     if (dtype == PSG_F32) {
@@ -206,6 +266,7 @@ static int conv_setup(const psg_conv_desc* d, ConvP& p) {
     p.ws_bytes = p.ws ? d->ws_bytes : 0;
     p.splits = 1; p.kt_per_split = p.KT;
     p.ntap = 0; p.sub_h0 = p.sub_w0 = p.sub_nH = p.sub_nW = 0;
+    p.tapcls = 0;
     return PSG_OK;
 }
 
@@ -253,5 +314,8 @@ int psg_conv_fwd(const psg_conv_desc* d, psg_stream_t stream) {
     }
     return choose_and_launch(p, d->dtype, s);
 }
+
+int psg_conv_set_tapclass(int on) { psg::g_tapcls = on < 0 ? 0 : (on > 2 ? 2 : on); return PSG_OK; }
+int64_t psg_conv_tapclass_launches(void) { return psg::g_tapcls_launches; }
 
 }  // extern "C"

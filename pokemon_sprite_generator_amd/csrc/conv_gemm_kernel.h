@@ -42,6 +42,7 @@ struct ConvP {
     // j < sub_nW; only the ntap filter taps that reach them: source pixel (i + tap_dh, j + tap_dw), weight tap tap_wi
     int sub_h0, sub_w0, sub_nH, sub_nW, ntap;
     int tap_dh[4], tap_dw[4], tap_wi[4];
+    int tapcls;                    // border-class form of a stride-1 3x3 pad-1 mode 0/1 launch (TapCls below)
     // split-K (small M: sampling, small training batches): `splits` workgroups share one output tile, each reduces
     // kt_per_split K steps and writes its fp32 partial tile to ws[split][M][N]; conv_splitk_finish_kernel sums the partials
     // in fixed order and applies the epilogue.  splits == 1: the kernel's own epilogue, no workspace.
@@ -205,6 +206,60 @@ __device__ __forceinline__ int conv_out_m(const ConvP& p, int mt) {
     return mt;
 }
 
+// Border-class form of modes 0/1 (stride 1, 3x3, pad 1, Ho and Wo >= 3; ConvP::tapcls).  The output positions fall into 9
+// classes - first / interior / last row x first / interior / last column - and every position of a class has the same
+// valid taps, a rectangle kh in [kh0, kh1] x kw in [kw0, kw1] (9 interior, 6 edge, 4 corner; mirrored in the data
+// gradient).  The GEMM's M axis runs class by class, heaviest first, each class padded to whole BM-row tiles (padded rows
+// load nothing and store nothing); inside a class, rows go by sample, then row-major over the class's (nh x nw) grid.  The
+// K walk of a tile skips the taps outside its rectangle: their gathers would load zeros for every row of the tile and their
+// MFMAs add exact zeros, so the remaining K steps in their usual order give every result bit for bit.
+struct TapCls { int r0, nrow, h0, w0, nh, nw, kh0, kh1, kw0, kw1; };
+// class slot s -> row class / column class (0 first, 1 interior, 2 last): interior, top, bottom, left, right, 4 corners
+__host__ __device__ constexpr int tapcls_hc(int s) { return s == 0 ? 1 : (s <= 2 ? 2 * (s - 1) : (s <= 4 ? 1 : (s <= 6 ? 0 : 2))); }
+__host__ __device__ constexpr int tapcls_wc(int s) { return s == 0 ? 1 : (s <= 2 ? 1 : (s <= 4 ? 2 * (s - 3) : 2 * ((s - 5) & 1))); }
+// class of M-tile mt (tiles of BM rows); r0 is the class's first GEMM row.  With mt >= the tile count: the last class, and
+// r0 / BM + its tiles = the tile count
+__host__ __device__ __forceinline__ TapCls tapcls_of(const ConvP& p, int BM, int mt, bool dgrad) {
+    TapCls c;
+    int t0 = 0;
+#pragma unroll
+    for (int s = 0; s < 9; ++s) {
+        const int hc = tapcls_hc(s), wc = tapcls_wc(s);
+        c.nh = hc == 1 ? p.Ho - 2 : 1; c.nw = wc == 1 ? p.Wo - 2 : 1;
+        c.h0 = hc == 0 ? 0 : (hc == 1 ? 1 : p.Ho - 1); c.w0 = wc == 0 ? 0 : (wc == 1 ? 1 : p.Wo - 1);
+        c.nrow = p.B * c.nh * c.nw;
+        c.r0 = t0 * BM;
+        // the forward reads source row ho - 1 + kh, the stride-1 data gradient ho + 1 - kh: on the first row the forward
+        // loses kh = 0 and the data gradient kh = 2, on the last row the other way round (columns alike)
+        c.kh0 = (dgrad ? hc == 2 : hc == 0) ? 1 : 0; c.kh1 = (dgrad ? hc == 0 : hc == 2) ? 1 : 2;
+        c.kw0 = (dgrad ? wc == 2 : wc == 0) ? 1 : 0; c.kw1 = (dgrad ? wc == 0 : wc == 2) ? 1 : 2;
+        const int nt = (c.nrow + BM - 1) / BM;
+        if (mt < t0 + nt) break;
+        t0 += nt;
+    }
+    return c;
+}
+static inline int tapcls_mtiles(const ConvP& p, int BM) {
+    const TapCls c = tapcls_of(p, BM, 1 << 30, p.transposed != 0);
+    return c.r0 / BM + (c.nrow + BM - 1) / BM;
+}
+// output position (sample b, ho, wo) of class row r, 0 <= r < c.nrow (fastdiv: rows < 2^24, checked on the host)
+__device__ __forceinline__ void tapcls_pix(const TapCls& c, float inv_hw, float inv_nw, int r, int& b, int& ho, int& wo) {
+    const int hw = c.nh * c.nw;
+    b = fastdiv(r, hw, inv_hw);
+    const int rm = r - b * hw, i = fastdiv(rm, c.nw, inv_nw);
+    ho = c.h0 + i; wo = c.w0 + rm - i * c.nw;
+}
+// y row of GEMM row mt of the class's tile, -1 for a padding row; b: its sample index
+__device__ __forceinline__ int tapcls_m(const ConvP& p, const TapCls& c, float inv_hw, float inv_nw, int mt, int& b) {
+    const int r = mt - c.r0;
+    b = 0;
+    if (r >= c.nrow) return -1;
+    int ho, wo;
+    tapcls_pix(c, inv_hw, inv_nw, r, b, ho, wo);
+    return (b * p.Ho + ho) * p.Wo + wo;
+}
+
 // MODE 0: forward gather, K step inside one tap (Cin % K-step == 0)   [every 3x3 / 1x1 layer of the U-Net body]
 // MODE 1: data-gradient gather of a stride-1 conv, same fast decode
 // MODE 2: generic (Cin = 8 first/last convs, odd channel counts): per-thread tap decode
@@ -215,8 +270,10 @@ __device__ __forceinline__ int conv_out_m(const ConvP& p, int mt) {
 // SPLITK: the split-K form (small output grids) is its OWN instantiation - it has no epilogue at all, and the epilogue-heavy
 // plain kernels keep their register allocation (as a run-time branch inside them it cost 274 more spilled registers and
 // 17 % of the forward / data-gradient families).
-template <typename T, int BM, int BN, int MODE, bool SPLITK = false>
+// CLS: the border-class form of modes 0 / 1 (TapCls; bf16, never split).
+template <typename T, int BM, int BN, int MODE, bool SPLITK = false, bool CLS = false>
 __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvP p) {
+    static_assert(!CLS || (sizeof(T) == 2 && (MODE == 0 || MODE == 1) && !SPLITK), "border-class form: bf16 modes 0/1, unsplit");
 #if defined(__HIP_DEVICE_COMPILE__)      // the LDS-DMA builtin exists only in the device pass
     constexpr int NT = 256;
     constexpr int CH = Elem<T>::CH;
@@ -251,8 +308,20 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvP p) {
         const int gm = min(GM, p.mtiles - g * GM);
         nt = rem / gm;
         mt = g * GM + (rem - nt * gm);
+        if constexpr (CLS) {
+            // Each XCD runs a contiguous range of M-tiles, and the classes lie heaviest first along M: read as is, the first
+            // XCDs would get all the 9-tap tiles and the last ones the corners.  Transposed (range x, i-th tile -> class-order
+            // tile 8i + x), every XCD gets every 8th tile of the class order - the same mix, heaviest first.
+            const int q8 = p.mtiles >> 3, r8 = p.mtiles & 7, big = r8 * (q8 + 1);
+            const int x = mt < big ? mt / (q8 + 1) : r8 + (mt - big) / q8;
+            const int i = mt < big ? mt - x * (q8 + 1) : mt - big - (x - r8) * q8;
+            mt = i * 8 + x;
+        }
     }
     const int m0 = mt * BM, n0 = nt * BN;
+    // border class of this tile (wave-uniform): first row, position grid, tap rectangle
+    const TapCls tc = CLS ? tapcls_of(p, BM, mt, MODE == 1) : TapCls{};
+    const float tc_ihw = CLS ? 1.0f / (float)(tc.nh * tc.nw) : 0.f, tc_inw = CLS ? 1.0f / (float)tc.nw : 0.f;
 
     // ---- per-thread staging coordinates ------------------------------------
     // Tiles go global -> LDS by LDS-DMA (buffer_load ... lds): the destination of a wave-instruction is
@@ -281,7 +350,15 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvP p) {
 #pragma unroll
         for (int j = 0; j < JX; ++j) {
             const int m = m0 + sr + RPP * j;
-            if (MODE == 3) {
+            if (CLS) {                                     // (stride 1, pad 1)
+                if (m - tc.r0 < tc.nrow) {
+                    int b, ho, wo;
+                    tapcls_pix(tc, tc_ihw, tc_inw, m - tc.r0, b, ho, wo);
+                    if (MODE == 1) { x_hb[j] = ho + 1; x_wb[j] = wo + 1; }
+                    else { x_hb[j] = ho - 1; x_wb[j] = wo - 1; }
+                    x_base[j] = ((b * p.Hi + x_hb[j]) * p.Wi + x_wb[j]) * (int)p.ldx * ESZ + sc * 16;
+                } else { x_hb[j] = -100000; x_wb[j] = -100000; x_base[j] = 0; }
+            } else if (MODE == 3) {
                 if (m < p.M) {
                     const int hw = p.sub_nH * p.sub_nW;
                     const int b = m / hw, rm = m - b * hw;
@@ -309,13 +386,21 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvP p) {
 
     // this workgroup's K steps [kt0, kt1) (the whole K axis unless split-K)
     const int kt0 = SPLITK ? split * p.kt_per_split : 0;
-    const int kt1 = (PSG_ABL & 1) ? kt0 + 1 : (SPLITK ? min(p.KT, kt0 + p.kt_per_split) : p.KT);
+    // (border class: Cin / 64 slices x the taps of the class's rectangle)
+    const int kt_all = CLS ? p.tpt * (tc.kh1 - tc.kh0 + 1) * (tc.kw1 - tc.kw0 + 1) : p.KT;
+    const int kt1 = (PSG_ABL & 1) ? kt0 + 1 : (SPLITK ? min(p.KT, kt0 + p.kt_per_split) : kt_all);
     // uniform tap state of the NEXT K step to load (fast modes): chunk offset inside the tap, kh, kw - at step kt0 of the
     // taps-innermost walk (MODE 3: t_kh indexes the class's tap table)
-    int t_c0 = 0, t_kh = 0, t_kw = 0;
+    int t_c0 = 0, t_kh = CLS ? tc.kh0 : 0, t_kw = CLS ? tc.kw0 : 0;
     if (SPLITK && kt0 > 0) {
         if (MODE == 3) { t_c0 = (kt0 / p.ntap) * 8; t_kh = kt0 % p.ntap; }
         else if (MODE != 2) { const int tp = kt0 % p.taps; t_c0 = (kt0 / p.taps) * 8; t_kh = tp / p.ks; t_kw = tp - t_kh * p.ks; }
+    }
+    // border class: the y row of each of the tile's BM rows (-1: padding), behind the two tile buffers - the epilogue's
+    // row-major passes read it instead of decoding a class position per 16-byte chunk (visible after the first barrier)
+    int* rowtab = reinterpret_cast<int*>(smem + 2 * BUF_BYTES);
+    if constexpr (CLS) {
+        if (tid < BM) { int b_; rowtab[tid] = tapcls_m(p, tc, tc_ihw, tc_inw, m0 + tid, b_); }
     }
     // wave-uniform LDS byte offset of this wave's 1 KiB slot in pass 0 (rows 8*wave .. 8*wave+7)
     typedef __attribute__((address_space(3))) char* lds_ptr_t;
@@ -355,7 +440,8 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvP p) {
                 const uint32_t off = (uint32_t)(x_base[j] + delta) | ((uint32_t)bad & OOB);
                 lds_dma16(xrs, xdst + j * PASS_BYTES, off);
             }
-            if (++t_kw == p.ks) { t_kw = 0; if (++t_kh == p.ks) { t_kh = 0; t_c0 += 8; } }
+            if (CLS) { if (++t_kw > tc.kw1) { t_kw = tc.kw0; if (++t_kh > tc.kh1) { t_kh = tc.kh0; t_c0 += 8; } } }   // the class's taps only
+            else if (++t_kw == p.ks) { t_kw = 0; if (++t_kh == p.ks) { t_kh = 0; t_c0 += 8; } }
         } else {
             const int qi = kt * 8 + sc;
             const int tap = qi / p.cpt, cc = qi - tap * p.cpt;
@@ -474,7 +560,8 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvP p) {
         for (int j = 0; j < NB; ++j) {
             const int mt_ = m0 + wm * WM + j * 16 + l16;
             rows[j] = -1; smp[j] = 0;
-            if (mt_ < p.M) conv_out_row<MODE>(p, mt_, rows[j], smp[j]);
+            if (CLS) rows[j] = tapcls_m(p, tc, tc_ihw, tc_inw, mt_, smp[j]);
+            else if (mt_ < p.M) conv_out_row<MODE>(p, mt_, rows[j], smp[j]);
             if (!SPLITK && resg && !p.epi_lds) {
 #pragma unroll
                 for (int i = 0; i < NA; ++i) {
@@ -546,10 +633,11 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvP p) {
                 const int idx = it * 64 + lane;
                 const int row = idx / E_CPRW, chk = idx - row * E_CPRW;
                 const int mt_ = m0 + wm * WM + row, n = n0 + wn * WN + chk * 8;
+                const int cm_ = CLS ? rowtab[mt_ - m0] : 0;      // (border class: y row, -1 = padding)
                 // (an unconditional load from a clamped address + a select on the VALUE: as `ok ? *ptr : zero` hipcc selected
                 //  between the pointer and the address of a zero in scratch memory and issued a flat load)
-                const bool ok = idx < E_NCH && mt_ < p.M && n < p.N;
-                const uint4 got = *reinterpret_cast<const uint4*>(resg + (ok ? (int64_t)conv_out_m<MODE>(p, mt_) * ldaux + n : (int64_t)0));
+                const bool ok = idx < E_NCH && (CLS ? cm_ >= 0 : mt_ < p.M) && n < p.N;
+                const uint4 got = *reinterpret_cast<const uint4*>(resg + (ok ? (int64_t)(CLS ? cm_ : conv_out_m<MODE>(p, mt_)) * ldaux + n : (int64_t)0));
                 res_row[it].x = ok ? got.x : 0u; res_row[it].y = ok ? got.y : 0u; res_row[it].z = ok ? got.z : 0u; res_row[it].w = ok ? got.w : 0u;
             }
         }
@@ -615,7 +703,8 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvP p) {
             //     `rbase` of the wave's sub-tile) to `dst`: a tile that lies wholly inside y (wave-uniform test; every tile of
             //     the U-Net's training shapes) reads all chunks first and stores them through one 64-bit row base + 32-bit
             //     offsets, without predicates
-            const bool tile_full = MODE != 3 && m0 + BM <= p.M && n0 + BN <= p.N;
+            // (border-class tiles: their rows are not consecutive y rows - the per-row store path below)
+            const bool tile_full = MODE != 3 && !CLS && m0 + BM <= p.M && n0 + BN <= p.N;
             auto flush_rows = [&](auto nchx_c, const char* src, int rbase, T* dst, int64_t ldd) {
                 constexpr int NCHX = decltype(nchx_c)::value, NITX = (NCHX + 63) / 64;
                 if (tile_full && ldd < (1 << 22)) {                 // (32-bit element offsets inside the tile: 128 rows x ldd)
@@ -653,9 +742,10 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvP p) {
                         const int idx = it * 64 + lane;
                         const int row = idx / CPRW, chk = idx - row * CPRW;
                         const int mt_ = m0 + wm * WM + rbase + row, n = n0 + wn * WN + chk * 8;
-                        if (idx < NCHX && mt_ < p.M && n < p.N) {
+                        const int cm_ = CLS ? rowtab[mt_ - m0] : 0;
+                        if (idx < NCHX && (CLS ? cm_ >= 0 : mt_ < p.M) && n < p.N) {
                             const uint4 val = *reinterpret_cast<const uint4*>(src + row * PITCH + chk * 16);
-                            *reinterpret_cast<uint4*>(dst + (int64_t)conv_out_m<MODE>(p, mt_) * ldd + n) = val;
+                            *reinterpret_cast<uint4*>(dst + (int64_t)(CLS ? cm_ : conv_out_m<MODE>(p, mt_)) * ldd + n) = val;
                         }
                         __builtin_amdgcn_sched_barrier(0);
                     }
@@ -794,10 +884,11 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvP p) {
                             const int idx = it * 64 + lane;              // chunk inside the half: same (row, chunk) walk as res_row
                             const int row = idx / CPRW, chk = idx - row * CPRW;
                             const int mt_ = m0 + wm * WM + h * HR + row, n = n0 + wn * WN + chk * 8;
-                            if (mt_ < p.M && n < p.N) {
+                            const int cm_ = CLS ? rowtab[mt_ - m0] : 0;
+                            if ((CLS ? cm_ >= 0 : mt_ < p.M) && n < p.N) {
                                 const f32x4 lo = *reinterpret_cast<const f32x4*>(reg + row * PITCHF + chk * 32);
                                 const f32x4 hi = *reinterpret_cast<const f32x4*>(reg + row * PITCHF + chk * 32 + 16);
-                                *reinterpret_cast<bf16x8*>(dy + (int64_t)conv_out_m<MODE>(p, mt_) * p.ldy + n) = join(lo, hi, res_row[h * NITH + it]);
+                                *reinterpret_cast<bf16x8*>(dy + (int64_t)(CLS ? cm_ : conv_out_m<MODE>(p, mt_)) * p.ldy + n) = join(lo, hi, res_row[h * NITH + it]);
                             }
                             __builtin_amdgcn_sched_barrier(0);
                         }
@@ -909,9 +1000,9 @@ __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(const ConvP p) 
 
 template <typename T, int BM, int BN>
 int launch_conv(const ConvP& p, hipStream_t stream) {
-    const size_t lds = (size_t)2 * (BM + BN) * 128;
+    const size_t lds = (size_t)2 * (BM + BN) * 128 + (p.tapcls ? BM * 4 : 0);     // (+ the border-class row table)
     ConvP q = p;
-    q.mtiles = (p.M + BM - 1) / BM;
+    q.mtiles = p.tapcls ? tapcls_mtiles(p, BM) : (p.M + BM - 1) / BM;
     q.ntiles = (p.N + BN - 1) / BN;
     const int grid = q.mtiles * q.ntiles * (q.splits > 1 ? q.splits : 1);
     // algorithmic bytes: every input pixel, weight and output element once (+ the epilogue's residual / saved tensors)
@@ -921,7 +1012,14 @@ int launch_conv(const ConvP& p, hipStream_t stream) {
     const ConvP fin = q;                               // (the finishing kernel runs the epilogue: it keeps the operands)
     if (q.splits > 1) { q.bias = nullptr; q.rowadd = nullptr; q.residual = nullptr; q.preact = nullptr; q.dact_u = nullptr; }
     const int mode = p.ntap > 0 ? 3 : (!p.fast ? 2 : (!p.transposed ? 0 : (p.stride == 1 ? 1 : 2)));
-    if (q.splits > 1) {
+    if (p.tapcls) {
+        if (q.splits > 1 || (mode != 0 && mode != 1) || p.ks != 3 || p.stride != 1 || p.pad != 1 || p.Ho < 3 || p.Wo < 3)
+            return set_error(PSG_ERR_ARG, "conv_gemm: border-class form needs an unsplit stride-1 3x3 pad-1 launch");
+        if constexpr (sizeof(T) == 2) {
+            if (mode == 0) hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, 0, false, true>), dim3(grid), dim3(256), lds, stream, q);
+            else hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, 1, false, true>), dim3(grid), dim3(256), lds, stream, q);
+        } else return set_error(PSG_ERR_ARG, "conv_gemm: no fp32 border-class kernel");
+    } else if (q.splits > 1) {
         if (mode == 0) hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, 0, true>), dim3(grid), dim3(256), lds, stream, q);
         else if (mode == 1) hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, 1, true>), dim3(grid), dim3(256), lds, stream, q);
         else if (mode == 2) hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, 2, true>), dim3(grid), dim3(256), lds, stream, q);
@@ -956,6 +1054,10 @@ int set_conv_attrs() {
     PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<T, BM, BN, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     if constexpr (BN != 160)
         PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<T, BM, BN, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if constexpr (sizeof(T) == 2) {
+        PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<T, BM, BN, 0, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds + BM * 4));
+        PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<T, BM, BN, 1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds + BM * 4));
+    }
     return PSG_OK;
 }
 
