@@ -288,7 +288,9 @@ def _conv_launch(lib, dtype, x, ldx, w, ldw, y, ldy, geom, Cin, Cout, transposed
                         residual.data_ptr() if residual is not None else 0, preact.data_ptr() if preact is not None else 0,
                         dact_u.data_ptr() if dact_u is not None else 0, 0, 0)
     # small grids (sampling, small batches): offer a split-K workspace.  Only launches with few output elements are asked
-    # about (one plan evaluation on the host); a batch-256 train step never is.
+    # about (one plan evaluation on the host).  A batch-256 train step asks for its 4x4 convs and its Linears up to 8 M
+    # outputs, and the planner takes split-K for one of them, the ProjGroup's time-projection data gradient (M = 256)
+    # (tests/test_gemm_b256_gpu.py records which).
     if B * Ho * Wo * Cout <= _SPLITK_MAX_OUT and _SPLITK:
         key = (dtype, geom, Cin, Cout, transposed, _lib.AVAIL_CUS[0], _lib.AVAIL_CUS[1])
         need = _splitk_need.get(key)
