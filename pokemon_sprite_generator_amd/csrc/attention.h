@@ -1,0 +1,49 @@
+// Attention: the kernel argument block shared by the three kernel families (attention.hip: VALU, attention_mfma.hip: bf16
+// matrix cores, attention_f32.hip: exact-fp32 matrix cores) and the MFMA families' host entry points.
+#pragma once
+#include "psg_common.h"
+#include <utility>
+
+namespace psg {
+
+// T: element type of q, k, v, o, dout and of every output
+template <typename T>
+struct AttnArgs {
+    const T *q, *k, *v, *o, *dout;
+    T *out, *dq, *dk, *dv;
+    float* lse; float* delta;                      // delta = rowsum(dO * O): written by the dQ (VALU: delta) kernel, read by dK/dV
+    int64_t ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
+    int B, H, L, S, d;
+    float scale;
+    uint32_t drop_thresh; float drop_scale; uint64_t seed;
+    const uint64_t* seed_dev;
+    const int32_t* kv_len;     // psg_attn_fwd_varlen: keys s >= kv_len[b] of sample b are left out (NULL otherwise)
+};
+
+// Head-dim list of an MFMA family: the kernels are instantiated for head_dim = 16 * ND, ND in NDs.  Calls
+// f(std::integral_constant<int, ND>) for the ND of head_dim d; false when d is not in the list.
+template <int... NDs, typename F>
+inline bool with_nd(std::integer_sequence<int, NDs...>, int d, F&& f) {
+    return ((d == 16 * NDs && (f(std::integral_constant<int, NDs>{}), true)) || ...);
+}
+// f(std::integral_constant<int, ND>) for every ND of the list, in order, until one returns non-zero (which is returned)
+template <int... NDs, typename F>
+inline int for_each_nd(std::integer_sequence<int, NDs...>, F&& f) {
+    int rc = PSG_OK;
+    ((rc = rc ? rc : f(std::integral_constant<int, NDs>{})), ...);
+    return rc;
+}
+
+// whether the family's kernels take this problem: its head_dim and row strides, and the LDS fit of its forward kernel and,
+// unless forward_only (psg_attn_fwd_varlen), of its backward kernels
+bool attn_mfma_applicable(int L, int S, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, bool forward_only);
+int attn_mfma_init_attrs();
+template <bool VARLEN> int attn_mfma_fwd(const AttnArgs<bf16_t>& p, hipStream_t s);
+int attn_mfma_bwd(const AttnArgs<bf16_t>& p, hipStream_t s);
+
+bool attn_f32_applicable(int L, int S, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, bool forward_only);
+int attn_f32_init_attrs();
+template <bool VARLEN> int attn_f32_fwd(const AttnArgs<float>& p, hipStream_t s);
+int attn_f32_bwd(const AttnArgs<float>& p, hipStream_t s);
+
+}  // namespace psg

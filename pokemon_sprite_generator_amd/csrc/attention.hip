@@ -4,7 +4,8 @@
 // score slab of a 16-query tile lives in LDS, row softmax is a wave-shuffle reduction, and the
 // probabilities never touch HBM.  lse (log-sum-exp) is saved for backward, which recomputes P.
 // Problems are tiny and independent (B*heads of them per call): latency/LDS-bound, not MFMA-bound.
-#include "psg_common.h"
+#include "attention.h"
+#include <type_traits>
 
 namespace psg {
 
@@ -12,22 +13,11 @@ constexpr int AT_Q = 16;      // query rows per workgroup (fwd, dq)
 constexpr int AT_KC = 32;     // keys per staged chunk
 constexpr int AT_MAXC = 20;   // head_dim <= 16 * AT_MAXC = 320
 
-struct AttnP {
-    const void *q, *k, *v, *o, *dout;
-    void *out, *dq, *dk, *dv;
-    float* lse; float* delta;
-    int64_t ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
-    int B, H, L, S, d;
-    float scale;
-    uint32_t drop_thresh; float drop_scale; uint64_t seed;
-    const uint64_t* seed_dev;
-    const int32_t* kv_len;     // psg_attn_fwd_varlen: keys s >= kv_len[b] of sample b are left out (NULL otherwise)
-};
-
 // dropout element index of P[bh][l][s]: each query row owns ceil(S/2) hash PAIRS (keys 2k, 2k+1 share one 32-bit hash),
 // exactly as attention_mfma.hip lays them out - so the VALU and the MFMA kernels draw the SAME mask for every S (odd S
 // too: 7x7 self-attention has S = 49) and a forward on one path can be differentiated on the other
-__device__ __forceinline__ uint64_t attn_idx(const AttnP& p, int bh, int l, int s) {
+template <typename T>
+__device__ __forceinline__ uint64_t attn_idx(const AttnArgs<T>& p, int bh, int l, int s) {
     return ((uint64_t)bh * p.L + l) * (uint64_t)(2 * ((p.S + 1) >> 1)) + s;
 }
 
@@ -53,7 +43,7 @@ __device__ __forceinline__ int key_end(const int32_t* kv_len, int b, int S) {
 }
 
 template <typename T, bool VARLEN = false>
-__global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnP p) {
+__global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs<T> p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int d = p.d, dp = d + 1;
     const int Sp = (p.S + 3) & ~3;
@@ -62,10 +52,10 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnP p) {
     float* KV = Ss + AT_Q * Sp;           // [AT_KC][dp]
     const int bh = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
     const int l0 = blockIdx.x * AT_Q;
-    const T* qg = reinterpret_cast<const T*>(p.q) + (int64_t)b * p.L * p.ldq + h * d;
-    const T* kg = reinterpret_cast<const T*>(p.k) + (int64_t)b * p.S * p.ldk + h * d;
-    const T* vg = reinterpret_cast<const T*>(p.v) + (int64_t)b * p.S * p.ldv + h * d;
-    T* og = reinterpret_cast<T*>(p.out) + (int64_t)b * p.L * p.ldo + h * d;
+    const T* qg = p.q + (int64_t)b * p.L * p.ldq + h * d;
+    const T* kg = p.k + (int64_t)b * p.S * p.ldk + h * d;
+    const T* vg = p.v + (int64_t)b * p.S * p.ldv + h * d;
+    T* og = p.out + (int64_t)b * p.L * p.ldo + h * d;
     const int tid = threadIdx.x;
     const int Se = key_end<VARLEN>(p.kv_len, b, p.S);
 
@@ -133,15 +123,15 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnP p) {
 
 // delta[bh, l] = sum_d dO * O
 template <typename T>
-__global__ void attn_delta_kernel(const AttnP p) {
+__global__ void attn_delta_kernel(const AttnArgs<T> p) {
     const int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);   // (b*L + l)*H + h order? use bh-major
     const int lane = threadIdx.x & 63;
     const int64_t total = (int64_t)p.B * p.H * p.L;
     if (row >= total) return;
     const int bh = (int)(row / p.L), l = (int)(row - (int64_t)bh * p.L);
     const int b = bh / p.H, h = bh - b * p.H;
-    const T* o = reinterpret_cast<const T*>(p.o) + ((int64_t)b * p.L + l) * p.ldo + h * p.d;
-    const T* g = reinterpret_cast<const T*>(p.dout) + ((int64_t)b * p.L + l) * p.lddo + h * p.d;
+    const T* o = p.o + ((int64_t)b * p.L + l) * p.ldo + h * p.d;
+    const T* g = p.dout + ((int64_t)b * p.L + l) * p.lddo + h * p.d;
     float a = 0.f;
     for (int e = lane; e < p.d; e += 64) a += Elem<T>::ld(o + e) * Elem<T>::ld(g + e);
     a = wave_sum(a);
@@ -150,7 +140,7 @@ __global__ void attn_delta_kernel(const AttnP p) {
 
 // dQ for a 16-query tile
 template <typename T>
-__global__ __launch_bounds__(256) void attn_dq_kernel(const AttnP p) {
+__global__ __launch_bounds__(256) void attn_dq_kernel(const AttnArgs<T> p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int d = p.d, dp = d + 1;
     const int Sp = (p.S + 3) & ~3;
@@ -161,11 +151,11 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const AttnP p) {
     float* Vs = Ks + AT_KC * dp;          // [AT_KC][dp]
     const int bh = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
     const int l0 = blockIdx.x * AT_Q;
-    const T* qg = reinterpret_cast<const T*>(p.q) + (int64_t)b * p.L * p.ldq + h * d;
-    const T* kg = reinterpret_cast<const T*>(p.k) + (int64_t)b * p.S * p.ldk + h * d;
-    const T* vg = reinterpret_cast<const T*>(p.v) + (int64_t)b * p.S * p.ldv + h * d;
-    const T* gg = reinterpret_cast<const T*>(p.dout) + (int64_t)b * p.L * p.lddo + h * d;
-    T* dqg = reinterpret_cast<T*>(p.dq) + (int64_t)b * p.L * p.lddq + h * d;
+    const T* qg = p.q + (int64_t)b * p.L * p.ldq + h * d;
+    const T* kg = p.k + (int64_t)b * p.S * p.ldk + h * d;
+    const T* vg = p.v + (int64_t)b * p.S * p.ldv + h * d;
+    const T* gg = p.dout + (int64_t)b * p.L * p.lddo + h * d;
+    T* dqg = p.dq + (int64_t)b * p.L * p.lddq + h * d;
     const int tid = threadIdx.x;
 
     stage_rows<T>(Qs, qg, p.ldq, l0, AT_Q, p.L, d, p.scale);
@@ -229,7 +219,7 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const AttnP p) {
 
 // dK, dV for a 16-key tile: loops over all queries in chunks of 32
 template <typename T>
-__global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnP p) {
+__global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnArgs<T> p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int d = p.d, dp = d + 1;
     float* Ks = sm;                        // [16][dp]
@@ -240,12 +230,12 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnP p) {
     float* Dt = Pt + AT_Q * 33;            // [16][33] dS^T
     const int bh = blockIdx.y, b = bh / p.H, h = bh - b * p.H;
     const int s0 = blockIdx.x * AT_Q;
-    const T* qg = reinterpret_cast<const T*>(p.q) + (int64_t)b * p.L * p.ldq + h * d;
-    const T* kg = reinterpret_cast<const T*>(p.k) + (int64_t)b * p.S * p.ldk + h * d;
-    const T* vg = reinterpret_cast<const T*>(p.v) + (int64_t)b * p.S * p.ldv + h * d;
-    const T* gg = reinterpret_cast<const T*>(p.dout) + (int64_t)b * p.L * p.lddo + h * d;
-    T* dkg = reinterpret_cast<T*>(p.dk) + (int64_t)b * p.S * p.lddk + h * d;
-    T* dvg = reinterpret_cast<T*>(p.dv) + (int64_t)b * p.S * p.lddv + h * d;
+    const T* qg = p.q + (int64_t)b * p.L * p.ldq + h * d;
+    const T* kg = p.k + (int64_t)b * p.S * p.ldk + h * d;
+    const T* vg = p.v + (int64_t)b * p.S * p.ldv + h * d;
+    const T* gg = p.dout + (int64_t)b * p.L * p.lddo + h * d;
+    T* dkg = p.dk + (int64_t)b * p.S * p.lddk + h * d;
+    T* dvg = p.dv + (int64_t)b * p.S * p.lddv + h * d;
     const int tid = threadIdx.x;
     stage_rows<T>(Ks, kg, p.ldk, s0, AT_Q, p.S, d, 1.0f);
     stage_rows<T>(Vs, vg, p.ldv, s0, AT_Q, p.S, d, 1.0f);
@@ -333,85 +323,10 @@ static int attn_check(const char* who, int B, int heads, int L, int S, int d, in
     return PSG_OK;
 }
 
-// attention_mfma.hip (bf16 matrix-core path)
-struct AttnMP {
-    const bf16_t *q, *k, *v, *o, *dout;
-    bf16_t *out, *dq, *dk, *dv;
-    float* lse; float* delta;
-    int64_t ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
-    int B, H, L, S, d;
-    float scale;
-    uint32_t drop_thresh; float drop_scale; uint64_t seed;
-    const uint64_t* seed_dev;
-    const int32_t* kv_len;     // psg_attn_fwd_varlen: keys s >= kv_len[b] of sample b are left out (NULL otherwise)
-};
-int attn_mfma_applicable(int L, int S, int d, int dtype, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo);
-int attn_mfma_init_attrs();
-int attn_mfma_fwd(const AttnMP& p, hipStream_t s);
-int attn_mfma_bwd(const AttnMP& p, hipStream_t s);
-int attn_mfma_fwd_applicable(int S, int d, int dtype, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo);
-int attn_mfma_fwd_varlen(const AttnMP& p, hipStream_t s);
-
-// attention_f32.hip (exact-fp32 matrix-core path)
-struct AttnFP {
-    const float *q, *k, *v, *o, *dout;
-    float *out, *dq, *dk, *dv;
-    float* lse; float* delta;
-    int64_t ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
-    int B, H, L, S, d;
-    float scale;
-    uint32_t drop_thresh; float drop_scale; uint64_t seed;
-    const uint64_t* seed_dev;
-    const int32_t* kv_len;     // psg_attn_fwd_varlen: keys s >= kv_len[b] of sample b are left out (NULL otherwise)
-};
-int attn_f32_applicable(int L, int S, int d, int dtype, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo);
-int attn_f32_init_attrs();
-int attn_f32_fwd(const AttnFP& p, hipStream_t s);
-int attn_f32_bwd(const AttnFP& p, hipStream_t s);
-int attn_f32_fwd_applicable(int S, int d, int dtype, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo);
-int attn_f32_fwd_varlen(const AttnFP& p, hipStream_t s);
-
-static AttnFP to_f32(const AttnP& a) {
-    AttnFP m;
-    m.q = (const float*)a.q; m.k = (const float*)a.k; m.v = (const float*)a.v; m.o = (const float*)a.o; m.dout = (const float*)a.dout;
-    m.out = (float*)a.out; m.dq = (float*)a.dq; m.dk = (float*)a.dk; m.dv = (float*)a.dv;
-    m.lse = a.lse; m.delta = a.delta;
-    m.ldq = a.ldq; m.ldk = a.ldk; m.ldv = a.ldv; m.ldo = a.ldo; m.lddo = a.lddo; m.lddq = a.lddq; m.lddk = a.lddk; m.lddv = a.lddv;
-    m.B = a.B; m.H = a.H; m.L = a.L; m.S = a.S; m.d = a.d; m.scale = a.scale;
-    m.drop_thresh = a.drop_thresh; m.drop_scale = a.drop_scale; m.seed = a.seed; m.seed_dev = a.seed_dev; m.kv_len = a.kv_len;
-    return m;
-}
-
-static AttnMP to_mfma(const AttnP& a) {
-    AttnMP m;
-    m.q = (const bf16_t*)a.q; m.k = (const bf16_t*)a.k; m.v = (const bf16_t*)a.v; m.o = (const bf16_t*)a.o; m.dout = (const bf16_t*)a.dout;
-    m.out = (bf16_t*)a.out; m.dq = (bf16_t*)a.dq; m.dk = (bf16_t*)a.dk; m.dv = (bf16_t*)a.dv;
-    m.lse = a.lse; m.delta = a.delta;
-    m.ldq = a.ldq; m.ldk = a.ldk; m.ldv = a.ldv; m.ldo = a.ldo; m.lddo = a.lddo; m.lddq = a.lddq; m.lddk = a.lddk; m.lddv = a.lddv;
-    m.B = a.B; m.H = a.H; m.L = a.L; m.S = a.S; m.d = a.d; m.scale = a.scale;
-    m.drop_thresh = a.drop_thresh; m.drop_scale = a.drop_scale; m.seed = a.seed; m.seed_dev = a.seed_dev; m.kv_len = a.kv_len;
-    return m;
-}
-
-}  // namespace psg
-using namespace psg;
-
-extern "C" {
-
-int psg_attn_init_attrs(void) {
-    { int rc = attn_mfma_init_attrs(); if (rc) return rc; }
-    { int rc = attn_f32_init_attrs(); if (rc) return rc; }
-    const int big = 150 * 1024;
-#define SET_LDS(K) PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, big))
-    SET_LDS(attn_fwd_kernel<float>); SET_LDS(attn_fwd_kernel<bf16_t>);
-    SET_LDS(attn_dq_kernel<float>); SET_LDS(attn_dq_kernel<bf16_t>);
-    SET_LDS(attn_dkv_kernel<float>); SET_LDS(attn_dkv_kernel<bf16_t>);
-#undef SET_LDS
-    void (*const varlen_f32)(const AttnP) = attn_fwd_kernel<float, true>;
-    void (*const varlen_bf16)(const AttnP) = attn_fwd_kernel<bf16_t, true>;
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(varlen_f32), hipFuncAttributeMaxDynamicSharedMemorySize, big));
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(varlen_bf16), hipFuncAttributeMaxDynamicSharedMemorySize, big));
-    return PSG_OK;
+// the VALU kernels of element type T (attention_mfma.hip / attention_f32.hip raise their own)
+template <typename T>
+static int valu_init_attrs() {
+    return set_max_lds(150 * 1024, attn_fwd_kernel<T, false>, attn_fwd_kernel<T, true>, attn_dq_kernel<T>, attn_dkv_kernel<T>);
 }
 
 static int64_t g_attn_paths[3] = {0, 0, 0};         // launches taken by the bf16 MFMA / the VALU / the fp32 MFMA kernels
@@ -421,6 +336,69 @@ static int f32_mfma_on() {
     return on;
 }
 static int g_attn_allow = 3;                         // psg_attn_set_paths: bit 0 bf16 MFMA, bit 1 exact-fp32 MFMA
+
+enum AttnPass { ATTN_FWD, ATTN_FWD_VARLEN, ATTN_BWD };
+
+// The kernel family of one call - the bf16 MFMA kernels, the exact-fp32 MFMA kernels or the VALU kernels - counted in
+// g_attn_paths.  A plain forward and a backward take an MFMA family where both its forward and its backward kernels fit
+// LDS; a varlen forward where its forward kernel does.
+template <typename T>
+static int attn_route(AttnPass pass, const AttnArgs<T>& p, hipStream_t s) {
+    const bool bwd = pass == ATTN_BWD, varlen = pass == ATTN_FWD_VARLEN;
+    // (varlen: the FLOP count is the padded problem's, the key lengths live on the device)
+    ProfScope prof(PROF_ATTN, (bwd ? 10.0 : 4.0) * (double)p.B * p.H * p.L * p.S * p.d, s,
+                   (double)p.B * p.H * p.d * (bwd ? 4.0 * p.L + 4.0 * p.S : 2.0 * p.L + 2.0 * p.S) * (double)sizeof(T));
+    const bool in16 = aligned16(p.q) && aligned16(p.k) && aligned16(p.v);
+    const int64_t ldg = p.lddo | p.lddq | p.lddk | p.lddv;
+    if constexpr (std::is_same<T, bf16_t>::value) {
+        const bool out_ok = bwd ? (ldg & 7) == 0 && aligned16(p.o) && aligned16(p.dout) && aligned8(p.dq) && aligned8(p.dk) && aligned8(p.dv)
+                                : aligned8(p.out);
+        if ((g_attn_allow & 1) && attn_mfma_applicable(p.L, p.S, p.d, p.ldq, p.ldk, p.ldv, p.ldo, varlen) && in16 && out_ok) {
+            ++g_attn_paths[0];
+            return bwd ? attn_mfma_bwd(p, s) : varlen ? attn_mfma_fwd<true>(p, s) : attn_mfma_fwd<false>(p, s);
+        }
+    } else {
+        const bool out_ok = bwd ? (ldg & 3) == 0 && aligned16(p.o) && aligned16(p.dout) && aligned16(p.dq) && aligned16(p.dk) && aligned16(p.dv)
+                                : aligned16(p.out);
+        if ((g_attn_allow & 2) && f32_mfma_on() && attn_f32_applicable(p.L, p.S, p.d, p.ldq, p.ldk, p.ldv, p.ldo, varlen) && in16 && out_ok) {
+            ++g_attn_paths[2];
+            return bwd ? attn_f32_bwd(p, s) : varlen ? attn_f32_fwd<true>(p, s) : attn_f32_fwd<false>(p, s);
+        }
+    }
+    ++g_attn_paths[1];
+    const dim3 grid((p.L + AT_Q - 1) / AT_Q, p.B * p.H);
+    if (bwd) {
+        const int64_t rows = (int64_t)p.B * p.H * p.L;
+        hipLaunchKernelGGL(attn_delta_kernel<T>, dim3((int)((rows + 3) / 4)), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(attn_dq_kernel<T>, grid, dim3(256), dq_lds(p.S, p.d), s, p);
+        hipLaunchKernelGGL(attn_dkv_kernel<T>, dim3((p.S + AT_Q - 1) / AT_Q, p.B * p.H), dim3(256), dkv_lds(p.d), s, p);
+        PSG_LAUNCH_CHECK("attn_bwd");
+    } else if (varlen) {
+        hipLaunchKernelGGL((attn_fwd_kernel<T, true>), grid, dim3(256), fwd_lds(p.S, p.d), s, p);
+        PSG_LAUNCH_CHECK("attn_fwd_varlen");
+    } else {
+        hipLaunchKernelGGL((attn_fwd_kernel<T, false>), grid, dim3(256), fwd_lds(p.S, p.d), s, p);
+        PSG_LAUNCH_CHECK("attn_fwd");
+    }
+    return PSG_OK;
+}
+
+// f((T*)nullptr) for the element type T of dtype (PSG_F32 or PSG_BF16: attn_check has accepted it)
+template <typename F>
+static int with_elem(int dtype, F&& f) { return dtype == PSG_BF16 ? f((bf16_t*)nullptr) : f((float*)nullptr); }
+
+}  // namespace psg
+using namespace psg;
+
+extern "C" {
+
+int psg_attn_init_attrs(void) {
+    { int rc = attn_mfma_init_attrs(); if (rc) return rc; }
+    { int rc = attn_f32_init_attrs(); if (rc) return rc; }
+    { int rc = valu_init_attrs<float>(); if (rc) return rc; }
+    return valu_init_attrs<bf16_t>();
+}
+
 int psg_attn_set_paths(int allow_mask) { g_attn_allow = allow_mask & 3; return PSG_OK; }
 int psg_attn_path_counts(int64_t* mfma, int64_t* valu, int64_t* mfma_f32) {
     if (mfma) *mfma = g_attn_paths[0];
@@ -438,25 +416,14 @@ int psg_attn_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const v
     PSG_REQUIRE(drop_p >= 0.f && drop_p < 1.f, PSG_ERR_ARG, "attn_fwd: drop_p");
     const size_t lds = fwd_lds(S, d);
     PSG_REQUIRE(lds <= 150 * 1024, PSG_ERR_SHAPE, "attn_fwd: LDS need %zu too large", lds);
-    AttnP p = {};
-    p.q = q; p.k = k; p.v = v; p.out = o; p.lse = lse; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-    p.B = B; p.H = heads; p.L = L; p.S = S; p.d = d; p.scale = scale;
-    p.drop_thresh = drop_p > 0.f ? drop_thresh(drop_p) : 0u; p.drop_scale = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f; p.seed = seed; p.seed_dev = seed_source();
-    dim3 grid((L + AT_Q - 1) / AT_Q, B * heads);
-    ProfScope prof(PROF_ATTN, 4.0 * (double)B * heads * L * S * d, (hipStream_t)stream, (double)B * heads * d * (2.0 * L + 2.0 * S) * (dtype == PSG_BF16 ? 2.0 : 4.0));
-    if ((g_attn_allow & 1) && attn_mfma_applicable(L, S, d, dtype, ldq, ldk, ldv, ldo) && aligned16(q) && aligned16(k) && aligned16(v) && aligned8(o)) {
-        ++g_attn_paths[0];
-        return attn_mfma_fwd(to_mfma(p), (hipStream_t)stream);
-    }
-    if ((g_attn_allow & 2) && f32_mfma_on() && attn_f32_applicable(L, S, d, dtype, ldq, ldk, ldv, ldo) && aligned16(q) && aligned16(k) && aligned16(v) && aligned16(o)) {
-        ++g_attn_paths[2];
-        return attn_f32_fwd(to_f32(p), (hipStream_t)stream);
-    }
-    ++g_attn_paths[1];
-    if (dtype == PSG_F32) hipLaunchKernelGGL(attn_fwd_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(attn_fwd_kernel<bf16_t>, grid, dim3(256), lds, (hipStream_t)stream, p);
-    PSG_LAUNCH_CHECK("attn_fwd");
-    return PSG_OK;
+    return with_elem(dtype, [&](auto* tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        AttnArgs<T> p = {};
+        p.q = (const T*)q; p.k = (const T*)k; p.v = (const T*)v; p.out = (T*)o; p.lse = lse; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
+        p.B = B; p.H = heads; p.L = L; p.S = S; p.d = d; p.scale = scale;
+        p.drop_thresh = drop_p > 0.f ? drop_thresh(drop_p) : 0u; p.drop_scale = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f; p.seed = seed; p.seed_dev = seed_source();
+        return attn_route(ATTN_FWD, p, (hipStream_t)stream);
+    });
 }
 
 int psg_attn_fwd_varlen(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
@@ -468,26 +435,14 @@ int psg_attn_fwd_varlen(const void* q, int64_t ldq, const void* k, int64_t ldk, 
     PSG_REQUIRE(drop_p == 0.f, PSG_ERR_ARG, "attn_fwd_varlen: forward-only entry, drop_p must be 0 (got %g)", (double)drop_p);
     const size_t lds = fwd_lds(S, d);
     PSG_REQUIRE(lds <= 150 * 1024, PSG_ERR_SHAPE, "attn_fwd_varlen: LDS need %zu too large", lds);
-    AttnP p = {};
-    p.q = q; p.k = k; p.v = v; p.out = o; p.lse = lse; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-    p.B = B; p.H = heads; p.L = L; p.S = S; p.d = d; p.scale = scale;
-    p.drop_scale = 1.0f; p.seed = seed; p.kv_len = kv_len;
-    dim3 grid((L + AT_Q - 1) / AT_Q, B * heads);
-    // (the FLOP count is the padded problem's: the key lengths live on the device)
-    ProfScope prof(PROF_ATTN, 4.0 * (double)B * heads * L * S * d, (hipStream_t)stream, (double)B * heads * d * (2.0 * L + 2.0 * S) * (dtype == PSG_BF16 ? 2.0 : 4.0));
-    if ((g_attn_allow & 1) && attn_mfma_fwd_applicable(S, d, dtype, ldq, ldk, ldv, ldo) && aligned16(q) && aligned16(k) && aligned16(v) && aligned8(o)) {
-        ++g_attn_paths[0];
-        return attn_mfma_fwd_varlen(to_mfma(p), (hipStream_t)stream);
-    }
-    if ((g_attn_allow & 2) && f32_mfma_on() && attn_f32_fwd_applicable(S, d, dtype, ldq, ldk, ldv, ldo) && aligned16(q) && aligned16(k) && aligned16(v) && aligned16(o)) {
-        ++g_attn_paths[2];
-        return attn_f32_fwd_varlen(to_f32(p), (hipStream_t)stream);
-    }
-    ++g_attn_paths[1];
-    if (dtype == PSG_F32) hipLaunchKernelGGL((attn_fwd_kernel<float, true>), grid, dim3(256), lds, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, true>), grid, dim3(256), lds, (hipStream_t)stream, p);
-    PSG_LAUNCH_CHECK("attn_fwd_varlen");
-    return PSG_OK;
+    return with_elem(dtype, [&](auto* tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        AttnArgs<T> p = {};
+        p.q = (const T*)q; p.k = (const T*)k; p.v = (const T*)v; p.out = (T*)o; p.lse = lse; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
+        p.B = B; p.H = heads; p.L = L; p.S = S; p.d = d; p.scale = scale;
+        p.drop_scale = 1.0f; p.seed = seed; p.kv_len = kv_len;
+        return attn_route(ATTN_FWD_VARLEN, p, (hipStream_t)stream);
+    });
 }
 
 int psg_attn_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o,
@@ -502,39 +457,16 @@ int psg_attn_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const v
     PSG_REQUIRE(drop_p >= 0.f && drop_p < 1.f, PSG_ERR_ARG, "attn_bwd: drop_p");
     const size_t l1 = dq_lds(S, d), l2 = dkv_lds(d);
     PSG_REQUIRE(l1 <= 150 * 1024 && l2 <= 150 * 1024, PSG_ERR_SHAPE, "attn_bwd: LDS need too large");
-    AttnP p = {};
-    p.q = q; p.k = k; p.v = v; p.o = o; p.dout = dout; p.lse = const_cast<float*>(lse); p.delta = delta;
-    p.dq = dq; p.dk = dk; p.dv = dv;
-    p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
-    p.B = B; p.H = heads; p.L = L; p.S = S; p.d = d; p.scale = scale;
-    p.drop_thresh = drop_p > 0.f ? drop_thresh(drop_p) : 0u; p.drop_scale = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f; p.seed = seed; p.seed_dev = seed_source();
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t rows = (int64_t)B * heads * L;
-    const int gdelta = (int)((rows + 3) / 4);
-    dim3 gq((L + AT_Q - 1) / AT_Q, B * heads), gkv((S + AT_Q - 1) / AT_Q, B * heads);
-    ProfScope prof(PROF_ATTN, 10.0 * (double)B * heads * L * S * d, s, (double)B * heads * d * (4.0 * L + 4.0 * S) * (dtype == PSG_BF16 ? 2.0 : 4.0));
-    if ((g_attn_allow & 1) && attn_mfma_applicable(L, S, d, dtype, ldq, ldk, ldv, ldo) && ((lddo | lddq | lddk | lddv) & 7) == 0 && aligned16(q) && aligned16(k) &&
-        aligned16(v) && aligned16(o) && aligned16(dout) && aligned8(dq) && aligned8(dk) && aligned8(dv)) {
-        ++g_attn_paths[0];
-        return attn_mfma_bwd(to_mfma(p), s);       // (delta is produced inside the dQ kernel)
-    }
-    if ((g_attn_allow & 2) && f32_mfma_on() && attn_f32_applicable(L, S, d, dtype, ldq, ldk, ldv, ldo) && ((lddo | lddq | lddk | lddv) & 3) == 0 && aligned16(q) &&
-        aligned16(k) && aligned16(v) && aligned16(o) && aligned16(dout) && aligned16(dq) && aligned16(dk) && aligned16(dv)) {
-        ++g_attn_paths[2];
-        return attn_f32_bwd(to_f32(p), s);          // (delta is produced inside the dQ kernel)
-    }
-    ++g_attn_paths[1];
-    if (dtype == PSG_F32) {
-        hipLaunchKernelGGL(attn_delta_kernel<float>, dim3(gdelta), dim3(256), 0, s, p);
-        hipLaunchKernelGGL(attn_dq_kernel<float>, gq, dim3(256), l1, s, p);
-        hipLaunchKernelGGL(attn_dkv_kernel<float>, gkv, dim3(256), l2, s, p);
-    } else {
-        hipLaunchKernelGGL(attn_delta_kernel<bf16_t>, dim3(gdelta), dim3(256), 0, s, p);
-        hipLaunchKernelGGL(attn_dq_kernel<bf16_t>, gq, dim3(256), l1, s, p);
-        hipLaunchKernelGGL(attn_dkv_kernel<bf16_t>, gkv, dim3(256), l2, s, p);
-    }
-    PSG_LAUNCH_CHECK("attn_bwd");
-    return PSG_OK;
+    return with_elem(dtype, [&](auto* tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        AttnArgs<T> p = {};
+        p.q = (const T*)q; p.k = (const T*)k; p.v = (const T*)v; p.o = (const T*)o; p.dout = (const T*)dout; p.lse = const_cast<float*>(lse); p.delta = delta;
+        p.dq = (T*)dq; p.dk = (T*)dk; p.dv = (T*)dv;
+        p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
+        p.B = B; p.H = heads; p.L = L; p.S = S; p.d = d; p.scale = scale;
+        p.drop_thresh = drop_p > 0.f ? drop_thresh(drop_p) : 0u; p.drop_scale = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f; p.seed = seed; p.seed_dev = seed_source();
+        return attn_route(ATTN_BWD, p, (hipStream_t)stream);
+    });
 }
 
 }  // extern "C"

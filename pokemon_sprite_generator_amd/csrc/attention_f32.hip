@@ -13,21 +13,9 @@
 // The backward kernels use the same two patterns (dQ: query on the lane; dK / dV: key on the lane, Q and dO in LDS).
 // K / V (or Q / dO) live in LDS as fp32 rows of d*4 + 16 bytes: (d + 4) mod 64 dwords in {4, 20, 36} keeps the 16 rows of
 // a ds_read_b128 group on distinct banks for every head_dim that is a multiple of 16.
-#include "psg_common.h"
+#include "attention.h"
 
 namespace psg {
-
-struct AttnFP {
-    const float *q, *k, *v, *o, *dout;
-    float *out, *dq, *dk, *dv;
-    float* lse; float* delta;
-    int64_t ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
-    int B, H, L, S, d;
-    float scale;
-    uint32_t drop_thresh; float drop_scale; uint64_t seed;
-    const uint64_t* seed_dev;
-    const int32_t* kv_len;                         // forward with per-sample key lengths (NULL otherwise)
-};
 
 __device__ __forceinline__ int acc_row32(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
@@ -88,7 +76,7 @@ __device__ __forceinline__ void acc_cols(const char* img, int stride, int row0, 
 // ------------------------------------------------------------------------------------------------ forward
 // VARLEN: sample b's keys end at kv_len[b] (clamped to [1, S]); key tiles past it are neither staged nor computed
 template <int ND, bool VARLEN = false>
-__global__ __launch_bounds__(256, 1) void attn_fwd_f32(const AttnFP p) {
+__global__ __launch_bounds__(256, 1) void attn_fwd_f32(const AttnArgs<float> p) {
     constexpr int D = ND * 16, HD = D / 2, NDT = (D + 31) / 32, STR = D * 4 + 16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int Sp = (p.S + 31) & ~31;
@@ -180,7 +168,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_f32(const AttnFP p) {
 
 // ------------------------------------------------------------------------------------------------ dQ (query on the lane)
 template <int ND>
-__global__ __launch_bounds__(256, 1) void attn_dq_f32(const AttnFP p) {
+__global__ __launch_bounds__(256, 1) void attn_dq_f32(const AttnArgs<float> p) {
     constexpr int D = ND * 16, HD = D / 2, NDT = (D + 31) / 32, STR = D * 4 + 16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int Sp = (p.S + 31) & ~31;
@@ -267,7 +255,7 @@ __global__ __launch_bounds__(256, 1) void attn_dq_f32(const AttnFP p) {
 
 // ------------------------------------------------------------------------------------------------ dK, dV (key on the lane)
 template <int ND>
-__global__ __launch_bounds__(256, 1) void attn_dkv_f32(const AttnFP p) {
+__global__ __launch_bounds__(256, 1) void attn_dkv_f32(const AttnArgs<float> p) {
     constexpr int D = ND * 16, HD = D / 2, NDT = (D + 31) / 32, STR = D * 4 + 16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int Lp = (p.L + 31) & ~31;
@@ -359,67 +347,42 @@ __global__ __launch_bounds__(256, 1) void attn_dkv_f32(const AttnFP p) {
 constexpr size_t F32_LDS_CAP = 158 * 1024;
 static inline int f32_waves(int rows) { const int t = (rows + 31) / 32; return t < 1 ? 1 : (t > 4 ? 4 : t); }
 static inline size_t f32_lds(int rows, int d) { return 2 * (size_t)((rows + 31) & ~31) * ((size_t)d * 4 + 16) + 128; }   // (+ slack: the last 32-column tile reads past d)
-static inline int f32_nd(int d) { return (d == 16 || d == 32 || d == 64 || d == 80 || d == 160) ? d / 16 : 0; }
+using F32NDs = std::integer_sequence<int, 1, 2, 4, 5, 10>;     // head_dim 16, 32, 64, 80, 160
 
-// returns 1 when the exact-fp32 MFMA kernels handle this problem (forward AND backward: one predicate for both)
-int attn_f32_applicable(int L, int S, int d, int dtype, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo) {
-    if (dtype != PSG_F32 || !f32_nd(d)) return 0;
-    if (((ldq | ldk | ldv | ldo) & 3) != 0) return 0;                    // 16-byte row fragments
-    if (f32_lds(S, d) > F32_LDS_CAP || f32_lds(L, d) > F32_LDS_CAP) return 0;
-    return 1;
+bool attn_f32_applicable(int L, int S, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, bool forward_only) {
+    if (!with_nd(F32NDs{}, d, [](auto) {})) return false;
+    if (((ldq | ldk | ldv | ldo) & 3) != 0) return false;                // 16-byte row fragments
+    return f32_lds(S, d) <= F32_LDS_CAP && (forward_only || f32_lds(L, d) <= F32_LDS_CAP);
 }
 
-#define F32_DISPATCH(KERNEL, ...)                                        \
-    switch (p.d) {                                                       \
-        case 16: hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); break;      \
-        case 32: hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__); break;      \
-        case 64: hipLaunchKernelGGL(KERNEL<4>, __VA_ARGS__); break;      \
-        case 80: hipLaunchKernelGGL(KERNEL<5>, __VA_ARGS__); break;      \
-        default: hipLaunchKernelGGL(KERNEL<10>, __VA_ARGS__); break;     \
-    }
-
-template <int ND> static int varlen_attr() {
-    void (*const k)(const AttnFP) = attn_fwd_f32<ND, true>;
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)F32_LDS_CAP));
-    return PSG_OK;
-}
 int attn_f32_init_attrs() {
-    { const int rc = varlen_attr<1>() | varlen_attr<2>() | varlen_attr<4>() | varlen_attr<5>() | varlen_attr<10>(); if (rc) return rc; }
-#define SET_LDS(K) PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)F32_LDS_CAP))
-    SET_LDS(attn_fwd_f32<1>); SET_LDS(attn_fwd_f32<2>); SET_LDS(attn_fwd_f32<4>); SET_LDS(attn_fwd_f32<5>); SET_LDS(attn_fwd_f32<10>);
-    SET_LDS(attn_dq_f32<1>); SET_LDS(attn_dq_f32<2>); SET_LDS(attn_dq_f32<4>); SET_LDS(attn_dq_f32<5>); SET_LDS(attn_dq_f32<10>);
-    SET_LDS(attn_dkv_f32<1>); SET_LDS(attn_dkv_f32<2>); SET_LDS(attn_dkv_f32<4>); SET_LDS(attn_dkv_f32<5>); SET_LDS(attn_dkv_f32<10>);
-#undef SET_LDS
-    return PSG_OK;
+    return for_each_nd(F32NDs{}, [](auto nd) {
+        constexpr int ND = decltype(nd)::value;
+        return set_max_lds((int)F32_LDS_CAP, attn_fwd_f32<ND, false>, attn_fwd_f32<ND, true>, attn_dq_f32<ND>, attn_dkv_f32<ND>);
+    });
 }
 
-int attn_f32_fwd(const AttnFP& p, hipStream_t s) {
-    F32_DISPATCH(attn_fwd_f32, dim3(p.B * p.H), dim3(64 * f32_waves(p.L)), f32_lds(p.S, p.d), s, p);
-    PSG_LAUNCH_CHECK("attn_fwd_f32");
+template <bool VARLEN>
+int attn_f32_fwd(const AttnArgs<float>& p, hipStream_t s) {
+    if (!with_nd(F32NDs{}, p.d, [&](auto nd) {
+            hipLaunchKernelGGL((attn_fwd_f32<decltype(nd)::value, VARLEN>), dim3(p.B * p.H), dim3(64 * f32_waves(p.L)), f32_lds(p.S, p.d), s, p);
+        }))
+        return set_error(PSG_ERR_SHAPE, "attn_fwd_f32: head_dim %d", p.d);
+    PSG_LAUNCH_CHECK(VARLEN ? "attn_fwd_f32_varlen" : "attn_fwd_f32");
     return PSG_OK;
 }
-int attn_f32_fwd_applicable(int S, int d, int dtype, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo) {
-    if (dtype != PSG_F32 || !f32_nd(d)) return 0;
-    if (((ldq | ldk | ldv | ldo) & 3) != 0) return 0;
-    return f32_lds(S, d) <= F32_LDS_CAP;
-}
-int attn_f32_fwd_varlen(const AttnFP& p, hipStream_t s) {
-    const dim3 grid(p.B * p.H), block(64 * f32_waves(p.L));
-    const size_t lds = f32_lds(p.S, p.d);
-    switch (p.d) {
-        case 16: hipLaunchKernelGGL((attn_fwd_f32<1, true>), grid, block, lds, s, p); break;
-        case 32: hipLaunchKernelGGL((attn_fwd_f32<2, true>), grid, block, lds, s, p); break;
-        case 64: hipLaunchKernelGGL((attn_fwd_f32<4, true>), grid, block, lds, s, p); break;
-        case 80: hipLaunchKernelGGL((attn_fwd_f32<5, true>), grid, block, lds, s, p); break;
-        default: hipLaunchKernelGGL((attn_fwd_f32<10, true>), grid, block, lds, s, p); break;
-    }
-    PSG_LAUNCH_CHECK("attn_fwd_f32_varlen");
-    return PSG_OK;
-}
-int attn_f32_bwd(const AttnFP& p, hipStream_t s) {
-    F32_DISPATCH(attn_dq_f32, dim3(p.B * p.H), dim3(64 * f32_waves(p.L)), f32_lds(p.S, p.d), s, p);
+template int attn_f32_fwd<false>(const AttnArgs<float>&, hipStream_t);
+template int attn_f32_fwd<true>(const AttnArgs<float>&, hipStream_t);
+
+int attn_f32_bwd(const AttnArgs<float>& p, hipStream_t s) {
+    if (!with_nd(F32NDs{}, p.d, [&](auto nd) {
+            hipLaunchKernelGGL(attn_dq_f32<decltype(nd)::value>, dim3(p.B * p.H), dim3(64 * f32_waves(p.L)), f32_lds(p.S, p.d), s, p);
+        }))
+        return set_error(PSG_ERR_SHAPE, "attn_dq_f32: head_dim %d", p.d);
     PSG_LAUNCH_CHECK("attn_dq_f32");
-    F32_DISPATCH(attn_dkv_f32, dim3(p.B * p.H), dim3(64 * f32_waves(p.S)), f32_lds(p.L, p.d), s, p);
+    with_nd(F32NDs{}, p.d, [&](auto nd) {
+        hipLaunchKernelGGL(attn_dkv_f32<decltype(nd)::value>, dim3(p.B * p.H), dim3(64 * f32_waves(p.S)), f32_lds(p.L, p.d), s, p);
+    });
     PSG_LAUNCH_CHECK("attn_dkv_f32");
     return PSG_OK;
 }

@@ -20,24 +20,12 @@
 // are directly the B operands of dV^T += dO^T . P and dK^T += Q^T . dS.
 // Dropout: a stateless 16-bit-per-element hash shared by the two keys of a pair (psg_common.h: drop_hash_pair),
 // regenerated identically in both backward kernels.
-#include "psg_common.h"
+#include "attention.h"
 
 #ifndef PSG_STAGE_U
 #define PSG_STAGE_U 10      // 16-byte loads in flight per lane while staging (8 / 10 / 12 / 20 measured: 10 takes the d = 160 dK/dV kernel from 70 to 60 us, the others within 2 %)
 #endif
 namespace psg {
-
-struct AttnMP {     // mirrored in attention.hip
-    const bf16_t *q, *k, *v, *o, *dout;
-    bf16_t *out, *dq, *dk, *dv;
-    float* lse; float* delta;                      // delta = rowsum(dO * O): written by the dQ kernel, read by dK/dV
-    int64_t ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
-    int B, H, L, S, d;
-    float scale;
-    uint32_t drop_thresh; float drop_scale; uint64_t seed;
-    const uint64_t* seed_dev;
-    const int32_t* kv_len;                         // forward with per-sample key lengths (NULL otherwise)
-};
 
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 #define LDS_TR(ptr) __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ptr))
@@ -99,7 +87,7 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* img, int stride, int row0,
 // VARLEN (psg_attn_fwd_varlen): sample b's keys end at kv_len[b] (clamped to [1, S]) instead of S - only the key tiles below
 // that bound are staged and computed, and the key-tail mask of the last one moves with it
 template <int ND, bool VARLEN = false>
-__global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_fwd_mfma(const AttnMP p) {
+__global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_fwd_mfma(const AttnArgs<bf16_t> p) {
     constexpr int NDT = (ND + 1) / 2;
     constexpr int D32 = NDT * 32;
     constexpr int STR = 2 * ND * 16 + 16;      // row = d values + one 16-byte slot (odd slot count: conflict-free row reads)
@@ -216,7 +204,7 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_fwd_mfma(const At
 // dQ: same query-on-lane structure
 // ------------------------------------------------------------------------------------------------
 template <int ND>
-__global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dq_mfma(const AttnMP p) {
+__global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dq_mfma(const AttnArgs<bf16_t> p) {
     constexpr int NDT = (ND + 1) / 2;
     constexpr int D32 = NDT * 32;
     constexpr int STR = 2 * ND * 16 + 16;      // row = d values + one 16-byte slot (odd slot count: conflict-free row reads)
@@ -328,7 +316,7 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dq_mfma(const Att
 // K/V tile (row reads for the B operands) into a private LDS region.
 // ------------------------------------------------------------------------------------------------
 template <int ND>
-__global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dkv_mfma(const AttnMP p) {
+__global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dkv_mfma(const AttnArgs<bf16_t> p) {
     constexpr int NDT = (ND + 1) / 2;
     constexpr int D32 = NDT * 32;
     constexpr int STR = 2 * ND * 16 + 16;      // row = d values + one 16-byte slot (odd slot count: conflict-free row reads)
@@ -509,7 +497,7 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dkv_mfma(const At
     }
 }
 
-static inline int nd_supported(int d) { return d == 16 || d == 32 || d == 64 || d == 80 || d == 160 || d == 320; }
+using MfmaNDs = std::integer_sequence<int, 1, 2, 4, 5, 10, 20>;     // head_dim 16, 32, 64, 80, 160, 320
 static inline size_t str_bytes(int d) { return 2 * (size_t)d + 16; }
 static inline size_t fwd_lds_m(int S, int d) { return 2 * (size_t)((S + 31) & ~31) * str_bytes(d) + 32; }
 // one wave per 32-row tile of the loop the waves share (queries for fwd/dQ, keys for dK/dV), at most 4: a 7x7 map
@@ -542,69 +530,40 @@ static inline int dkv_waves(int L, int S, int d) {
 }
 static inline size_t dkv_lds_m(int L, int S, int d) { return dkv_lds_w(L, d, dkv_waves(L, S, d)); }
 
-// returns 1 when the MFMA path handles this problem
-int attn_mfma_applicable(int L, int S, int d, int dtype, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo) {
-    if (dtype != PSG_BF16 || !nd_supported(d)) return 0;
-    if (((ldq | ldk | ldv | ldo) & 7) != 0) return 0;                    // 16-byte row fragments
-    if (fwd_lds_m(S, d) > MFMA_LDS_CAP || dkv_lds_m(L, S, d) > MFMA_LDS_CAP) return 0;
-    return 1;
+bool attn_mfma_applicable(int L, int S, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, bool forward_only) {
+    if (!with_nd(MfmaNDs{}, d, [](auto) {})) return false;
+    if (((ldq | ldk | ldv | ldo) & 7) != 0) return false;                // 16-byte row fragments
+    return fwd_lds_m(S, d) <= MFMA_LDS_CAP && (forward_only || dkv_lds_m(L, S, d) <= MFMA_LDS_CAP);
 }
 
-#define ND_DISPATCH(KERNEL, ...)                                                                      \
-    switch (d) {                                                                                      \
-        case 16: hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); break;                                   \
-        case 32: hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__); break;                                   \
-        case 64: hipLaunchKernelGGL(KERNEL<4>, __VA_ARGS__); break;                                   \
-        case 80: hipLaunchKernelGGL(KERNEL<5>, __VA_ARGS__); break;                                   \
-        case 160: hipLaunchKernelGGL(KERNEL<10>, __VA_ARGS__); break;                                 \
-        default: hipLaunchKernelGGL(KERNEL<20>, __VA_ARGS__); break;                                  \
-    }
-
-template <int ND> static int varlen_attr() {
-    void (*const k)(const AttnMP) = attn_fwd_mfma<ND, true>;
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MFMA_LDS_CAP));
-    return PSG_OK;
-}
 int attn_mfma_init_attrs() {
-    { const int rc = varlen_attr<1>() | varlen_attr<2>() | varlen_attr<4>() | varlen_attr<5>() | varlen_attr<10>() | varlen_attr<20>(); if (rc) return rc; }
-#define SET_LDS(K) PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MFMA_LDS_CAP))
-    SET_LDS(attn_fwd_mfma<1>); SET_LDS(attn_fwd_mfma<2>); SET_LDS(attn_fwd_mfma<4>); SET_LDS(attn_fwd_mfma<5>); SET_LDS(attn_fwd_mfma<10>); SET_LDS(attn_fwd_mfma<20>);
-    SET_LDS(attn_dq_mfma<1>); SET_LDS(attn_dq_mfma<2>); SET_LDS(attn_dq_mfma<4>); SET_LDS(attn_dq_mfma<5>); SET_LDS(attn_dq_mfma<10>); SET_LDS(attn_dq_mfma<20>);
-    SET_LDS(attn_dkv_mfma<1>); SET_LDS(attn_dkv_mfma<2>); SET_LDS(attn_dkv_mfma<4>); SET_LDS(attn_dkv_mfma<5>); SET_LDS(attn_dkv_mfma<10>); SET_LDS(attn_dkv_mfma<20>);
-#undef SET_LDS
-    return PSG_OK;
+    return for_each_nd(MfmaNDs{}, [](auto nd) {
+        constexpr int ND = decltype(nd)::value;
+        return set_max_lds((int)MFMA_LDS_CAP, attn_fwd_mfma<ND, false>, attn_fwd_mfma<ND, true>, attn_dq_mfma<ND>, attn_dkv_mfma<ND>);
+    });
 }
 
-int attn_mfma_fwd(const AttnMP& p, hipStream_t s) {
-    const int d = p.d;
-    ND_DISPATCH(attn_fwd_mfma, dim3(p.B * p.H), dim3(64 * attn_waves(p.L)), fwd_lds_m(p.S, d), s, p);
-    PSG_LAUNCH_CHECK("attn_fwd_mfma");
+template <bool VARLEN>
+int attn_mfma_fwd(const AttnArgs<bf16_t>& p, hipStream_t s) {
+    if (!with_nd(MfmaNDs{}, p.d, [&](auto nd) {
+            hipLaunchKernelGGL((attn_fwd_mfma<decltype(nd)::value, VARLEN>), dim3(p.B * p.H), dim3(64 * attn_waves(p.L)), fwd_lds_m(p.S, p.d), s, p);
+        }))
+        return set_error(PSG_ERR_SHAPE, "attn_fwd_mfma: head_dim %d", p.d);
+    PSG_LAUNCH_CHECK(VARLEN ? "attn_fwd_mfma_varlen" : "attn_fwd_mfma");
     return PSG_OK;
 }
-int attn_mfma_fwd_applicable(int S, int d, int dtype, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo) {
-    if (dtype != PSG_BF16 || !nd_supported(d)) return 0;
-    if (((ldq | ldk | ldv | ldo) & 7) != 0) return 0;
-    return fwd_lds_m(S, d) <= MFMA_LDS_CAP;
-}
-int attn_mfma_fwd_varlen(const AttnMP& p, hipStream_t s) {
-    const dim3 grid(p.B * p.H), block(64 * attn_waves(p.L));
-    const size_t lds = fwd_lds_m(p.S, p.d);
-    switch (p.d) {
-        case 16: hipLaunchKernelGGL((attn_fwd_mfma<1, true>), grid, block, lds, s, p); break;
-        case 32: hipLaunchKernelGGL((attn_fwd_mfma<2, true>), grid, block, lds, s, p); break;
-        case 64: hipLaunchKernelGGL((attn_fwd_mfma<4, true>), grid, block, lds, s, p); break;
-        case 80: hipLaunchKernelGGL((attn_fwd_mfma<5, true>), grid, block, lds, s, p); break;
-        case 160: hipLaunchKernelGGL((attn_fwd_mfma<10, true>), grid, block, lds, s, p); break;
-        default: hipLaunchKernelGGL((attn_fwd_mfma<20, true>), grid, block, lds, s, p); break;
-    }
-    PSG_LAUNCH_CHECK("attn_fwd_mfma_varlen");
-    return PSG_OK;
-}
-int attn_mfma_bwd(const AttnMP& p, hipStream_t s) {
-    const int d = p.d;
-    ND_DISPATCH(attn_dq_mfma, dim3(p.B * p.H), dim3(64 * attn_waves(p.L)), fwd_lds_m(p.S, d), s, p);
+template int attn_mfma_fwd<false>(const AttnArgs<bf16_t>&, hipStream_t);
+template int attn_mfma_fwd<true>(const AttnArgs<bf16_t>&, hipStream_t);
+
+int attn_mfma_bwd(const AttnArgs<bf16_t>& p, hipStream_t s) {
+    if (!with_nd(MfmaNDs{}, p.d, [&](auto nd) {
+            hipLaunchKernelGGL(attn_dq_mfma<decltype(nd)::value>, dim3(p.B * p.H), dim3(64 * attn_waves(p.L)), fwd_lds_m(p.S, p.d), s, p);
+        }))
+        return set_error(PSG_ERR_SHAPE, "attn_dq_mfma: head_dim %d", p.d);
     PSG_LAUNCH_CHECK("attn_dq_mfma");
-    ND_DISPATCH(attn_dkv_mfma, dim3(p.B * p.H), dim3(64 * dkv_waves(p.L, p.S, d)), dkv_lds_m(p.L, p.S, d), s, p);
+    with_nd(MfmaNDs{}, p.d, [&](auto nd) {
+        hipLaunchKernelGGL(attn_dkv_mfma<decltype(nd)::value>, dim3(p.B * p.H), dim3(64 * dkv_waves(p.L, p.S, p.d)), dkv_lds_m(p.L, p.S, p.d), s, p);
+    });
     PSG_LAUNCH_CHECK("attn_dkv_mfma");
     return PSG_OK;
 }

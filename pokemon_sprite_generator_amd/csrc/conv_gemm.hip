@@ -5,17 +5,21 @@
 #include <cstring>
 #include <mutex>
 #include <queue>
+#include <type_traits>
 #include <vector>
 
 namespace psg {
 
-#define PSG_TILE_DECL(T, BM, BN)                                                  \
-    extern template int launch_conv<T, BM, BN>(const ConvP&, hipStream_t);        \
+// the (dtype, BM, BN) tiles of conv_gemm_kernel: each is instantiated in a conv_tile_<dtype>_<BM>_<BN>.o (Makefile TILES)
+#define PSG_CONV_TILES(X)                                                      \
+    X(float, 128, 128) X(float, 128, 64) X(float, 64, 64)                      \
+    X(bf16_t, 128, 128) X(bf16_t, 128, 64) X(bf16_t, 64, 64) X(bf16_t, 128, 160) X(bf16_t, 64, 160)
+
+#define X(T, BM, BN)                                                          \
+    extern template int launch_conv<T, BM, BN>(const ConvP&, hipStream_t);    \
     extern template int set_conv_attrs<T, BM, BN>();
-PSG_TILE_DECL(float, 128, 128) PSG_TILE_DECL(float, 128, 64) PSG_TILE_DECL(float, 64, 64)
-PSG_TILE_DECL(bf16_t, 128, 128) PSG_TILE_DECL(bf16_t, 128, 64) PSG_TILE_DECL(bf16_t, 64, 64)
-PSG_TILE_DECL(bf16_t, 128, 160) PSG_TILE_DECL(bf16_t, 64, 160)
-#undef PSG_TILE_DECL
+PSG_CONV_TILES(X)
+#undef X
 
 
 // persistent pointwise kernel (conv_pw.hip)
@@ -156,22 +160,13 @@ static int choose_and_launch(const ConvP& p0, int dtype, hipStream_t s) {
         if (dbg) fprintf(stderr, "psg conv: M=%d N=%d Cin=%d ks=%d tr=%d fast=%d epi_lds=%d -> tile %dx%d splits=%d tapcls=%d\n", p.M, p.N, p.Cin, p.ks, p.transposed,
                          p.fast, p.epi_lds, BM, BN, p.splits, p.tapcls);
     }
-    if (BM == 128 && BN == 128 && p.splits == 1 && conv_pw_applicable(p, dtype)) {
-        const int rc = launch_conv_pw(p, s);
-        if (rc != -1) return rc;
-    }
+    if (BM == 128 && BN == 128 && p.splits == 1 && conv_pw_applicable(p, dtype)) return launch_conv_pw(p, s);
     if (p.tapcls) ++g_tapcls_launches;
-    if (BN == 160 && BM == 64) return launch_conv<bf16_t, 64, 160>(p, s);
-    if (BN == 160) return launch_conv<bf16_t, 128, 160>(p, s);
-    if (dtype == PSG_F32) {
-        if (BM == 128 && BN == 128) return launch_conv<float, 128, 128>(p, s);
-        if (BM == 128 && BN == 64) return launch_conv<float, 128, 64>(p, s);
-        return launch_conv<float, 64, 64>(p, s);
-    } else {
-        if (BM == 128 && BN == 128) return launch_conv<bf16_t, 128, 128>(p, s);
-        if (BM == 128 && BN == 64) return launch_conv<bf16_t, 128, 64>(p, s);
-        return launch_conv<bf16_t, 64, 64>(p, s);
-    }
+#define X(T, TBM, TBN) \
+    if ((dtype == PSG_BF16) == std::is_same<T, bf16_t>::value && BM == TBM && BN == TBN) return launch_conv<T, TBM, TBN>(p, s);
+    PSG_CONV_TILES(X)
+#undef X
+    return set_error(PSG_ERR_ARG, "conv_gemm: no %s %dx%d tile", dtype == PSG_BF16 ? "bf16" : "fp32", BM, BN);
 }
 
 }  // namespace psg
@@ -181,16 +176,10 @@ extern "C" {
 
 int psg_conv_init_attrs(void) {
     int rc;
-    if ((rc = set_conv_attrs<float, 128, 128>())) return rc;
-    if ((rc = set_conv_attrs<bf16_t, 128, 128>())) return rc;
-    if ((rc = set_conv_attrs<float, 128, 64>())) return rc;
-    if ((rc = set_conv_attrs<bf16_t, 128, 64>())) return rc;
-    if ((rc = set_conv_attrs<float, 64, 64>())) return rc;
-    if ((rc = set_conv_attrs<bf16_t, 64, 64>())) return rc;
-    if ((rc = set_conv_attrs<bf16_t, 128, 160>())) return rc;
-    if ((rc = set_conv_attrs<bf16_t, 64, 160>())) return rc;
-    if ((rc = conv_pw_set_attrs())) return rc;
-    return PSG_OK;
+#define X(T, BM, BN) if ((rc = set_conv_attrs<T, BM, BN>())) return rc;
+    PSG_CONV_TILES(X)
+#undef X
+    return conv_pw_set_attrs();
 }
 
 static int conv_setup(const psg_conv_desc* d, ConvP& p) {

@@ -998,9 +998,12 @@ __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(const ConvP p) 
     conv_emit<T>(p, m, n, v, b4, a4, r4, dseed);
 }
 
+// dynamic LDS of a BM x BN conv_gemm_kernel: two [W tile | X tile] buffers of 128-byte rows (+ the border-class row table)
+constexpr int conv_lds(int BM, int BN, bool cls) { return 2 * (BM + BN) * 128 + (cls ? BM * 4 : 0); }
+
 template <typename T, int BM, int BN>
 int launch_conv(const ConvP& p, hipStream_t stream) {
-    const size_t lds = (size_t)2 * (BM + BN) * 128 + (p.tapcls ? BM * 4 : 0);     // (+ the border-class row table)
+    const size_t lds = conv_lds(BM, BN, p.tapcls);
     ConvP q = p;
     q.mtiles = p.tapcls ? tapcls_mtiles(p, BM) : (p.M + BM - 1) / BM;
     q.ntiles = (p.N + BN - 1) / BN;
@@ -1045,20 +1048,14 @@ int launch_conv(const ConvP& p, hipStream_t stream) {
 
 template <typename T, int BM, int BN>
 int set_conv_attrs() {
-    const int lds = 2 * (BM + BN) * 128;
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<T, BM, BN, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<T, BM, BN, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<T, BM, BN, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<T, BM, BN, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<T, BM, BN, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<T, BM, BN, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    constexpr int lds = conv_lds(BM, BN, false);
+    int rc = set_max_lds(lds, conv_gemm_kernel<T, BM, BN, 0>, conv_gemm_kernel<T, BM, BN, 1>, conv_gemm_kernel<T, BM, BN, 2>,
+                         conv_gemm_kernel<T, BM, BN, 0, true>, conv_gemm_kernel<T, BM, BN, 1, true>, conv_gemm_kernel<T, BM, BN, 2, true>);
     if constexpr (BN != 160)
-        PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<T, BM, BN, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    if constexpr (sizeof(T) == 2) {
-        PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<T, BM, BN, 0, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds + BM * 4));
-        PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<T, BM, BN, 1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds + BM * 4));
-    }
-    return PSG_OK;
+        if (!rc) rc = set_max_lds(lds, conv_gemm_kernel<T, BM, BN, 3>);
+    if constexpr (sizeof(T) == 2)
+        if (!rc) rc = set_max_lds(conv_lds(BM, BN, true), conv_gemm_kernel<T, BM, BN, 0, false, true>, conv_gemm_kernel<T, BM, BN, 1, false, true>);
+    return rc;
 }
 
 }  // namespace psg

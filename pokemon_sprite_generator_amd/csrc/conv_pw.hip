@@ -269,12 +269,29 @@ static int pw_kind(const ConvP& p) {
     return -1;
 }
 
+static constexpr int PW_LDS = 2 * 256 * 128 + 4 * 16 * (64 * 2 + 16);
+
+#define PSG_PW_FOR_ALL(X)                                                                                  \
+    X(EK_PLAIN, false, false) X(EK_PLAIN, true, false) X(EK_DROP, false, false) X(EK_DROP, true, false)   \
+    X(EK_GELU, false, false) X(EK_GELU, false, true) X(EK_GELU_DROP, false, false) X(EK_GELU_DROP, false, true) \
+    X(EK_DMUL, true, false)
+
+// PSG_PW_FOR_ALL has a conv_pw_kernel for p's (epilogue kind, aux, preact)
+static bool pw_instantiated(const ConvP& p) {
+    const int ek = pw_kind(p);
+    const bool aux = p.dact_u || p.residual, pre = p.preact != nullptr;
+#define X(EK, AUX, PRE) if (ek == EK && aux == AUX && pre == PRE) return true;
+    PSG_PW_FOR_ALL(X)
+#undef X
+    return false;
+}
+
 // Whole 128 x 128 tiles, K a whole number (>= 3) of 64-channel slices, bf16, the staged (16-byte row) store conditions, an
 // epilogue kind with a branch-free copy, no per-sample add, and enough tiles that a resident workgroup gets at least two.
 bool conv_pw_applicable(const ConvP& p, int dtype) {
     if (!pw_enabled() || dtype != PSG_BF16 || p.taps != 1 || p.stride != 1 || !p.fast || p.ntap > 0 || p.splits > 1) return false;
     if (!p.epi_lds || p.rowadd || p.M % 128 || p.N % 128 || p.KT < 3 || p.Cin % 64) return false;
-    if (pw_kind(p) < 0) return false;
+    if (!pw_instantiated(p)) return false;
     if (p.dact_u && p.residual) return false;
     const int64_t tiles = (int64_t)(p.M / 128) * (p.N / 128);
     if (tiles < 3 * (int64_t)avail_cus_for((double)tiles / 512.0)) return false;   // (1.5 tiles per resident slot: most workgroups get a second tile)
@@ -287,13 +304,6 @@ bool conv_pw_applicable(const ConvP& p, int dtype) {
     if (p.bias && !aligned16(p.bias)) return false;
     return true;
 }
-
-static constexpr int PW_LDS = 2 * 256 * 128 + 4 * 16 * (64 * 2 + 16);
-
-#define PSG_PW_FOR_ALL(X)                                                                                  \
-    X(EK_PLAIN, false, false) X(EK_PLAIN, true, false) X(EK_DROP, false, false) X(EK_DROP, true, false)   \
-    X(EK_GELU, false, false) X(EK_GELU, false, true) X(EK_GELU_DROP, false, false) X(EK_GELU_DROP, false, true) \
-    X(EK_DMUL, true, false)
 
 int conv_pw_set_attrs() {
 #define X(EK, AUX, PRE)                                                                                                                                   \
@@ -326,7 +336,7 @@ int launch_conv_pw(const ConvP& p0, hipStream_t stream) {
     }
     PSG_PW_FOR_ALL(X)
 #undef X
-    if (!done) return -1;                                // (combination without an instantiation: the caller falls back)
+    if (!done) return set_error(PSG_ERR_ARG, "conv_pw: no kernel for epilogue kind %d", ek);       // (conv_pw_applicable rules it out)
     ++g_pw_launches;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "conv_pw launch");

@@ -6,6 +6,7 @@
 #include <stdarg.h>
 #include <math.h>
 #include <stdlib.h>
+#include <initializer_list>
 
 #include "../../include/psg_hip.h"
 
@@ -56,6 +57,14 @@ int avail_cus_for(double rounds_full);
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+// psg_init: let each of the kernels take up to `lds` bytes of dynamic LDS
+template <typename... K>
+static inline int set_max_lds(int lds, K*... kernels) {
+    for (const void* k : {reinterpret_cast<const void*>(kernels)...})
+        PSG_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    return PSG_OK;
+}
 
 // ---- element access -------------------------------------------------------
 template <typename T> struct Elem;

@@ -1041,6 +1041,12 @@ static void wgrad_plan(const psg_wgrad_desc* d, WgP& p) {
     p.steps_per_split = best_sps;
     p.splits = (total_steps + p.steps_per_split - 1) / p.steps_per_split;
 }
+// dynamic LDS of each kernel variant: wgrad_kernel<T, GEOM, BR> double-buffers a [BKP x BR] dY tile and a [BKP x ROWB] X tile;
+// the wide kernel two 8 KB dY + 16 KB X stages; the pipe kernel four 32 KB stages + 1 KB
+template <typename T> constexpr int wgrad_lds(int BR) { return 2 * WgCfg<T>::BKP * (BR * (int)sizeof(T) + WgCfg<T>::ROWB); }
+constexpr int WG_WIDE_LDS = 2 * (8192 + 16384);
+constexpr int WG_PIPE_LDS = 4 * 32768 + 1024;
+
 // tiles land directly in dw: native order, one split, no accumulation
 static bool wgrad_direct(const psg_wgrad_desc* d, const WgP& p) {
     return (d->dw_layout == PSG_W_OHWI || p.taps == 1) && p.splits == 1 && !d->accumulate;
@@ -1052,20 +1058,12 @@ using namespace psg;
 extern "C" {
 
 int psg_wgrad_init_attrs(void) {
-#define PSG_WG_ATTR(G)                                                                                                                   \
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<bf16_t, G>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 256)); \
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<float, G>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32 * 512));
-    PSG_WG_ATTR(0) PSG_WG_ATTR(1) PSG_WG_ATTR(2)
-#undef PSG_WG_ATTR
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<bf16_t, 1, 160>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * (320 + 256)));
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<bf16_t, 2, 160>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * (320 + 256)));
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pipe_kernel<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768 + 1024));
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pipe_kernel<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768 + 1024));
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pipe_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768 + 1024));
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_pipe_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768 + 1024));
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_wide_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (8192 + 16384)));
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_wide_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (8192 + 16384)));
-    return PSG_OK;
+    int rc = set_max_lds(wgrad_lds<bf16_t>(128), wgrad_kernel<bf16_t, 0>, wgrad_kernel<bf16_t, 1>, wgrad_kernel<bf16_t, 2>);
+    if (!rc) rc = set_max_lds(wgrad_lds<float>(128), wgrad_kernel<float, 0>, wgrad_kernel<float, 1>, wgrad_kernel<float, 2>);
+    if (!rc) rc = set_max_lds(wgrad_lds<bf16_t>(160), wgrad_kernel<bf16_t, 1, 160>, wgrad_kernel<bf16_t, 2, 160>);
+    if (!rc) rc = set_max_lds(WG_PIPE_LDS, wgrad_pipe_kernel<1, false>, wgrad_pipe_kernel<2, false>, wgrad_pipe_kernel<1, true>, wgrad_pipe_kernel<2, true>);
+    if (!rc) rc = set_max_lds(WG_WIDE_LDS, wgrad_wide_kernel<1>, wgrad_wide_kernel<2>);
+    return rc;
 }
 
 static int wgrad_check(const psg_wgrad_desc* d) {
@@ -1136,23 +1134,22 @@ int psg_conv_wgrad(const psg_wgrad_desc* d, psg_stream_t stream) {
                        ((double)d->B * d->Hi * d->Wi * d->Cin + (double)p.M * d->Cout) * esz + (double)d->Cout * p.Q * 4.0);
         const int geom = d->stride != 1 || d->Hi != d->Ho || d->Wi != d->Wo ? 0 : (d->ksize == 1 ? 2 : 1);
 #define PSG_WG_LAUNCH(G)                                                                                               \
-        if (d->dtype == PSG_BF16) hipLaunchKernelGGL((wgrad_kernel<bf16_t, G>), dim3(grid), dim3(256), 4 * 64 * 256, s, p); \
-        else hipLaunchKernelGGL((wgrad_kernel<float, G>), dim3(grid), dim3(256), 4 * 32 * 512, s, p);
+        if (d->dtype == PSG_BF16) hipLaunchKernelGGL((wgrad_kernel<bf16_t, G>), dim3(grid), dim3(256), wgrad_lds<bf16_t>(128), s, p); \
+        else hipLaunchKernelGGL((wgrad_kernel<float, G>), dim3(grid), dim3(256), wgrad_lds<float>(128), s, p);
         if (p.wide == 3) {
-            constexpr int PL = 4 * 32768 + 1024;
             if (p.bws) {
-                if (geom == 1) hipLaunchKernelGGL((wgrad_pipe_kernel<1, true>), dim3(grid), dim3(256), PL, s, p);
-                else hipLaunchKernelGGL((wgrad_pipe_kernel<2, true>), dim3(grid), dim3(256), PL, s, p);
+                if (geom == 1) hipLaunchKernelGGL((wgrad_pipe_kernel<1, true>), dim3(grid), dim3(256), WG_PIPE_LDS, s, p);
+                else hipLaunchKernelGGL((wgrad_pipe_kernel<2, true>), dim3(grid), dim3(256), WG_PIPE_LDS, s, p);
             } else {
-                if (geom == 1) hipLaunchKernelGGL((wgrad_pipe_kernel<1, false>), dim3(grid), dim3(256), PL, s, p);
-                else hipLaunchKernelGGL((wgrad_pipe_kernel<2, false>), dim3(grid), dim3(256), PL, s, p);
+                if (geom == 1) hipLaunchKernelGGL((wgrad_pipe_kernel<1, false>), dim3(grid), dim3(256), WG_PIPE_LDS, s, p);
+                else hipLaunchKernelGGL((wgrad_pipe_kernel<2, false>), dim3(grid), dim3(256), WG_PIPE_LDS, s, p);
             }
         } else if (p.wide) {
-            if (geom == 1) hipLaunchKernelGGL((wgrad_wide_kernel<1>), dim3(grid), dim3(256), 2 * (8192 + 16384), s, p);
-            else hipLaunchKernelGGL((wgrad_wide_kernel<2>), dim3(grid), dim3(256), 2 * (8192 + 16384), s, p);
+            if (geom == 1) hipLaunchKernelGGL((wgrad_wide_kernel<1>), dim3(grid), dim3(256), WG_WIDE_LDS, s, p);
+            else hipLaunchKernelGGL((wgrad_wide_kernel<2>), dim3(grid), dim3(256), WG_WIDE_LDS, s, p);
         } else if (p.BR == 160) {
-            if (geom == 1) hipLaunchKernelGGL((wgrad_kernel<bf16_t, 1, 160>), dim3(grid), dim3(256), 2 * 64 * (320 + 256), s, p);
-            else hipLaunchKernelGGL((wgrad_kernel<bf16_t, 2, 160>), dim3(grid), dim3(256), 2 * 64 * (320 + 256), s, p);
+            if (geom == 1) hipLaunchKernelGGL((wgrad_kernel<bf16_t, 1, 160>), dim3(grid), dim3(256), wgrad_lds<bf16_t>(160), s, p);
+            else hipLaunchKernelGGL((wgrad_kernel<bf16_t, 2, 160>), dim3(grid), dim3(256), wgrad_lds<bf16_t>(160), s, p);
         } else if (geom == 0) { PSG_WG_LAUNCH(0) } else if (geom == 1) { PSG_WG_LAUNCH(1) } else { PSG_WG_LAUNCH(2) }
 #undef PSG_WG_LAUNCH
     }
