@@ -2,7 +2,6 @@
 // matrix cores, attention_f32.hip: exact-fp32 matrix cores) and the MFMA families' host entry points.
 #pragma once
 #include "psg_common.h"
-#include <utility>
 
 namespace psg {
 
@@ -22,10 +21,8 @@ struct AttnArgs {
 
 // Head-dim list of an MFMA family: the kernels are instantiated for head_dim = 16 * ND, ND in NDs.  Calls
 // f(std::integral_constant<int, ND>) for the ND of head_dim d; false when d is not in the list.
-template <int... NDs, typename F>
-inline bool with_nd(std::integer_sequence<int, NDs...>, int d, F&& f) {
-    return ((d == 16 * NDs && (f(std::integral_constant<int, NDs>{}), true)) || ...);
-}
+template <typename NDs, typename F>
+inline bool with_nd(NDs nds, int d, F&& f) { return d % 16 == 0 && with_const(nds, d / 16, f); }
 // f(std::integral_constant<int, ND>) for every ND of the list, in order, until one returns non-zero (which is returned)
 template <int... NDs, typename F>
 inline int for_each_nd(std::integer_sequence<int, NDs...>, F&& f) {

@@ -744,6 +744,15 @@ __global__ __launch_bounds__(256) void colsum_tile(const TI* __restrict__ a, int
     }
 }
 
+static int bad_dtype(int dtype) { return set_error(PSG_ERR_DTYPE, "unsupported dtype %d", dtype); }
+// launch(T{}) for the element type T of `dtype` (PSG_ERR_DTYPE if it has none), then the launch check
+template <typename F>
+static int launch_dtype(int dtype, const char* name, F&& launch) {
+    if (!with_dtype(dtype, launch)) return bad_dtype(dtype);
+    PSG_LAUNCH_CHECK(name);
+    return PSG_OK;
+}
+
 }  // namespace psg
 
 using namespace psg;
@@ -759,7 +768,6 @@ int psg_version(void) { return 100; }
 int psg_conv_init_attrs(void);   // conv_gemm.hip
 int psg_wgrad_init_attrs(void);  // wgrad.hip
 int psg_attn_init_attrs(void);   // attention.hip
-int psg_gn_init_attrs(void);     // groupnorm.hip
 
 int psg_init(int device) {
     PSG_HIP_CHECK(hipSetDevice(device));
@@ -767,7 +775,6 @@ int psg_init(int device) {
     if ((rc = psg_conv_init_attrs()) != PSG_OK) return rc;
     if ((rc = psg_wgrad_init_attrs()) != PSG_OK) return rc;
     if ((rc = psg_attn_init_attrs()) != PSG_OK) return rc;
-    if ((rc = psg_gn_init_attrs()) != PSG_OK) return rc;
     return PSG_OK;
 }
 
@@ -907,42 +914,34 @@ int psg_clip_scale_f32(float* g, int64_t n, const float* normsq, float max_norm,
     return PSG_OK;
 }
 
-#define DISPATCH_DTYPE(dtype, CALL_F32, CALL_BF16)                                        \
-    if ((dtype) == PSG_F32) { CALL_F32; }                                                 \
-    else if ((dtype) == PSG_BF16) { CALL_BF16; }                                          \
-    else return set_error(PSG_ERR_DTYPE, "unsupported dtype %d", (int)(dtype));
-
 int psg_nchw_to_nhwc(const float* src, void* dst, int64_t ld_dst, int B, int C, int HW, int dtype, psg_stream_t stream) {
     PSG_REQUIRE(src && dst, PSG_ERR_ARG, "nchw_to_nhwc: null pointer");
     PSG_REQUIRE(B > 0 && C > 0 && HW > 0 && ld_dst >= C, PSG_ERR_SHAPE, "nchw_to_nhwc: bad shape");
     const int g = grid_for((int64_t)B * C * HW, 256);
-    DISPATCH_DTYPE(dtype,
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, src, (float*)dst, ld_dst, B, C, HW),
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, ld_dst, B, C, HW));
-    PSG_LAUNCH_CHECK("nchw_to_nhwc");
-    return PSG_OK;
+    return launch_dtype(dtype, "nchw_to_nhwc", [&](auto elem) {
+        using T = decltype(elem);
+        hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, src, (T*)dst, ld_dst, B, C, HW);
+    });
 }
 
 int psg_nhwc_to_nchw(const void* src, int64_t ld_src, float* dst, int B, int C, int HW, int dtype, psg_stream_t stream) {
     PSG_REQUIRE(src && dst, PSG_ERR_ARG, "nhwc_to_nchw: null pointer");
     PSG_REQUIRE(B > 0 && C > 0 && HW > 0 && ld_src >= C, PSG_ERR_SHAPE, "nhwc_to_nchw: bad shape");
     const int g = grid_for((int64_t)B * C * HW, 256);
-    DISPATCH_DTYPE(dtype,
-        hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)src, ld_src, dst, B, C, HW),
-        hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, ld_src, dst, B, C, HW));
-    PSG_LAUNCH_CHECK("nhwc_to_nchw");
-    return PSG_OK;
+    return launch_dtype(dtype, "nhwc_to_nchw", [&](auto elem) {
+        using T = decltype(elem);
+        hipLaunchKernelGGL(nhwc_to_nchw_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const T*)src, ld_src, dst, B, C, HW);
+    });
 }
 
 int psg_text_pool(const float* text, void* pooled, int64_t ld_pooled, void* text_cast, int B, int S, int D, int dtype,
                   psg_stream_t stream) {
     PSG_REQUIRE(text && pooled, PSG_ERR_ARG, "text_pool: null pointer");
     PSG_REQUIRE(B > 0 && S > 0 && D > 0 && ld_pooled >= D, PSG_ERR_SHAPE, "text_pool: bad shape");
-    DISPATCH_DTYPE(dtype,
-        hipLaunchKernelGGL(text_pool_kernel<float>, dim3(B), dim3(256), 0, (hipStream_t)stream, text, (float*)pooled, ld_pooled, (float*)text_cast, B, S, D),
-        hipLaunchKernelGGL(text_pool_kernel<bf16_t>, dim3(B), dim3(256), 0, (hipStream_t)stream, text, (bf16_t*)pooled, ld_pooled, (bf16_t*)text_cast, B, S, D));
-    PSG_LAUNCH_CHECK("text_pool");
-    return PSG_OK;
+    return launch_dtype(dtype, "text_pool", [&](auto elem) {
+        using T = decltype(elem);
+        hipLaunchKernelGGL(text_pool_kernel<T>, dim3(B), dim3(256), 0, (hipStream_t)stream, text, (T*)pooled, ld_pooled, (T*)text_cast, B, S, D);
+    });
 }
 
 int psg_timestep_sinusoid(const int64_t* t, const float* coeff, void* out, int64_t ld_out, int B, int half, int dtype,
@@ -950,11 +949,22 @@ int psg_timestep_sinusoid(const int64_t* t, const float* coeff, void* out, int64
     PSG_REQUIRE(t && coeff && out, PSG_ERR_ARG, "sinusoid: null pointer");
     PSG_REQUIRE(B > 0 && half > 0 && ld_out >= 2 * half, PSG_ERR_SHAPE, "sinusoid: bad shape");
     const int g = (B * half + 255) / 256;
-    DISPATCH_DTYPE(dtype,
-        hipLaunchKernelGGL(sinusoid_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, t, coeff, (float*)out, ld_out, B, half),
-        hipLaunchKernelGGL(sinusoid_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, t, coeff, (bf16_t*)out, ld_out, B, half));
-    PSG_LAUNCH_CHECK("sinusoid");
-    return PSG_OK;
+    return launch_dtype(dtype, "sinusoid", [&](auto elem) {
+        using T = decltype(elem);
+        hipLaunchKernelGGL(sinusoid_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, t, coeff, (T*)out, ld_out, B, half);
+    });
+}
+
+// Whether the 8-channel form takes an upsample launch: bf16 with 16-byte channel chunks and 32-bit offsets.  A lane writes one
+// chunk of `wr` and gathers from `rd` (forward: input -> output; backward: dy -> dx).  Backward also needs Wo <= 3 * Wi:
+// upsample_bwd8_kernel keeps 6 contributing output columns per input column, enough up to 3x (checked for Wi <= 64) while
+// 7 -> 28 has 8, and its 32-bit b * Ho * Wo.  Launches it does not take go to the 4-channel kernels, which have neither limit.
+static bool upsample8_applies(bool backward, int dtype, const void* rd, int64_t ldrd, const void* wr, int64_t ldwr, int B, int Hi,
+                              int Wi, int Ho, int Wo, int C) {
+    const int64_t in_px = (int64_t)Hi * Wi, out_px = (int64_t)Ho * Wo, rd_px = backward ? out_px : in_px, wr_px = backward ? in_px : out_px;
+    return dtype == PSG_BF16 && (C & 7) == 0 && (ldrd & 7) == 0 && (ldwr & 7) == 0 && aligned16(rd) && aligned16(wr) &&
+           B * wr_px * (C / 8) < (1ll << 31) && rd_px * ldrd < (1ll << 31) && ldwr < (1ll << 24) &&
+           (!backward || (Wo <= 3 * (int64_t)Wi && B * out_px < (1ll << 31)));
 }
 
 int psg_upsample_bilinear_fwd(const void* x, int64_t ldx, void* y, int64_t ldy, int B, int Hi, int Wi, int Ho, int Wo,
@@ -962,9 +972,7 @@ int psg_upsample_bilinear_fwd(const void* x, int64_t ldx, void* y, int64_t ldy, 
     PSG_REQUIRE(x && y, PSG_ERR_ARG, "upsample_fwd: null pointer");
     PSG_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && Ho >= Hi && Wo >= Wi && C > 0 && (C & 3) == 0 && ldx >= C && ldy >= C &&
                 (ldx & 3) == 0 && (ldy & 3) == 0, PSG_ERR_SHAPE, "upsample_fwd: bad shape (C, ld multiples of 4)");
-    // bf16 with 16-byte channel chunks and 32-bit offsets: the 8-channel form
-    if (dtype == PSG_BF16 && (C & 7) == 0 && (ldx & 7) == 0 && (ldy & 7) == 0 && aligned16(x) && aligned16(y) &&
-        (int64_t)B * Ho * Wo * (C / 8) < (1ll << 31) && (int64_t)Hi * Wi * ldx < (1ll << 31) && ldy < (1ll << 24)) {
+    if (upsample8_applies(false, dtype, x, ldx, y, ldy, B, Hi, Wi, Ho, Wo, C)) {
         const int64_t n8 = (int64_t)B * Ho * Wo * (C / 8);
         hipLaunchKernelGGL(upsample_fwd8_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (int)ldx,
                            (bf16_t*)y, (int)ldy, B, Hi, Wi, Ho, Wo, C);
@@ -972,11 +980,10 @@ int psg_upsample_bilinear_fwd(const void* x, int64_t ldx, void* y, int64_t ldy, 
         return PSG_OK;
     }
     const int g = grid_for((int64_t)B * Ho * Wo * (C / 4), 256, 8192);
-    DISPATCH_DTYPE(dtype,
-        hipLaunchKernelGGL(upsample_fwd_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)x, ldx, (float*)y, ldy, B, Hi, Wi, Ho, Wo, C),
-        hipLaunchKernelGGL(upsample_fwd_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, B, Hi, Wi, Ho, Wo, C));
-    PSG_LAUNCH_CHECK("upsample_fwd");
-    return PSG_OK;
+    return launch_dtype(dtype, "upsample_fwd", [&](auto elem) {
+        using T = decltype(elem);
+        hipLaunchKernelGGL(upsample_fwd_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx, (T*)y, ldy, B, Hi, Wi, Ho, Wo, C);
+    });
 }
 
 int psg_upsample_bilinear_bwd(const void* dy, int64_t lddy, void* dx, int64_t lddx, int B, int Hi, int Wi, int Ho,
@@ -984,8 +991,7 @@ int psg_upsample_bilinear_bwd(const void* dy, int64_t lddy, void* dx, int64_t ld
     PSG_REQUIRE(dy && dx, PSG_ERR_ARG, "upsample_bwd: null pointer");
     PSG_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && Ho >= Hi && Wo >= Wi && C > 0 && (C & 3) == 0 && lddy >= C && lddx >= C &&
                 (lddx & 3) == 0 && (lddy & 3) == 0, PSG_ERR_SHAPE, "upsample_bwd: bad shape (C, ld multiples of 4)");
-    if (dtype == PSG_BF16 && (C & 7) == 0 && (lddy & 7) == 0 && (lddx & 7) == 0 && aligned16(dy) && aligned16(dx) &&
-        (int64_t)B * Hi * Wi * (C / 8) < (1ll << 31) && (int64_t)Ho * Wo * lddy < (1ll << 31) && lddx < (1ll << 24)) {
+    if (upsample8_applies(true, dtype, dy, lddy, dx, lddx, B, Hi, Wi, Ho, Wo, C)) {
         const int64_t n8 = (int64_t)B * Hi * Wi * (C / 8);
         hipLaunchKernelGGL(upsample_bwd8_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (int)lddy,
                            (bf16_t*)dx, (int)lddx, B, Hi, Wi, Ho, Wo, C);
@@ -993,11 +999,10 @@ int psg_upsample_bilinear_bwd(const void* dy, int64_t lddy, void* dx, int64_t ld
         return PSG_OK;
     }
     const int g = grid_for((int64_t)B * Hi * Wi * (C / 4), 256, 8192);
-    DISPATCH_DTYPE(dtype,
-        hipLaunchKernelGGL(upsample_bwd_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)dy, lddy, (float*)dx, lddx, B, Hi, Wi, Ho, Wo, C),
-        hipLaunchKernelGGL(upsample_bwd_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, lddy, (bf16_t*)dx, lddx, B, Hi, Wi, Ho, Wo, C));
-    PSG_LAUNCH_CHECK("upsample_bwd");
-    return PSG_OK;
+    return launch_dtype(dtype, "upsample_bwd", [&](auto elem) {
+        using T = decltype(elem);
+        hipLaunchKernelGGL(upsample_bwd_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const T*)dy, lddy, (T*)dx, lddx, B, Hi, Wi, Ho, Wo, C);
+    });
 }
 
 int psg_add(const void* a, int64_t lda, const void* b, int64_t ldb, void* y, int64_t ldy, int64_t rows, int cols,
@@ -1005,11 +1010,10 @@ int psg_add(const void* a, int64_t lda, const void* b, int64_t ldb, void* y, int
     PSG_REQUIRE(a && b && y, PSG_ERR_ARG, "add: null pointer");
     PSG_REQUIRE(rows > 0 && cols > 0 && (cols & 3) == 0 && ((lda | ldb | ldy) & 3) == 0, PSG_ERR_SHAPE, "add: cols/ld must be multiples of 4");
     const int g = grid_for(rows * (cols / 4), 256, 8192);
-    DISPATCH_DTYPE(dtype,
-        hipLaunchKernelGGL(add_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)a, lda, (const float*)b, ldb, (float*)y, ldy, rows, cols),
-        hipLaunchKernelGGL(add_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, lda, (const bf16_t*)b, ldb, (bf16_t*)y, ldy, rows, cols));
-    PSG_LAUNCH_CHECK("add");
-    return PSG_OK;
+    return launch_dtype(dtype, "add", [&](auto elem) {
+        using T = decltype(elem);
+        hipLaunchKernelGGL(add_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const T*)a, lda, (const T*)b, ldb, (T*)y, ldy, rows, cols);
+    });
 }
 
 int psg_set_seed_source(const uint64_t* seed_dev) {
@@ -1026,11 +1030,10 @@ int psg_sum_rows(const void* a, int64_t lda, const void* b, int64_t ldb, const v
                 PSG_ERR_SHAPE, "sum_rows: cols / row strides must be multiples of %d", CH);
     PSG_REQUIRE(aligned16(a) && aligned16(y) && (!b || aligned16(b)) && (!c || aligned16(c)), PSG_ERR_ALIGN, "sum_rows: 16-byte alignment");
     const int g = grid_for(rows * (cols / CH), 256, 65536);
-    DISPATCH_DTYPE(dtype,
-        hipLaunchKernelGGL(sum_rows_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)a, lda, (const float*)b, ldb, (const float*)c, ldc, (float*)y, ldy, rows, cols),
-        hipLaunchKernelGGL(sum_rows_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, lda, (const bf16_t*)b, ldb, (const bf16_t*)c, ldc, (bf16_t*)y, ldy, rows, cols));
-    PSG_LAUNCH_CHECK("sum_rows");
-    return PSG_OK;
+    return launch_dtype(dtype, "sum_rows", [&](auto elem) {
+        using T = decltype(elem);
+        hipLaunchKernelGGL(sum_rows_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const T*)a, lda, (const T*)b, ldb, (const T*)c, ldc, (T*)y, ldy, rows, cols);
+    });
 }
 
 int psg_dropout_apply(const void* x, int64_t ldx, void* y, int64_t ldy, int64_t rows, int cols, float p, uint64_t seed,
@@ -1039,11 +1042,10 @@ int psg_dropout_apply(const void* x, int64_t ldx, void* y, int64_t ldy, int64_t 
     PSG_REQUIRE(rows > 0 && cols > 0 && (cols & 3) == 0 && ((ldx | ldy) & 3) == 0 && p >= 0.f && p < 1.f, PSG_ERR_SHAPE, "dropout_apply: bad shape");
     const int g = grid_for(rows * (cols / 4), 256, 8192);
     const uint32_t th = drop_thresh(p);
-    DISPATCH_DTYPE(dtype,
-        hipLaunchKernelGGL(dropout_apply_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const float*)x, ldx, (float*)y, ldy, rows, cols, th, seed, scale, seed_source()),
-        hipLaunchKernelGGL(dropout_apply_kernel<bf16_t>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, rows, cols, th, seed, scale, seed_source()));
-    PSG_LAUNCH_CHECK("dropout_apply");
-    return PSG_OK;
+    return launch_dtype(dtype, "dropout_apply", [&](auto elem) {
+        using T = decltype(elem);
+        hipLaunchKernelGGL(dropout_apply_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx, (T*)y, ldy, rows, cols, th, seed, scale, seed_source());
+    });
 }
 
 int psg_epilogue_bwd(const void* dy, int64_t lddy, const void* u, int64_t ldu, void* g, int64_t ldg, int64_t rows, int cols,
@@ -1054,11 +1056,10 @@ int psg_epilogue_bwd(const void* dy, int64_t lddy, const void* u, int64_t ldu, v
     const int gr = grid_for(rows * (cols / 4), 256, 8192);
     const uint32_t th = drop_p > 0.f ? drop_thresh(drop_p) : 0u;
     const float ds = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
-    DISPATCH_DTYPE(dtype,
-        hipLaunchKernelGGL(epilogue_bwd_kernel<float>, dim3(gr), dim3(256), 0, (hipStream_t)stream, (const float*)dy, lddy, (const float*)u, ldu, (float*)g, ldg, rows, cols, act, alpha, th, ds, seed, seed_source()),
-        hipLaunchKernelGGL(epilogue_bwd_kernel<bf16_t>, dim3(gr), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, lddy, (const bf16_t*)u, ldu, (bf16_t*)g, ldg, rows, cols, act, alpha, th, ds, seed, seed_source()));
-    PSG_LAUNCH_CHECK("epilogue_bwd");
-    return PSG_OK;
+    return launch_dtype(dtype, "epilogue_bwd", [&](auto elem) {
+        using T = decltype(elem);
+        hipLaunchKernelGGL(epilogue_bwd_kernel<T>, dim3(gr), dim3(256), 0, (hipStream_t)stream, (const T*)dy, lddy, (const T*)u, ldu, (T*)g, ldg, rows, cols, act, alpha, th, ds, seed, seed_source());
+    });
 }
 
 int64_t psg_kpad(int64_t K, int dtype) {
@@ -1086,21 +1087,19 @@ int psg_prep_weight(const void* w, int w_dtype, int w_layout, void* wf, void* wd
                 hipLaunchKernelGGL(prep_wd_bf16_kernel, g, dim3(256), 0, s, (const bf16_t*)w, (bf16_t*)wd, O, I, taps, kpd);
             else
                 hipLaunchKernelGGL((prep_weight_ohwi_kernel<bf16_t, bf16_t>), g, dim3(256), 0, s, (const bf16_t*)w, (bf16_t*)wf, (bf16_t*)wd, O, I, taps, kpf, kpd);
-        } else {
-            DISPATCH_DTYPE(dtype,
-                hipLaunchKernelGGL((prep_weight_ohwi_kernel<float, float>), g, dim3(256), 0, s, (const float*)w, (float*)wf, (float*)wd, O, I, taps, kpf, kpd),
-                hipLaunchKernelGGL((prep_weight_ohwi_kernel<float, bf16_t>), g, dim3(256), 0, s, (const float*)w, (bf16_t*)wf, (bf16_t*)wd, O, I, taps, kpf, kpd));
-        }
+        } else if (!with_dtype(dtype, [&](auto elem) {
+            using T = decltype(elem);
+            hipLaunchKernelGGL((prep_weight_ohwi_kernel<float, T>), g, dim3(256), 0, s, (const float*)w, (T*)wf, (T*)wd, O, I, taps, kpf, kpd);
+        })) return bad_dtype(dtype);
         PSG_LAUNCH_CHECK("prep_weight");
         return PSG_OK;
     }
     PSG_REQUIRE(w_dtype == PSG_F32, PSG_ERR_ARG, "prep_weight: a bf16 source must be OHWI (or 1x1), 16-byte aligned, O and I multiples of 4");
     const dim3 g((I + 31) / 32, (O + 31) / 32);
-    DISPATCH_DTYPE(dtype,
-        hipLaunchKernelGGL(prep_weight_kernel<float>, dim3(g), dim3(256), 0, s, (const float*)w, ohwi, (float*)wf, (float*)wd, O, I, taps, kpf, kpd),
-        hipLaunchKernelGGL(prep_weight_kernel<bf16_t>, dim3(g), dim3(256), 0, s, (const float*)w, ohwi, (bf16_t*)wf, (bf16_t*)wd, O, I, taps, kpf, kpd));
-    PSG_LAUNCH_CHECK("prep_weight");
-    return PSG_OK;
+    return launch_dtype(dtype, "prep_weight", [&](auto elem) {
+        using T = decltype(elem);
+        hipLaunchKernelGGL(prep_weight_kernel<T>, dim3(g), dim3(256), 0, s, (const float*)w, ohwi, (T*)wf, (T*)wd, O, I, taps, kpf, kpd);
+    });
 }
 
 static inline void colsum_plan(int64_t R, int groups, int cols, int& splits, int64_t& rps) {
@@ -1132,23 +1131,23 @@ int psg_colsum(const void* a, int64_t lda, void* out, int64_t ld_out, int64_t R,
     colsum_plan(R, groups, cols, splits, rps);
     hipStream_t st = (hipStream_t)stream;
     const int cb = (cols + 63) / 64;
-    float* wsf = (float*)ws;
+    // one colsum_tile launch: `rows` rows of src per group in `nsplit` splits of `per` rows, element types from the dtype codes
+    const auto tile = [&](int src_dtype, int dst_dtype, int gy, const void* src, int64_t ld_src, void* dst, int64_t ld_dst, int64_t rows,
+                          int nsplit, int64_t per, int acc) {
+        with_dtype(src_dtype, [&](auto ei) { with_dtype(dst_dtype, [&](auto eo) {
+            using TI = decltype(ei); using TO = decltype(eo);
+            hipLaunchKernelGGL((colsum_tile<TI, TO>), dim3(cb, gy), dim3(256), 0, st, (const TI*)src, ld_src, (TO*)dst, ld_dst, rows, cols, nsplit, per, acc);
+        }); });
+    };
     if (splits == 1) {      // single pass straight into the output
-        dim3 g1(cb, groups);
-        if (dtype == PSG_F32 && out_dtype == PSG_F32) hipLaunchKernelGGL((colsum_tile<float, float>), g1, dim3(256), 0, st, (const float*)a, lda, (float*)out, ld_out, R, cols, 1, R, accumulate);
-        else if (dtype == PSG_F32) hipLaunchKernelGGL((colsum_tile<float, bf16_t>), g1, dim3(256), 0, st, (const float*)a, lda, (bf16_t*)out, ld_out, R, cols, 1, R, 0);
-        else if (out_dtype == PSG_F32) hipLaunchKernelGGL((colsum_tile<bf16_t, float>), g1, dim3(256), 0, st, (const bf16_t*)a, lda, (float*)out, ld_out, R, cols, 1, R, accumulate);
-        else hipLaunchKernelGGL((colsum_tile<bf16_t, bf16_t>), g1, dim3(256), 0, st, (const bf16_t*)a, lda, (bf16_t*)out, ld_out, R, cols, 1, R, 0);
+        tile(dtype, out_dtype, groups, a, lda, out, ld_out, R, 1, R, accumulate);
         PSG_LAUNCH_CHECK("colsum");
         return PSG_OK;
     }
-    dim3 g1(cb, groups * splits);
-    if (dtype == PSG_F32) hipLaunchKernelGGL((colsum_tile<float, float>), g1, dim3(256), 0, st, (const float*)a, lda, wsf, (int64_t)cols, R, cols, splits, rps, 0);
-    else hipLaunchKernelGGL((colsum_tile<bf16_t, float>), g1, dim3(256), 0, st, (const bf16_t*)a, lda, wsf, (int64_t)cols, R, cols, splits, rps, 0);
+    tile(dtype, PSG_F32, groups * splits, a, lda, ws, cols, R, splits, rps, 0);
     PSG_LAUNCH_CHECK("colsum_stage1");
-    dim3 g2(cb, groups);    // second stage: the partial slab [groups][splits][cols] is itself a column-sum problem
-    if (out_dtype == PSG_F32) hipLaunchKernelGGL((colsum_tile<float, float>), g2, dim3(256), 0, st, (const float*)wsf, (int64_t)cols, (float*)out, ld_out, (int64_t)splits, cols, 1, (int64_t)splits, accumulate);
-    else hipLaunchKernelGGL((colsum_tile<float, bf16_t>), g2, dim3(256), 0, st, (const float*)wsf, (int64_t)cols, (bf16_t*)out, ld_out, (int64_t)splits, cols, 1, (int64_t)splits, 0);
+    // second stage: the partial slab [groups][splits][cols] is itself a column-sum problem
+    tile(PSG_F32, out_dtype, groups, ws, cols, out, ld_out, splits, 1, splits, accumulate);
     PSG_LAUNCH_CHECK("colsum_stage2");
     return PSG_OK;
 }

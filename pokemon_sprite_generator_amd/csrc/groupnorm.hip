@@ -1,14 +1,20 @@
 // GroupNorm (+ fused SiLU) forward / backward, channels-last [B, HW, C].  Roofline: HBM.
 //
-// FUSED (register-resident) path - every shape of the U-Net: one workgroup owns one (sample, channel slab) - a run of
-// whole groups whose width is a multiple of the 16-byte chunk - and keeps the slab's HW x slabC values IN REGISTERS
-// (<= 16 packed 16-byte chunks per lane), so the tensor is read from memory exactly once:
+// Two routes, chosen per launch by gn_route_fwd / gn_route_bwd (nothing else decides which kernels run).
+//
+// FUSED (register-resident): one workgroup owns one (sample, channel slab) - a run of whole groups whose width is a
+// multiple of the chunk - and keeps the slab's HW x slabC values IN REGISTERS (<= 16 packed chunks per lane forward, <= 8
+// per tensor backward), so the tensor is read from memory exactly once:
 //   forward : load -> channel sums -> group mean -> centred second pass over the registers (exact two-pass variance,
 //             no E[x^2]-E[x]^2 cancellation) -> normalise (+SiLU) -> store              = 1 read + 1 write
 //   backward: load x, dy -> per-channel (sum dz*xhat, sum dz) -> group sums -> dx (+ the bypass gradient) -> store;
 //             per-sample channel sums go to the workspace for dgamma / dbeta            = 2(+1) reads + 1 write
-// against 2 + 1 and 4 + 1 passes of the split kernels below (kept as the general fallback: shapes whose slab does not
-// fit the register budget).  Reductions are fixed-order LDS trees, as below: results are run-to-run identical.
+// Reductions are fixed-order LDS trees, as below: results are run-to-run identical.
+//
+// SPLIT: 2 + 1 (forward) and 4 + 1 (backward) passes, for every shape whose slab does not fit the fused kernels' lanes,
+// registers or LDS.  With 32 groups the bf16 U-Net (27x27x320/640, 14x14x640/1280, 7x7 and 4x4 x 1280/2560) is fused
+// throughout; its fp32 backward at 27x27x640 is SPLIT (a 729-pixel slab needs more than 8 chunks per lane in 512 lanes): a
+// product path.  So are larger maps (backward from 54x54x256, forward too at 108x108x128) and bf16 groups narrower than a chunk.
 //
 // Every pass streams whole pixel rows with 16-byte vectors per lane (a thread owns one fixed
 // 16-byte channel chunk and walks pixels), so loads/stores are fully coalesced for every
@@ -36,12 +42,14 @@ constexpr int GN_MAXSPLIT = 16;
 constexpr int GN_U = GN_U_VALUE;     // loads in flight per lane, forward passes
 constexpr int GN_UB = GN_UB_VALUE;   // backward passes (two operands each)
 
-struct GnP {
+// Arguments of every GroupNorm kernel.  A launch fills the plan of its own route only; PP (pixel lanes) belongs to both.
+struct GnArgs {
     const void *x, *dy, *dres; void *y, *dx;
-    const float *gamma, *beta; float *mean, *rstd, *ws, *dgamma, *dbeta;
-    int64_t ldx, ldy, lddy, lddx, lddres;
-    int B, HW, C, G, Cg, CC, PP, NS, pps;   // CC chunks per row, PP pixel lanes, NS splits, pps pixels per split
-    float eps; int silu, accumulate;
+    const float *gamma, *beta; float *mean, *rstd, *ws;   // ws: split - partial sums; fused backward - per-sample channel sums
+    int64_t ldx, ldy, lddy, lddres, lddx;
+    int B, HW, C, G, Cg, slabC, CCs, PP, nslab, SG;   // fused: slabC channels = CCs chunks = SG groups per slab, nslab slabs
+    float eps; int silu;
+    int CC, NS, pps;                                  // split: CC chunks per row, NS splits, pps pixels per split
 };
 
 template <typename T> struct Vec;
@@ -67,7 +75,7 @@ template <> struct Vec<bf16_t> {
 
 // ---------------------------------------------------------------- forward: partial statistics
 template <typename T>
-__global__ void gn_stats_kernel(const GnP p) {
+__global__ void gn_stats_kernel(const GnArgs p) {
     constexpr int N = Vec<T>::N;
     extern __shared__ __attribute__((aligned(16))) float sm[];      // [PP][C][2]
     const int b = blockIdx.x / p.NS, split = blockIdx.x - b * p.NS;
@@ -107,7 +115,7 @@ __global__ void gn_stats_kernel(const GnP p) {
 
 // ---------------------------------------------------------------- forward: apply
 template <typename T>
-__global__ void gn_apply_kernel(const GnP p) {
+__global__ void gn_apply_kernel(const GnArgs p) {
     constexpr int N = Vec<T>::N;
     extern __shared__ __attribute__((aligned(16))) float sm[];      // [G][2] mean, rstd
     const int b = blockIdx.x / p.NS, split = blockIdx.x - b * p.NS;
@@ -157,7 +165,7 @@ __global__ void gn_apply_kernel(const GnP p) {
 
 // ---------------------------------------------------------------- backward: per-channel partials
 template <typename T>
-__global__ void gn_bwd_reduce_kernel(const GnP p) {
+__global__ void gn_bwd_reduce_kernel(const GnArgs p) {
     constexpr int N = Vec<T>::N;
     extern __shared__ __attribute__((aligned(16))) float sm[];      // [PP][C][2]
     const int b = blockIdx.x / p.NS, split = blockIdx.x - b * p.NS;
@@ -206,7 +214,7 @@ __global__ void gn_bwd_reduce_kernel(const GnP p) {
 
 // ---------------------------------------------------------------- backward: dx
 template <typename T>
-__global__ void gn_bwd_apply_kernel(const GnP p) {
+__global__ void gn_bwd_apply_kernel(const GnArgs p) {
     constexpr int N = Vec<T>::N;
     extern __shared__ __attribute__((aligned(16))) float sm[];      // [C][2] per-sample channel sums, then [G][2]
     float* gs = sm + (int64_t)p.C * 2;
@@ -300,14 +308,6 @@ __global__ __launch_bounds__(1024) void gn_param_reduce_kernel(const float* __re
 
 
 // ---------------------------------------------------------------- fused, register-resident kernels
-struct GnF {
-    const void *x, *dy, *dres; void *y, *dx;
-    const float *gamma, *beta; float *mean, *rstd, *chan_ws;
-    int64_t ldx, ldy, lddy, lddres, lddx;
-    int B, HW, C, G, Cg, slabC, CCs, PP, nslab, SG;   // slabC channels = CCs chunks = SG groups per slab; PP pixel lanes
-    float eps; int silu;
-};
-
 // A chunk of N consecutive channels as it lies in memory (bf16 stays packed in registers).  The forward kernel moves
 // 16-byte chunks; the backward kernel, which holds TWO tensors plus twice the per-channel constants, moves 8-byte
 // chunks: the per-element state (constants, temporaries) halves while the slab bytes per lane stay the same.
@@ -329,7 +329,7 @@ template <typename T, int N> __device__ __forceinline__ void chk_st(void* p, con
 // Two levels so that the whole workgroup works (nseg = blockDim / slabC segments of the pixel lanes in parallel) instead
 // of slabC lanes walking PP dependent LDS reads each: the reduction phases are dead time for the memory pipe.
 // `seg` (nseg * slabC floats) and `chan` (slabC floats) are scratch.  Fixed order.  Ends with a barrier.
-__device__ __forceinline__ void gn_tree(const GnF& p, const float* part, float* seg, float* chan, float* grp, int stride, int comp) {
+__device__ __forceinline__ void gn_tree(const GnArgs& p, const float* part, float* seg, float* chan, float* grp, int stride, int comp) {
     const int nseg = max(1, min((int)blockDim.x / p.slabC, p.PP));
     __syncthreads();
     for (int idx = threadIdx.x; idx < nseg * p.slabC; idx += blockDim.x) {      // (one trip unless slabC > blockDim)
@@ -358,9 +358,24 @@ __device__ __forceinline__ void gn_tree(const GnF& p, const float* part, float* 
     if (grp) __syncthreads();
 }
 
+// Dynamic LDS of the fused kernels, workgroup of `threads` lanes: floats per region, in order, and in total.  Backward has K = 2
+// values per entry.  part: [PP][slabC][K] per-lane partials | seg: [nseg][slabC][K] (gn_tree: nseg * slabC <= max(threads, slabC)) |
+// chan: [slabC] channel totals, backward [4][slabC] | then 2 * K group tables of [SG].  Kernels carve by it, the host sizes by it.
+struct GnLds { int part, seg, chan, total; };
+template <bool BWD>
+__host__ __device__ __forceinline__ GnLds gn_lds(int PP, int slabC, int SG, int threads) {
+    constexpr int K = BWD ? 2 : 1;
+    GnLds l;
+    l.part = (int)((int64_t)PP * slabC * K);
+    l.seg = K * (threads > slabC ? threads : slabC);
+    l.chan = (BWD ? 4 : 1) * slabC;
+    l.total = PP * slabC * K + l.seg + l.chan + 2 * K * SG;      // (not l.part + ...: hipcc then selects other code for the kernels)
+    return l;
+}
+
 // Both components of part[pl][ch][2] in one walk (the backward kernel's two sums: half the barriers, 8-byte LDS reads).
 // `seg` holds 2 * nseg * slabC floats.  Same summation order per component as gn_tree.
-__device__ __forceinline__ void gn_tree2(const GnF& p, const float* part, float* seg, float* c0, float* c1) {
+__device__ __forceinline__ void gn_tree2(const GnArgs& p, const float* part, float* seg, float* c0, float* c1) {
     const int nseg = max(1, min((int)blockDim.x / p.slabC, p.PP));
     const f32x2* part2 = reinterpret_cast<const f32x2*>(part);
     f32x2* seg2 = reinterpret_cast<f32x2*>(seg);
@@ -403,13 +418,14 @@ __device__ __forceinline__ void gn_fence(Raw (&raw)[R]) {
 }
 
 template <typename T, int N, int R, bool SILU>
-__global__ __launch_bounds__(512, 4) void gn_fwd_fused_kernel(const GnF p) {
+__global__ __launch_bounds__(512, 4) void gn_fwd_fused_kernel(const GnArgs p) {
     typedef typename Chk<T, N>::type Raw;
     constexpr bool FAST = sizeof(T) == 2;                            // bf16 compute: v_rcp / fma forms (psg_common.h)
-    extern __shared__ __attribute__((aligned(16))) float sm[];      // [PP][slabC] partials | [nseg][slabC] | [slabC] | [SG] | [SG]
-    float* segb = sm + (int64_t)p.PP * p.slabC;
-    float* chan = segb + max((int)blockDim.x, p.slabC);
-    float* gmean = chan + p.slabC;
+    extern __shared__ __attribute__((aligned(16))) float sm[];      // (regions: gn_lds)
+    const GnLds l = gn_lds<false>(p.PP, p.slabC, p.SG, (int)blockDim.x);
+    float* segb = sm + l.part;
+    float* chan = segb + l.seg;
+    float* gmean = chan + l.chan;
     float* gvar = gmean + p.SG;
     const int lid = gn_xcd_lid();
     const int b = lid / p.nslab, slab = lid - b * p.nslab;
@@ -496,13 +512,14 @@ __global__ __launch_bounds__(512, 4) void gn_fwd_fused_kernel(const GnF p) {
 }
 
 template <typename T, int N, int R, bool SILU, bool RES>
-__global__ __launch_bounds__(512, 4) void gn_bwd_fused_kernel(const GnF p) {
+__global__ __launch_bounds__(512, 4) void gn_bwd_fused_kernel(const GnArgs p) {
     typedef typename Chk<T, N>::type Raw;
     constexpr bool FAST = sizeof(T) == 2;
-    extern __shared__ __attribute__((aligned(16))) float sm[];      // [PP][slabC][2] partials | [nseg][slabC][2] | [4][slabC] | 4 x [SG]
-    float* segb = sm + (int64_t)p.PP * p.slabC * 2;
-    float* chan = segb + 2 * max((int)blockDim.x, p.slabC);          // [0],[1]: gamma-weighted; [2],[3]: raw channel totals
-    float* g1 = chan + 4 * p.slabC;
+    extern __shared__ __attribute__((aligned(16))) float sm[];      // (regions: gn_lds)
+    const GnLds l = gn_lds<true>(p.PP, p.slabC, p.SG, (int)blockDim.x);
+    float* segb = sm + l.part;
+    float* chan = segb + l.seg;           // [0],[1]: gamma-weighted; [2],[3]: raw channel totals
+    float* g1 = chan + l.chan;
     float* g2 = g1 + p.SG;
     float* gmu = g2 + p.SG;          // the slab's group statistics, staged once (per-element global addresses of mean /
     float* grs = gmu + p.SG;         // rstd kept live across the passes cost 32 registers)
@@ -561,7 +578,7 @@ __global__ __launch_bounds__(512, 4) void gn_bwd_fused_kernel(const GnF p) {
         const float t0 = chan[2 * p.slabC + ch], t1 = chan[3 * p.slabC + ch];
         const float m_ = gmu[ch / p.Cg], r_ = grs[ch / p.Cg];
         const float dzh = r_ * t0 - m_ * r_ * t1;          // sum dz * xhat
-        float* o = p.chan_ws + ((int64_t)b * p.C + slab * p.slabC + ch) * 2;
+        float* o = p.ws + ((int64_t)b * p.C + slab * p.slabC + ch) * 2;
         o[0] = dzh; o[1] = t1;
         const float gm = p.gamma[slab * p.slabC + ch];
         chan[ch] = dzh * gm;                // sum(dxhat * xhat) contribution
@@ -612,7 +629,7 @@ static int gcd_i(int a, int b) { while (b) { const int t = a % b; a = b; b = t; 
 
 // Slab plan of the fused kernels: the widest run of whole groups (a multiple of the 16-byte chunk that divides C) whose
 // HW x slabC values fit rmax chunks per lane within max_threads lanes.  Returns R (4, 8 or 16), or 0 = use the split kernels.
-static int gn_fused_plan(GnF& p, int N, int max_threads, int rmax) {
+static int gn_fused_plan(GnArgs& p, int N, int max_threads, int rmax) {
     static int off = -1;
     if (off < 0) { const char* e = getenv("PSG_GN_FUSED"); off = (e && atoi(e) == 0) ? 1 : 0; }
     if (off) return 0;
@@ -644,14 +661,50 @@ static int gn_fused_plan(GnF& p, int N, int max_threads, int rmax) {
     return r <= 4 ? 4 : (r <= 8 ? 8 : 16);
 }
 
-static int gn_plan(GnP& p, int dtype) {
-    const int N = dtype == PSG_BF16 ? 8 : 4;
-    PSG_REQUIRE(p.B > 0 && p.HW > 0 && p.C > 0 && p.G > 0 && p.C % p.G == 0, PSG_ERR_SHAPE, "groupnorm: B=%d HW=%d C=%d G=%d", p.B, p.HW, p.C, p.G);
-    PSG_REQUIRE(p.C % N == 0, PSG_ERR_SHAPE, "groupnorm: C=%d must be a multiple of %d", p.C, N);
-    PSG_REQUIRE(p.G <= 64, PSG_ERR_SHAPE, "groupnorm: G=%d > 64", p.G);
+// the shape checks of every launch, whichever route it takes (N: elements per 16-byte chunk)
+static int gn_check_shape(int N, int B, int HW, int C, int G) {
+    PSG_REQUIRE(B > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0, PSG_ERR_SHAPE, "groupnorm: B=%d HW=%d C=%d G=%d", B, HW, C, G);
+    PSG_REQUIRE(C % N == 0, PSG_ERR_SHAPE, "groupnorm: C=%d must be a multiple of %d", C, N);
+    PSG_REQUIRE(G <= 64, PSG_ERR_SHAPE, "groupnorm: G=%d > 64", G);
+    PSG_REQUIRE(C / N <= 1024, PSG_ERR_SHAPE, "groupnorm: C=%d too wide", C);
+    return PSG_OK;
+}
+
+// The fused kernel variants, declared once: forward <T, 16-byte chunk, R, SILU>, backward <T, N, R, SILU, RES>
+using GnFwdRs = std::integer_sequence<int, 4, 8, 16>;
+using GnBwdRs = std::integer_sequence<int, 4, 8>;
+template <typename T> struct GnBwdNs;
+template <> struct GnBwdNs<float> { using list = std::integer_sequence<int, 2>; };
+template <> struct GnBwdNs<bf16_t> { using list = std::integer_sequence<int, 4, 8>; };
+
+// What a launch runs.  `p` holds the shape and the plan of the chosen route; the entry point adds pointers, strides, flags.
+struct GnRoute {
+    GnArgs p;
+    bool fused;            // one register-resident kernel <N, R>, else the split kernels
+    int N, R;              // fused: channels per chunk, chunks per lane
+    int grid, threads;
+    size_t lds, lds2;      // dynamic LDS bytes: fused kernel | first and second split kernel
+};
+
+// 256-lane workgroups first: four or more of them share a CU and their load / reduce / store phases interleave
+// (measured: -9 % GroupNorm time against 512 lanes); 512 lanes where a 256-lane slab cannot hold whole groups
+static int gn_fused_plan2(GnArgs& p, int N, int rmax) {
+    const int R = gn_fused_plan(p, N, 256, rmax);
+    return R ? R : gn_fused_plan(p, N, 512, rmax);
+}
+
+// Fused if a slab plan was found (rt.R) and its LDS fits; else the split plan: 16-byte chunks, pixel splits to fill the chip
+// (lds2: the second split kernel's LDS)
+template <bool BWD>
+static GnRoute gn_route_end(GnRoute rt, int dtype, size_t lds2) {
+    rt.threads = rt.p.CCs * rt.p.PP;
+    rt.lds = (size_t)gn_lds<BWD>(rt.p.PP, rt.p.slabC, rt.p.SG, rt.threads).total * sizeof(float);
+    rt.fused = rt.R && rt.lds <= 64 * 1024;
+    if (rt.fused) { rt.grid = rt.p.B * rt.p.nslab; return rt; }
+    GnArgs& p = rt.p;
+    p.slabC = p.CCs = p.nslab = p.SG = 0;      // (what a slab plan that did not fit has left)
     p.Cg = p.C / p.G;
-    p.CC = p.C / N;
-    PSG_REQUIRE(p.CC <= 1024, PSG_ERR_SHAPE, "groupnorm: C=%d too wide", p.C);
+    p.CC = p.C / (dtype == PSG_BF16 ? 8 : 4);
     p.PP = 256 / p.CC;
     if (p.PP < 1) p.PP = 1;
     if (p.PP * p.CC < 64) p.PP = (64 + p.CC - 1) / p.CC;
@@ -662,15 +715,47 @@ static int gn_plan(GnP& p, int dtype) {
     if (ns < 1) ns = 1;
     p.pps = (p.HW + ns - 1) / ns;
     p.NS = (p.HW + p.pps - 1) / p.pps;
-    return PSG_OK;
+    rt.threads = p.CC * p.PP; rt.grid = p.B * p.NS;
+    rt.lds = (size_t)p.PP * p.C * 2 * sizeof(float); rt.lds2 = lds2;
+    return rt;
+}
+
+// The routes.  Pure functions of a checked shape (gn_check_shape) and the switches PSG_GN_FUSED, PSG_GN_MAXT, PSG_GN_BWD_WIDE.
+static GnRoute gn_route_fwd(int dtype, int B, int HW, int C, int G) {
+    GnRoute rt = {};
+    rt.p.B = B; rt.p.HW = HW; rt.p.C = C; rt.p.G = G;
+    rt.N = dtype == PSG_BF16 ? 8 : 4;
+    rt.R = gn_fused_plan2(rt.p, rt.N, 16);
+    return gn_route_end<false>(rt, dtype, (size_t)G * 2 * sizeof(float));
+}
+
+static GnRoute gn_route_bwd(int dtype, int B, int HW, int C, int G, bool has_dres) {
+    GnRoute rt = {};
+    rt.p.B = B; rt.p.HW = HW; rt.p.C = C; rt.p.G = G;
+    // 8-byte chunks, <= 8 per lane and tensor (16 fit the register file since the v_rcp forms - 120 VGPRs - and let the
+    // 27x27 slabs run in 256 lanes, but measured no faster: 640 vs 648 us over the U-Net's eight shapes)
+    rt.N = dtype == PSG_BF16 ? 4 : 2;
+    rt.R = gn_fused_plan2(rt.p, rt.N, 8);
+    // These kernels wait on memory (round 4, rocprofv3: 50 % of the wave cycles; the LDS pipe is active 1 % of them, so its
+    // bank conflicts do not matter) and their slab rows are narrower than a 128-byte line (27x27x320: 40-byte rows, 3.1 TB/s;
+    // 14x14x640: 80 bytes, 4.5).  16-byte chunks double the row a (lanes x chunks) budget covers: with the bypass gradient
+    // as a third input stream -8...-20 % per launch (27x27x640 303 -> 267 us, 14x14x1280 143 -> 122), without it +-0
+    // (14x14x640 +10 %): taken for the bypass form only.
+    static int wide = -1;                          // PSG_GN_BWD_WIDE=0: 8-byte chunks only (A/B)
+    if (wide < 0) { const char* e = getenv("PSG_GN_BWD_WIDE"); wide = (e && atoi(e) == 0) ? 0 : 1; }
+    if (wide && has_dres && dtype == PSG_BF16 && rt.R && rt.p.slabC * 2 < 128) {
+        GnArgs p2 = rt.p;
+        int R2 = gn_fused_plan(p2, 8, 256, 8);
+        if (!R2 || p2.slabC <= rt.p.slabC) { p2 = rt.p; R2 = gn_fused_plan(p2, 8, 512, 8); }
+        if (R2 && p2.slabC > rt.p.slabC) { rt.p = p2; rt.R = R2; rt.N = 8; }
+    }
+    return gn_route_end<true>(rt, dtype, ((size_t)C + G) * 2 * sizeof(float));
 }
 
 }  // namespace psg
 using namespace psg;
 
 extern "C" {
-
-int psg_gn_init_attrs(void) { return PSG_OK; }
 
 int64_t psg_groupnorm_fwd_workspace_bytes(int B, int G) { return (int64_t)B * GN_MAXSPLIT * G * 2 * sizeof(float); }
 int64_t psg_groupnorm_bwd_workspace_bytes(int B, int C) { return (int64_t)B * (GN_MAXSPLIT + 1) * C * 2 * sizeof(float); }
@@ -680,47 +765,28 @@ int psg_groupnorm_fwd(const void* x, int64_t ldx, void* y, int64_t ldy, const fl
                       psg_stream_t stream) {
     PSG_REQUIRE(x && y && gamma && beta && mean && rstd && ws, PSG_ERR_ARG, "groupnorm_fwd: null pointer");
     PSG_REQUIRE(dtype == PSG_F32 || dtype == PSG_BF16, PSG_ERR_DTYPE, "groupnorm_fwd: dtype %d", dtype);
-    GnP p = {};
-    p.x = x; p.y = y; p.gamma = gamma; p.beta = beta; p.mean = mean; p.rstd = rstd; p.ws = (float*)ws;
-    p.ldx = ldx; p.ldy = ldy; p.B = B; p.HW = HW; p.C = C; p.G = G; p.eps = eps; p.silu = silu;
-    int rc = gn_plan(p, dtype);
-    if (rc) return rc;
-    const int N = dtype == PSG_BF16 ? 8 : 4;
+    const int N = dtype == PSG_BF16 ? 8 : 4;      // elements per 16-byte chunk
+    { const int rc = gn_check_shape(N, B, HW, C, G); if (rc) return rc; }
     PSG_REQUIRE(ldx >= C && ldy >= C && ldx % N == 0 && ldy % N == 0 && aligned16(x) && aligned16(y), PSG_ERR_ALIGN,
                 "groupnorm_fwd: rows must be 16-byte aligned (ld multiple of %d)", N);
+    GnRoute rt = gn_route_fwd(dtype, B, HW, C, G);
+    GnArgs& p = rt.p;
+    p.x = x; p.y = y; p.gamma = gamma; p.beta = beta; p.mean = mean; p.rstd = rstd; p.ws = (float*)ws;
+    p.ldx = ldx; p.ldy = ldy; p.eps = eps; p.silu = silu;
     hipStream_t s = (hipStream_t)stream;
-    const int threads = p.CC * p.PP, grid = B * p.NS;
-    const size_t lds1 = (size_t)p.PP * C * 2 * sizeof(float), lds2 = (size_t)G * 2 * sizeof(float);
-    ProfScope prof(PROF_GN, 2.0 * (double)B * HW * C * (double)(dtype == PSG_BF16 ? 2 : 4), s, 2.0 * (double)B * HW * C * (double)(dtype == PSG_BF16 ? 2 : 4));
-    {
-        GnF f = {};
-        f.x = x; f.y = y; f.gamma = gamma; f.beta = beta; f.mean = mean; f.rstd = rstd; f.ldx = ldx; f.ldy = ldy;
-        f.B = B; f.HW = HW; f.C = C; f.G = G; f.eps = eps; f.silu = silu;
-        // 256-lane workgroups first: four or more of them share a CU and their load / reduce / store phases interleave
-        // (measured: -9 % GroupNorm time against 512 lanes); 512 lanes where a 256-lane slab cannot hold whole groups
-        int R = gn_fused_plan(f, dtype == PSG_BF16 ? 8 : 4, 256, 16);
-        if (!R) R = gn_fused_plan(f, dtype == PSG_BF16 ? 8 : 4, 512, 16);
-        const size_t lds = ((size_t)f.PP * f.slabC + (f.CCs * f.PP > f.slabC ? f.CCs * f.PP : f.slabC) + f.slabC + 2 * f.SG) * sizeof(float);
-        if (R && lds <= 64 * 1024) {
-            const dim3 g(B * f.nslab), t(f.CCs * f.PP);
-#define PSG_GN_FWD(TT, NN, RR)                                                                     \
-    do { if (silu) hipLaunchKernelGGL((gn_fwd_fused_kernel<TT, NN, RR, true>), g, t, lds, s, f);  \
-         else hipLaunchKernelGGL((gn_fwd_fused_kernel<TT, NN, RR, false>), g, t, lds, s, f); } while (0)
-            if (dtype == PSG_F32) { if (R == 4) PSG_GN_FWD(float, 4, 4); else if (R == 8) PSG_GN_FWD(float, 4, 8); else PSG_GN_FWD(float, 4, 16); }
-            else { if (R == 4) PSG_GN_FWD(bf16_t, 8, 4); else if (R == 8) PSG_GN_FWD(bf16_t, 8, 8); else PSG_GN_FWD(bf16_t, 8, 16); }
-#undef PSG_GN_FWD
-            PSG_LAUNCH_CHECK("groupnorm_fwd_fused");
-            return PSG_OK;
-        }
-    }
-    if (dtype == PSG_F32) {
-        hipLaunchKernelGGL(gn_stats_kernel<float>, dim3(grid), dim3(threads), lds1, s, p);
-        hipLaunchKernelGGL(gn_apply_kernel<float>, dim3(grid), dim3(threads), lds2, s, p);
-    } else {
-        hipLaunchKernelGGL(gn_stats_kernel<bf16_t>, dim3(grid), dim3(threads), lds1, s, p);
-        hipLaunchKernelGGL(gn_apply_kernel<bf16_t>, dim3(grid), dim3(threads), lds2, s, p);
-    }
-    PSG_LAUNCH_CHECK("groupnorm_fwd");
+    const dim3 g(rt.grid), t(rt.threads);
+    const double bytes = 2.0 * (double)B * HW * C * (double)(16 / N);
+    ProfScope prof(PROF_GN, bytes, s, bytes);
+    with_dtype(dtype, [&](auto elem) {
+        using T = decltype(elem);
+        if (!rt.fused) {
+            hipLaunchKernelGGL(gn_stats_kernel<T>, g, t, rt.lds, s, p);
+            hipLaunchKernelGGL(gn_apply_kernel<T>, g, t, rt.lds2, s, p);
+        } else with_const(GnFwdRs{}, rt.R, [&](auto r) { with_const(Bools{}, silu, [&](auto sl) {
+            hipLaunchKernelGGL((gn_fwd_fused_kernel<T, Vec<T>::N, decltype(r)::value, decltype(sl)::value>), g, t, rt.lds, s, p);
+        }); });
+    });
+    PSG_LAUNCH_CHECK(rt.fused ? "groupnorm_fwd_fused" : "groupnorm_fwd");
     return PSG_OK;
 }
 
@@ -737,73 +803,35 @@ int psg_groupnorm_bwd_res(const void* dy, int64_t lddy, const void* x, int64_t l
                           psg_stream_t stream) {
     PSG_REQUIRE(dy && x && gamma && beta && mean && rstd && dx && dgamma && dbeta && ws, PSG_ERR_ARG, "groupnorm_bwd: null pointer");
     PSG_REQUIRE(dtype == PSG_F32 || dtype == PSG_BF16, PSG_ERR_DTYPE, "groupnorm_bwd: dtype %d", dtype);
-    GnP p = {};
-    p.x = x; p.dy = dy; p.dx = dx; p.gamma = gamma; p.beta = beta; p.mean = const_cast<float*>(mean); p.rstd = const_cast<float*>(rstd);
-    p.ws = (float*)ws; p.ldx = ldx; p.lddy = lddy; p.lddx = lddx; p.B = B; p.HW = HW; p.C = C; p.G = G; p.silu = silu;
-    p.dres = dres; p.lddres = lddres;
-    int rc = gn_plan(p, dtype);
-    if (rc) return rc;
-    const int N = dtype == PSG_BF16 ? 8 : 4;
+    const int N = dtype == PSG_BF16 ? 8 : 4;      // elements per 16-byte chunk
+    { const int rc = gn_check_shape(N, B, HW, C, G); if (rc) return rc; }
     PSG_REQUIRE(ldx >= C && lddy >= C && lddx >= C && ldx % N == 0 && lddy % N == 0 && lddx % N == 0 && aligned16(x) && aligned16(dy) &&
                 aligned16(dx), PSG_ERR_ALIGN, "groupnorm_bwd: rows must be 16-byte aligned (ld multiple of %d)", N);
     PSG_REQUIRE(!dres || (lddres >= C && lddres % N == 0 && aligned16(dres)), PSG_ERR_ALIGN, "groupnorm_bwd: dres rows must be 16-byte aligned");
+    GnRoute rt = gn_route_bwd(dtype, B, HW, C, G, dres != nullptr);
+    GnArgs& p = rt.p;
+    p.x = x; p.dy = dy; p.dres = dres; p.dx = dx; p.gamma = gamma; p.beta = beta; p.mean = const_cast<float*>(mean);
+    p.rstd = const_cast<float*>(rstd); p.ws = (float*)ws; p.ldx = ldx; p.lddy = lddy; p.lddres = lddres; p.lddx = lddx; p.silu = silu;
     hipStream_t s = (hipStream_t)stream;
-    const int threads = p.CC * p.PP, grid = B * p.NS;
-    const size_t lds1 = (size_t)p.PP * C * 2 * sizeof(float), lds2 = ((size_t)C + G) * 2 * sizeof(float);
-    ProfScope prof(PROF_GN, (dres ? 4.0 : 3.0) * (double)B * HW * C * (double)(dtype == PSG_BF16 ? 2 : 4), s, (dres ? 4.0 : 3.0) * (double)B * HW * C * (double)(dtype == PSG_BF16 ? 2 : 4));
-    {
-        GnF f = {};
-        f.x = x; f.dy = dy; f.dres = dres; f.dx = dx; f.gamma = gamma; f.beta = beta; f.mean = const_cast<float*>(mean);
-        f.rstd = const_cast<float*>(rstd); f.chan_ws = (float*)ws; f.ldx = ldx; f.lddy = lddy; f.lddres = lddres; f.lddx = lddx;
-        f.B = B; f.HW = HW; f.C = C; f.G = G; f.silu = silu;
-        // 8-byte chunks, <= 8 per lane and tensor (16 fit the register file since the v_rcp forms - 120 VGPRs - and let the
-        // 27x27 slabs run in 256 lanes, but measured no faster: 640 vs 648 us over the U-Net's eight shapes)
-        int R = gn_fused_plan(f, dtype == PSG_BF16 ? 4 : 2, 256, 8);
-        if (!R) R = gn_fused_plan(f, dtype == PSG_BF16 ? 4 : 2, 512, 8);
-        // These kernels wait on memory (round 4, rocprofv3: 50 % of the wave cycles; the LDS pipe is active 1 % of them, so its
-        // bank conflicts do not matter) and their slab rows are narrower than a 128-byte line (27x27x320: 40-byte rows, 3.1 TB/s;
-        // 14x14x640: 80 bytes, 4.5).  16-byte chunks double the row a (lanes x chunks) budget covers: with the bypass gradient
-        // as a third input stream -8...-20 % per launch (27x27x640 303 -> 267 us, 14x14x1280 143 -> 122), without it +-0
-        // (14x14x640 +10 %): taken for the bypass form only.
-        int NN = dtype == PSG_BF16 ? 4 : 2;
-        {
-            static int wide = -1;                          // PSG_GN_BWD_WIDE=0: 8-byte chunks only (A/B)
-            if (wide < 0) { const char* e = getenv("PSG_GN_BWD_WIDE"); wide = (e && atoi(e) == 0) ? 0 : 1; }
-            if (wide && dres && dtype == PSG_BF16 && R && f.slabC * 2 < 128) {
-                GnF f2 = f;
-                int R2 = gn_fused_plan(f2, 8, 256, 8);
-                if (!R2 || f2.slabC <= f.slabC) { f2 = f; R2 = gn_fused_plan(f2, 8, 512, 8); }
-                if (R2 && f2.slabC > f.slabC) { f = f2; R = R2; NN = 8; }
-            }
-        }
-        const size_t lds = ((size_t)f.PP * f.slabC * 2 + 2 * (f.CCs * f.PP > f.slabC ? f.CCs * f.PP : f.slabC) + 4 * f.slabC + 4 * f.SG) * sizeof(float);
-        if (R && lds <= 64 * 1024) {
-            const dim3 g(B * f.nslab), t(f.CCs * f.PP);
-#define PSG_GN_BWD(TT, NN, RR)                                                                                  \
-    do { if (silu && dres) hipLaunchKernelGGL((gn_bwd_fused_kernel<TT, NN, RR, true, true>), g, t, lds, s, f);  \
-         else if (silu) hipLaunchKernelGGL((gn_bwd_fused_kernel<TT, NN, RR, true, false>), g, t, lds, s, f);    \
-         else if (dres) hipLaunchKernelGGL((gn_bwd_fused_kernel<TT, NN, RR, false, true>), g, t, lds, s, f);    \
-         else hipLaunchKernelGGL((gn_bwd_fused_kernel<TT, NN, RR, false, false>), g, t, lds, s, f); } while (0)
-            if (dtype == PSG_F32) { if (R == 4) PSG_GN_BWD(float, 2, 4); else PSG_GN_BWD(float, 2, 8); }
-            else if (NN == 8) { if (R == 4) PSG_GN_BWD(bf16_t, 8, 4); else PSG_GN_BWD(bf16_t, 8, 8); }
-            else { if (R == 4) PSG_GN_BWD(bf16_t, 4, 4); else PSG_GN_BWD(bf16_t, 4, 8); }
-#undef PSG_GN_BWD
-            PSG_LAUNCH_CHECK("groupnorm_bwd_fused");
-            hipLaunchKernelGGL(gn_param_reduce_kernel, dim3((C + 31) / 32), dim3(1024), 0, s, (const float*)ws, dgamma, dbeta, B, C, accumulate);
-            PSG_LAUNCH_CHECK("groupnorm_param_reduce");
-            return PSG_OK;
-        }
-    }
-    if (dtype == PSG_F32) {
-        hipLaunchKernelGGL(gn_bwd_reduce_kernel<float>, dim3(grid), dim3(threads), lds1, s, p);
-        hipLaunchKernelGGL(gn_bwd_apply_kernel<float>, dim3(grid), dim3(threads), lds2, s, p);
-    } else {
-        hipLaunchKernelGGL(gn_bwd_reduce_kernel<bf16_t>, dim3(grid), dim3(threads), lds1, s, p);
-        hipLaunchKernelGGL(gn_bwd_apply_kernel<bf16_t>, dim3(grid), dim3(threads), lds2, s, p);
-    }
-    PSG_LAUNCH_CHECK("groupnorm_bwd");
-    hipLaunchKernelGGL(gn_param_reduce_kernel, dim3((C + 31) / 32), dim3(1024), 0, s, (const float*)ws + (int64_t)B * p.NS * C * 2, dgamma, dbeta,
-                       B, C, accumulate);
+    const dim3 g(rt.grid), t(rt.threads);
+    const double bytes = (dres ? 4.0 : 3.0) * (double)B * HW * C * (double)(16 / N);
+    ProfScope prof(PROF_GN, bytes, s, bytes);
+    with_dtype(dtype, [&](auto elem) {
+        using T = decltype(elem);
+        if (!rt.fused) {
+            hipLaunchKernelGGL(gn_bwd_reduce_kernel<T>, g, t, rt.lds, s, p);
+            hipLaunchKernelGGL(gn_bwd_apply_kernel<T>, g, t, rt.lds2, s, p);
+        } else with_const(typename GnBwdNs<T>::list{}, rt.N, [&](auto n) { with_const(GnBwdRs{}, rt.R, [&](auto r) {
+            with_const(Bools{}, silu, [&](auto sl) { with_const(Bools{}, dres != nullptr, [&](auto res) {
+                hipLaunchKernelGGL((gn_bwd_fused_kernel<T, decltype(n)::value, decltype(r)::value, decltype(sl)::value, decltype(res)::value>),
+                                   g, t, rt.lds, s, p);
+            }); });
+        }); });
+    });
+    PSG_LAUNCH_CHECK(rt.fused ? "groupnorm_bwd_fused" : "groupnorm_bwd");
+    // dgamma / dbeta over the per-sample channel sums: B rows at the start of ws (fused) or behind the split partials
+    const float* rows = (const float*)ws + (rt.fused ? 0 : (int64_t)B * p.NS * C * 2);
+    hipLaunchKernelGGL(gn_param_reduce_kernel, dim3((C + 31) / 32), dim3(1024), 0, s, rows, dgamma, dbeta, B, C, accumulate);
     PSG_LAUNCH_CHECK("groupnorm_param_reduce");
     return PSG_OK;
 }

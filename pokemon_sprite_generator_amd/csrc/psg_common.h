@@ -7,6 +7,7 @@
 #include <math.h>
 #include <stdlib.h>
 #include <initializer_list>
+#include <utility>
 
 #include "../../include/psg_hip.h"
 
@@ -64,6 +65,23 @@ static inline int set_max_lds(int lds, K*... kernels) {
     for (const void* k : {reinterpret_cast<const void*>(kernels)...})
         PSG_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     return PSG_OK;
+}
+
+// ---- run-time value -> compile-time constant ----------------------------------
+// with_const(list, v, f): f(std::integral_constant<T, V>{}) for the V of the declared list that equals v; false (and no
+// call) when v is not in the list.  The list is the one place that says which variants of a kernel exist.
+template <typename T, T... Vs, typename F>
+inline bool with_const(std::integer_sequence<T, Vs...>, typename std::integer_sequence<T, Vs...>::value_type v, F&& f) {
+    return ((v == Vs && (f(std::integral_constant<T, Vs>{}), true)) || ...);
+}
+using Bools = std::integer_sequence<bool, false, true>;
+// with_dtype(dtype, f): f(T{}) - a zero of the element type - for T = float (PSG_F32) or bf16_t (PSG_BF16); false otherwise
+template <typename F>
+inline bool with_dtype(int dtype, F&& f) {
+    if (dtype == PSG_F32) f(float{});
+    else if (dtype == PSG_BF16) f(bf16_t{});
+    else return false;
+    return true;
 }
 
 // ---- element access -------------------------------------------------------

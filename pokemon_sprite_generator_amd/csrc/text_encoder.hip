@@ -138,58 +138,7 @@ __global__ __launch_bounds__(64 * LN_ROWS) void embed_ln_kernel(const int64_t* _
     ln_store<CPL, TO>(v, lane, nch, N, gamma, beta, eps, yrow);
 }
 
-template <typename TI, typename TO, int CPL>
-static void launch_ln(const void* x, int64_t ldx, const void* r, int64_t ldr, void* y, int64_t ldy, const float* gamma,
-                      const float* beta, int64_t rows, int N, float eps, hipStream_t s) {
-    const dim3 grid((unsigned)((rows + LN_ROWS - 1) / LN_ROWS)), block(64 * LN_ROWS);
-    if (r)
-        hipLaunchKernelGGL((layernorm_kernel<TI, TO, CPL, true>), grid, block, 0, s, (const TI*)x, ldx, (const TI*)r, ldr, (TO*)y, ldy,
-                           gamma, beta, rows, N, eps);
-    else
-        hipLaunchKernelGGL((layernorm_kernel<TI, TO, CPL, false>), grid, block, 0, s, (const TI*)x, ldx, (const TI*)nullptr, (int64_t)0,
-                           (TO*)y, ldy, gamma, beta, rows, N, eps);
-}
-
-template <typename TI, typename TO>
-static void ln_dispatch(int cpl, const void* x, int64_t ldx, const void* r, int64_t ldr, void* y, int64_t ldy, const float* gamma,
-                        const float* beta, int64_t rows, int N, float eps, hipStream_t s) {
-    switch (cpl) {
-        case 1: launch_ln<TI, TO, 1>(x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s); break;
-        case 2: launch_ln<TI, TO, 2>(x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s); break;
-        case 3: launch_ln<TI, TO, 3>(x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s); break;
-        case 4: launch_ln<TI, TO, 4>(x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s); break;
-        case 5: launch_ln<TI, TO, 5>(x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s); break;
-        case 6: launch_ln<TI, TO, 6>(x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s); break;
-        case 7: launch_ln<TI, TO, 7>(x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s); break;
-        default: launch_ln<TI, TO, 8>(x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s); break;
-    }
-}
-
-template <typename TO, int CPL>
-static void launch_embed(const int64_t* ids, const int64_t* type_ids, const float* wemb, const float* pemb, const float* temb,
-                         const float* gamma, const float* beta, void* y, int64_t ldy, int64_t rows, int S, int N, int vocab,
-                         int type_vocab, float eps, hipStream_t s) {
-    hipLaunchKernelGGL((embed_ln_kernel<TO, CPL>), dim3((unsigned)((rows + LN_ROWS - 1) / LN_ROWS)), dim3(64 * LN_ROWS), 0, s, ids,
-                       type_ids, wemb, pemb, temb, gamma, beta, (TO*)y, ldy, rows, S, N, vocab, type_vocab, eps);
-}
-
-template <typename TO>
-static void embed_dispatch(int cpl, const int64_t* ids, const int64_t* type_ids, const float* wemb, const float* pemb,
-                           const float* temb, const float* gamma, const float* beta, void* y, int64_t ldy, int64_t rows, int S,
-                           int N, int vocab, int type_vocab, float eps, hipStream_t s) {
-#define PSG_EMBED_CASE(C) launch_embed<TO, C>(ids, type_ids, wemb, pemb, temb, gamma, beta, y, ldy, rows, S, N, vocab, type_vocab, eps, s)
-    switch (cpl) {
-        case 1: PSG_EMBED_CASE(1); break;
-        case 2: PSG_EMBED_CASE(2); break;
-        case 3: PSG_EMBED_CASE(3); break;
-        case 4: PSG_EMBED_CASE(4); break;
-        case 5: PSG_EMBED_CASE(5); break;
-        case 6: PSG_EMBED_CASE(6); break;
-        case 7: PSG_EMBED_CASE(7); break;
-        default: PSG_EMBED_CASE(8); break;
-    }
-#undef PSG_EMBED_CASE
-}
+using LnCpls = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8>;      // 16-byte chunks per lane: every N row_width_check admits
 
 static int row_width_check(const char* who, int N) {
     PSG_REQUIRE(N >= 8 && N <= LN_MAXN && N % 8 == 0, PSG_ERR_SHAPE, "%s: row width N=%d must be a multiple of 8 in [8, %d]", who, N, LN_MAXN);
@@ -214,13 +163,13 @@ int psg_layernorm(const void* x, int64_t ldx, const void* r, int64_t ldr, void* 
                 aligned16(beta), PSG_ERR_ALIGN, "layernorm: rows must start on 16-byte boundaries (strides multiples of 8)");
     const int cpl = (N / 8 + 63) / 64;
     hipStream_t s = (hipStream_t)stream;
-    if (x_dtype == PSG_F32) {
-        if (y_dtype == PSG_F32) ln_dispatch<float, float>(cpl, x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s);
-        else ln_dispatch<float, bf16_t>(cpl, x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s);
-    } else {
-        if (y_dtype == PSG_F32) ln_dispatch<bf16_t, float>(cpl, x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s);
-        else ln_dispatch<bf16_t, bf16_t>(cpl, x, ldx, r, ldr, y, ldy, gamma, beta, rows, N, eps, s);
-    }
+    const dim3 grid((unsigned)((rows + LN_ROWS - 1) / LN_ROWS)), block(64 * LN_ROWS);
+    with_dtype(x_dtype, [&](auto ti) { with_dtype(y_dtype, [&](auto to) {
+    with_const(LnCpls{}, cpl, [&](auto c) { with_const(Bools{}, r != nullptr, [&](auto res) {
+        using TI = decltype(ti); using TO = decltype(to);
+        hipLaunchKernelGGL((layernorm_kernel<TI, TO, decltype(c)::value, decltype(res)::value>), grid, block, 0, s, (const TI*)x, ldx,
+                           (const TI*)r, r ? ldr : (int64_t)0, (TO*)y, ldy, gamma, beta, rows, N, eps);
+    }); }); }); });
     PSG_LAUNCH_CHECK("layernorm");
     return PSG_OK;
 }
@@ -240,8 +189,11 @@ int psg_bert_embed_ln(const int64_t* ids, const int64_t* type_ids, const float* 
     const int cpl = (N / 8 + 63) / 64;
     const int64_t rows = (int64_t)B * S;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == PSG_F32) embed_dispatch<float>(cpl, ids, type_ids, word_emb, pos_emb, type_emb, gamma, beta, y, ldy, rows, S, N, vocab, type_vocab, eps, s);
-    else embed_dispatch<bf16_t>(cpl, ids, type_ids, word_emb, pos_emb, type_emb, gamma, beta, y, ldy, rows, S, N, vocab, type_vocab, eps, s);
+    with_dtype(dtype, [&](auto to) { with_const(LnCpls{}, cpl, [&](auto c) {
+        using TO = decltype(to);
+        hipLaunchKernelGGL((embed_ln_kernel<TO, decltype(c)::value>), dim3((unsigned)((rows + LN_ROWS - 1) / LN_ROWS)), dim3(64 * LN_ROWS), 0, s, ids,
+                           type_ids, word_emb, pos_emb, type_emb, gamma, beta, (TO*)y, ldy, rows, S, N, vocab, type_vocab, eps);
+    }); });
     PSG_LAUNCH_CHECK("bert_embed_ln");
     return PSG_OK;
 }

@@ -184,7 +184,7 @@ def test_layout_pool_sinusoid(psg, dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("hi,ho", [(4, 7), (7, 14), (14, 27)])
+@pytest.mark.parametrize("hi,ho", [(4, 7), (7, 14), (14, 27), (7, 28)])
 def test_upsample(psg, dtype, hi, ho):
     from pokemon_sprite_generator_amd import ops
     x = _q(h((2, 64, hi, hi), f"up.x{hi}", 1.5), dtype).requires_grad_(True)
