@@ -318,6 +318,14 @@ int psg_attn_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const v
 int psg_attn_fwd_varlen(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                         void* o, int64_t ldo, float* lse, int B, int heads, int L, int S, int d, float scale,
                         float drop_p, uint64_t seed, int dtype, const int32_t* kv_len, psg_stream_t stream);
+/* Training forward with a key length per sample: psg_attn_fwd_varlen's masking (kv_len int32 [B] on the device, clamped to
+ * [1, S]; queries are not masked) with lse required and drop_p in [0, 1) drawing psg_attn_fwd's hash mask (same element
+ * index, so the mask of a key does not depend on kv_len).  The family is chosen as psg_attn_fwd chooses it (forward and
+ * backward kernels must fit LDS), so the pair with psg_attn_bwd_varlen stays on one family.  With kv_len[b] == S for every
+ * b the result is bit-identical to psg_attn_fwd. */
+int psg_attn_fwd_varlen_train(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                              void* o, int64_t ldo, float* lse, int B, int heads, int L, int S, int d, float scale,
+                              float drop_p, uint64_t seed, int dtype, const int32_t* kv_len, psg_stream_t stream);
 /* Diagnostic: launches of psg_attn_fwd / psg_attn_bwd served so far by the bf16 MFMA kernels (head_dim 16 / 32 / 64 / 80 /
  * 160 / 320, 16-byte aligned rows), by the VALU kernels (other shapes) and by the exact-fp32 MFMA kernels (fp32, head_dim
  * 16 / 32 / 64 / 80 / 160 while K/V - and Q/dO for backward - fit LDS).  All paths draw the same dropout mask. */
@@ -333,8 +341,20 @@ int psg_attn_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const v
                  int B, int heads, int L, int S, int d, float scale, float drop_p, uint64_t seed,
                  int dtype, psg_stream_t stream);
 
+/* psg_attn_bwd with psg_attn_fwd_varlen_train's key lengths: key tiles at or past kv_len[b] are neither staged nor
+ * computed, and dk / dv rows kv_len[b] <= s < S are written as zeros (a Linear's weight gradient sums over every row).
+ * Nothing stored in k or v past kv_len[b] can reach an output.  With kv_len[b] == S for every b: the bits of psg_attn_bwd.
+ * For a sample with kv_len[b] < S, delta is computed in fp32 as sum_s drop(P)[l,s] dP[l,s] from the recomputed
+ * probabilities rather than as rowsum(dO * O): few live keys concentrate P, dS = P (dP' - delta) then cancels (exactly at
+ * kv_len = 1), and the rounding of a bf16 O inside delta would otherwise be all that is left of dk. */
+int psg_attn_bwd_varlen(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                        const void* o, int64_t ldo, const void* dout, int64_t lddo, const float* lse,
+                        float* delta, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv,
+                        int B, int heads, int L, int S, int d, float scale, float drop_p, uint64_t seed,
+                        int dtype, const int32_t* kv_len, psg_stream_t stream);
+
 /* ---------------------------------------------------------------------------
- * Frozen BERT text encoder (src/models/text_encoder.py: transformers BertModel + projection + LayerNorm).
+ * BERT text encoder (src/models/text_encoder.py: transformers BertModel + projection + LayerNorm).
  * The GEMMs are psg_conv_fwd Linears, the attention is psg_attn_fwd_varlen; these are the row kernels.
  * Rows: 16-byte aligned starts (row strides multiples of 8 elements); gamma / beta / tables fp32.
  * ------------------------------------------------------------------------- */
@@ -343,6 +363,16 @@ int psg_attn_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const v
  * y_dtype (e.g. bf16 in, fp32 out for the encoder's final nn.LayerNorm). */
 int psg_layernorm(const void* x, int64_t ldx, const void* r, int64_t ldr, void* y, int64_t ldy, const float* gamma,
                   const float* beta, int64_t rows, int N, float eps, int x_dtype, int y_dtype, psg_stream_t stream);
+/* Backward of psg_layernorm.  x, r (may be NULL), N, eps: the forward's operands (the statistics are recomputed from them in
+ * the forward's reduction order, nothing else is saved); dy has dy_dtype.  dz (x_dtype) is the gradient of z = x + r - the
+ * one tensor serves both operands.  dgamma / dbeta: fp32 [N], either may be NULL; accumulate != 0 adds to what is there.
+ * They are summed without atomics in an order fixed by (rows, N): workgroup partials go through ws (16-byte aligned, at
+ * least psg_layernorm_bwd_workspace_bytes(rows, N) bytes - PSG_ERR_WORKSPACE otherwise; unused when both are NULL). */
+int psg_layernorm_bwd(const void* x, int64_t ldx, const void* r, int64_t ldr, const void* dy, int64_t lddy,
+                      const float* gamma, void* dz, int64_t lddz, float* dgamma, float* dbeta, int accumulate,
+                      int64_t rows, int N, float eps, int x_dtype, int dy_dtype, void* ws, int64_t ws_bytes,
+                      psg_stream_t stream);
+int64_t psg_layernorm_bwd_workspace_bytes(int64_t rows, int N);
 /* BertEmbeddings in eval mode: row b*S+s of y = LayerNorm(word_emb[ids] + type_emb[type_ids] + pos_emb[s]) (transformers'
  * summation order), y in `dtype`.  ids / type_ids: int64 [B*S] (type_ids NULL = all 0); tables fp32 row-major
  * [vocab|max_pos|type_vocab][N].  An id outside [0, vocab) or type id outside [0, type_vocab) reads nothing and yields a

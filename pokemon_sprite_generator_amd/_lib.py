@@ -95,12 +95,19 @@ SIGNATURES = {
                      + [c_int] * 5 + [c_float, c_float, c_uint64, c_int, c_void_p]),
     "psg_attn_fwd_varlen": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]
                             + [c_int] * 5 + [c_float, c_float, c_uint64, c_int, c_void_p, c_void_p]),
+    "psg_attn_fwd_varlen_train": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]
+                                  + [c_int] * 5 + [c_float, c_float, c_uint64, c_int, c_void_p, c_void_p]),
+    "psg_attn_bwd_varlen": (c_int, [c_void_p, c_int64] * 5 + [c_void_p, c_void_p] + [c_void_p, c_int64] * 3
+                            + [c_int] * 5 + [c_float, c_float, c_uint64, c_int, c_void_p, c_void_p]),
     "psg_attn_path_counts": (c_int, [c_void_p, c_void_p, c_void_p]),
     "psg_attn_set_paths": (c_int, [c_int]),
     "psg_attn_bwd": (c_int, [c_void_p, c_int64] * 5 + [c_void_p, c_void_p] + [c_void_p, c_int64] * 3
                      + [c_int] * 5 + [c_float, c_float, c_uint64, c_int, c_void_p]),
     "psg_layernorm": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_float,
                               c_int, c_int, c_void_p]),
+    "psg_layernorm_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                  c_int, c_int64, c_int, c_float, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "psg_layernorm_bwd_workspace_bytes": (c_int64, [c_int64, c_int]),
     "psg_bert_embed_ln": (c_int, [c_void_p] * 8 + [c_int64] + [c_int] * 6 + [c_float, c_int, c_void_p]),
     "psg_sumsq_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "psg_adamw_f32": (c_int, [c_void_p] * 4 + [c_int64] + [c_float] * 5 + [c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),

@@ -16,7 +16,7 @@ struct AttnArgs {
     float scale;
     uint32_t drop_thresh; float drop_scale; uint64_t seed;
     const uint64_t* seed_dev;
-    const int32_t* kv_len;     // psg_attn_fwd_varlen: keys s >= kv_len[b] of sample b are left out (NULL otherwise)
+    const int32_t* kv_len;     // the varlen entries: keys s >= kv_len[b] of sample b are left out (NULL otherwise)
 };
 
 // Head-dim list of an MFMA family: the kernels are instantiated for head_dim = 16 * ND, ND in NDs.  Calls
@@ -32,15 +32,16 @@ inline int for_each_nd(std::integer_sequence<int, NDs...>, F&& f) {
 }
 
 // whether the family's kernels take this problem: its head_dim and row strides, and the LDS fit of its forward kernel and,
-// unless forward_only (psg_attn_fwd_varlen), of its backward kernels
+// unless forward_only (psg_attn_fwd_varlen; the training pair psg_attn_fwd_varlen_train / psg_attn_bwd_varlen is not), of its
+// backward kernels
 bool attn_mfma_applicable(int L, int S, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, bool forward_only);
 int attn_mfma_init_attrs();
 template <bool VARLEN> int attn_mfma_fwd(const AttnArgs<bf16_t>& p, hipStream_t s);
-int attn_mfma_bwd(const AttnArgs<bf16_t>& p, hipStream_t s);
+template <bool VARLEN> int attn_mfma_bwd(const AttnArgs<bf16_t>& p, hipStream_t s);
 
 bool attn_f32_applicable(int L, int S, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, bool forward_only);
 int attn_f32_init_attrs();
 template <bool VARLEN> int attn_f32_fwd(const AttnArgs<float>& p, hipStream_t s);
-int attn_f32_bwd(const AttnArgs<float>& p, hipStream_t s);
+template <bool VARLEN> int attn_f32_bwd(const AttnArgs<float>& p, hipStream_t s);
 
 }  // namespace psg

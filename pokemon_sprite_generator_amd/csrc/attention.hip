@@ -138,8 +138,8 @@ __global__ void attn_delta_kernel(const AttnArgs<T> p) {
     if (lane == 0) p.delta[row] = a;
 }
 
-// dQ for a 16-query tile
-template <typename T>
+// dQ for a 16-query tile (VARLEN: over the keys below kv_len[b] only)
+template <typename T, bool VARLEN = false>
 __global__ __launch_bounds__(256) void attn_dq_kernel(const AttnArgs<T> p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int d = p.d, dp = d + 1;
@@ -157,6 +157,7 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const AttnArgs<T> p) {
     const T* gg = p.dout + (int64_t)b * p.L * p.lddo + h * d;
     T* dqg = p.dq + (int64_t)b * p.L * p.lddq + h * d;
     const int tid = threadIdx.x;
+    const int Se = key_end<VARLEN>(p.kv_len, b, p.S);
 
     stage_rows<T>(Qs, qg, p.ldq, l0, AT_Q, p.L, d, p.scale);
     stage_rows<T>(Gs, gg, p.lddo, l0, AT_Q, p.L, d, 1.0f);
@@ -164,12 +165,50 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const AttnArgs<T> p) {
     const int la = l0 + qa, lb = l0 + qb;
     const float lse_a = la < p.L ? p.lse[(int64_t)bh * p.L + la] : 0.f;
     const float lse_b = lb < p.L ? p.lse[(int64_t)bh * p.L + lb] : 0.f;
-    const float del_a = la < p.L ? p.delta[(int64_t)bh * p.L + la] : 0.f;
-    const float del_b = lb < p.L ? p.delta[(int64_t)bh * p.L + lb] : 0.f;
-    for (int s0 = 0; s0 < p.S; s0 += AT_KC) {
+    float del_a = la < p.L ? p.delta[(int64_t)bh * p.L + la] : 0.f;
+    float del_b = lb < p.L ? p.delta[(int64_t)bh * p.L + lb] : 0.f;
+    if (VARLEN && Se < p.S) {                      // (workgroup-uniform) a sample with masked keys: delta = sum_s drop(P) dP
+        // in fp32 from the recomputed probabilities instead of rowsum(dO O).  Few live keys concentrate P; dS = P (dP' - delta)
+        // then cancels (exactly, at kv_len = 1) and the rounding of O to the I/O dtype inside delta would be all that is left
+        // of dk.  Samples at full length keep psg_attn_bwd's delta (and its bits).  The dK/dV kernel reads what is stored here.
+        float part_a = 0.f, part_b = 0.f;
+        for (int s0 = 0; s0 < Se; s0 += AT_KC) {
+            __syncthreads();
+            stage_rows<T>(Ks, kg, p.ldk, s0, AT_KC, Se, d, 1.0f);
+            stage_rows<T>(Vs, vg, p.ldv, s0, AT_KC, Se, d, 1.0f);
+            __syncthreads();
+            const float* kr = Ks + kj * dp; const float* vr = Vs + kj * dp;
+            const float* q0 = Qs + qa * dp; const float* q1 = Qs + qb * dp;
+            const float* g0 = Gs + qa * dp; const float* g1 = Gs + qb * dp;
+            float s_a = 0.f, s_b = 0.f, dp_a = 0.f, dp_b = 0.f;
+            for (int e = 0; e < d; ++e) {
+                const float kv = kr[e], vv = vr[e];
+                s_a += q0[e] * kv; s_b += q1[e] * kv;
+                dp_a += g0[e] * vv; dp_b += g1[e] * vv;
+            }
+            const int s = s0 + kj;
+            if (s < Se) {
+                if (p.drop_thresh) {
+                    dp_a = (la < p.L && drop_keep(eff_seed(p.seed, p.seed_dev), attn_idx(p, bh, la, s), p.drop_thresh)) ? dp_a * p.drop_scale : 0.f;
+                    dp_b = (lb < p.L && drop_keep(eff_seed(p.seed, p.seed_dev), attn_idx(p, bh, lb, s), p.drop_thresh)) ? dp_b * p.drop_scale : 0.f;
+                }
+                part_a += __expf(s_a - lse_a) * dp_a;
+                part_b += __expf(s_b - lse_b) * dp_b;
+            }
+        }
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) { part_a += __shfl_xor(part_a, o, 64); part_b += __shfl_xor(part_b, o, 64); }   // the 32 key lanes of a query
+        del_a = la < p.L ? part_a : 0.f;
+        del_b = lb < p.L ? part_b : 0.f;
+        if (kj == 0) {
+            if (la < p.L) p.delta[(int64_t)bh * p.L + la] = del_a;
+            if (lb < p.L) p.delta[(int64_t)bh * p.L + lb] = del_b;
+        }
+    }
+    for (int s0 = 0; s0 < Se; s0 += AT_KC) {
         __syncthreads();
-        stage_rows<T>(Ks, kg, p.ldk, s0, AT_KC, p.S, d, 1.0f);
-        stage_rows<T>(Vs, vg, p.ldv, s0, AT_KC, p.S, d, 1.0f);
+        stage_rows<T>(Ks, kg, p.ldk, s0, AT_KC, Se, d, 1.0f);
+        stage_rows<T>(Vs, vg, p.ldv, s0, AT_KC, Se, d, 1.0f);
         __syncthreads();
         const float* kr = Ks + kj * dp; const float* vr = Vs + kj * dp;
         const float* q0 = Qs + qa * dp; const float* q1 = Qs + qb * dp;
@@ -181,7 +220,7 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const AttnArgs<T> p) {
             dp_a += g0[e] * vv; dp_b += g1[e] * vv;
         }
         const int s = s0 + kj;
-        if (s < p.S) {
+        if (s < Se) {
             float pa = __expf(s_a - lse_a), pb = __expf(s_b - lse_b);
             if (p.drop_thresh) {
                 dp_a = (la < p.L && drop_keep(eff_seed(p.seed, p.seed_dev), attn_idx(p, bh, la, s), p.drop_thresh)) ? dp_a * p.drop_scale : 0.f;
@@ -197,11 +236,11 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const AttnArgs<T> p) {
     float acc[AT_MAXC];
 #pragma unroll
     for (int c = 0; c < AT_MAXC; ++c) acc[c] = 0.f;
-    for (int s0 = 0; s0 < p.S; s0 += AT_KC) {
+    for (int s0 = 0; s0 < Se; s0 += AT_KC) {
         __syncthreads();
-        stage_rows<T>(Ks, kg, p.ldk, s0, AT_KC, p.S, d, 1.0f);
+        stage_rows<T>(Ks, kg, p.ldk, s0, AT_KC, Se, d, 1.0f);
         __syncthreads();
-        const int jn = min(AT_KC, p.S - s0);
+        const int jn = min(AT_KC, Se - s0);
         for (int j = 0; j < jn; ++j) {
             const float ds = Ss[qi * Sp + s0 + j];
             const float* kr = Ks + j * dp + dd0;
@@ -217,8 +256,9 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const AttnArgs<T> p) {
     }
 }
 
-// dK, dV for a 16-key tile: loops over all queries in chunks of 32
-template <typename T>
+// dK, dV for a 16-key tile: loops over all queries in chunks of 32 (VARLEN: rows s >= kv_len[b] are written as zeros, and
+// K / V rows past the bound are never read)
+template <typename T, bool VARLEN = false>
 __global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnArgs<T> p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int d = p.d, dp = d + 1;
@@ -237,11 +277,23 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnArgs<T> p) {
     T* dkg = p.dk + (int64_t)b * p.S * p.lddk + h * d;
     T* dvg = p.dv + (int64_t)b * p.S * p.lddv + h * d;
     const int tid = threadIdx.x;
-    stage_rows<T>(Ks, kg, p.ldk, s0, AT_Q, p.S, d, 1.0f);
-    stage_rows<T>(Vs, vg, p.ldv, s0, AT_Q, p.S, d, 1.0f);
-
+    const int Se = key_end<VARLEN>(p.kv_len, b, p.S);
     const int kj = tid >> 4, dd0 = tid & 15;       // accumulate phase mapping
     const int nc = (d + 15) >> 4;
+    if (VARLEN && s0 >= Se) {                      // (workgroup-uniform) a tile of padded keys
+        if (s0 + kj < p.S) {
+#pragma unroll
+            for (int c = 0; c < AT_MAXC; ++c)
+                if (c < nc && dd0 + 16 * c < d) {
+                    Elem<T>::st(dkg + (int64_t)(s0 + kj) * p.lddk + dd0 + 16 * c, 0.f);
+                    Elem<T>::st(dvg + (int64_t)(s0 + kj) * p.lddv + dd0 + 16 * c, 0.f);
+                }
+        }
+        return;
+    }
+    stage_rows<T>(Ks, kg, p.ldk, s0, AT_Q, Se, d, 1.0f);
+    stage_rows<T>(Vs, vg, p.ldv, s0, AT_Q, Se, d, 1.0f);
+
     float accK[AT_MAXC], accV[AT_MAXC];
 #pragma unroll
     for (int c = 0; c < AT_MAXC; ++c) { accK[c] = 0.f; accV[c] = 0.f; }
@@ -267,7 +319,7 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnArgs<T> p) {
             if (l < p.L) {
                 const float lse = p.lse[(int64_t)bh * p.L + l], del = p.delta[(int64_t)bh * p.L + l];
                 const int sa = s0 + ka, sb = s0 + kb;
-                if (sa < p.S) {
+                if (sa < Se) {
                     float pr = __expf(s_a - lse), pd = pr;
                     if (p.drop_thresh) {
                         const bool keep = drop_keep(eff_seed(p.seed, p.seed_dev), attn_idx(p, bh, l, sa), p.drop_thresh);
@@ -275,7 +327,7 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnArgs<T> p) {
                     }
                     pa = pd; da = pr * (dp_a - del);
                 }
-                if (sb < p.S) {
+                if (sb < Se) {
                     float pr = __expf(s_b - lse), pd = pr;
                     if (p.drop_thresh) {
                         const bool keep = drop_keep(eff_seed(p.seed, p.seed_dev), attn_idx(p, bh, l, sb), p.drop_thresh);
@@ -299,11 +351,12 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnArgs<T> p) {
         }
     }
     if (s0 + kj < p.S) {
+        const bool pad = VARLEN && s0 + kj >= Se;
 #pragma unroll
         for (int c = 0; c < AT_MAXC; ++c)
             if (c < nc && dd0 + 16 * c < d) {
-                Elem<T>::st(dkg + (int64_t)(s0 + kj) * p.lddk + dd0 + 16 * c, accK[c]);   // Qs already carries `scale`
-                Elem<T>::st(dvg + (int64_t)(s0 + kj) * p.lddv + dd0 + 16 * c, accV[c]);
+                Elem<T>::st(dkg + (int64_t)(s0 + kj) * p.lddk + dd0 + 16 * c, pad ? 0.f : accK[c]);   // Qs already carries `scale`
+                Elem<T>::st(dvg + (int64_t)(s0 + kj) * p.lddv + dd0 + 16 * c, pad ? 0.f : accV[c]);
             }
     }
 }
@@ -326,7 +379,8 @@ static int attn_check(const char* who, int B, int heads, int L, int S, int d, in
 // the VALU kernels of element type T (attention_mfma.hip / attention_f32.hip raise their own)
 template <typename T>
 static int valu_init_attrs() {
-    return set_max_lds(150 * 1024, attn_fwd_kernel<T, false>, attn_fwd_kernel<T, true>, attn_dq_kernel<T>, attn_dkv_kernel<T>);
+    return set_max_lds(150 * 1024, attn_fwd_kernel<T, false>, attn_fwd_kernel<T, true>, attn_dq_kernel<T, false>, attn_dq_kernel<T, true>,
+                       attn_dkv_kernel<T, false>, attn_dkv_kernel<T, true>);
 }
 
 static int64_t g_attn_paths[3] = {0, 0, 0};         // launches taken by the bf16 MFMA / the VALU / the fp32 MFMA kernels
@@ -337,14 +391,16 @@ static int f32_mfma_on() {
 }
 static int g_attn_allow = 3;                         // psg_attn_set_paths: bit 0 bf16 MFMA, bit 1 exact-fp32 MFMA
 
-enum AttnPass { ATTN_FWD, ATTN_FWD_VARLEN, ATTN_BWD };
+enum AttnPass { ATTN_FWD, ATTN_FWD_VARLEN, ATTN_BWD, ATTN_FWD_VARLEN_TRAIN, ATTN_BWD_VARLEN };
 
 // The kernel family of one call - the bf16 MFMA kernels, the exact-fp32 MFMA kernels or the VALU kernels - counted in
-// g_attn_paths.  A plain forward and a backward take an MFMA family where both its forward and its backward kernels fit
-// LDS; a varlen forward where its forward kernel does.
+// g_attn_paths.  A forward that a backward may follow (plain or varlen_train) and a backward take an MFMA family where both
+// its forward and its backward kernels fit LDS, so a training pair stays on one family; the forward-only varlen entry where
+// its forward kernel does.
 template <typename T>
 static int attn_route(AttnPass pass, const AttnArgs<T>& p, hipStream_t s) {
-    const bool bwd = pass == ATTN_BWD, varlen = pass == ATTN_FWD_VARLEN;
+    const bool bwd = pass == ATTN_BWD || pass == ATTN_BWD_VARLEN, varlen = pass != ATTN_FWD && pass != ATTN_BWD;
+    const bool fwd_only = pass == ATTN_FWD_VARLEN;
     // (varlen: the FLOP count is the padded problem's, the key lengths live on the device)
     ProfScope prof(PROF_ATTN, (bwd ? 10.0 : 4.0) * (double)p.B * p.H * p.L * p.S * p.d, s,
                    (double)p.B * p.H * p.d * (bwd ? 4.0 * p.L + 4.0 * p.S : 2.0 * p.L + 2.0 * p.S) * (double)sizeof(T));
@@ -353,16 +409,16 @@ static int attn_route(AttnPass pass, const AttnArgs<T>& p, hipStream_t s) {
     if constexpr (std::is_same<T, bf16_t>::value) {
         const bool out_ok = bwd ? (ldg & 7) == 0 && aligned16(p.o) && aligned16(p.dout) && aligned8(p.dq) && aligned8(p.dk) && aligned8(p.dv)
                                 : aligned8(p.out);
-        if ((g_attn_allow & 1) && attn_mfma_applicable(p.L, p.S, p.d, p.ldq, p.ldk, p.ldv, p.ldo, varlen) && in16 && out_ok) {
+        if ((g_attn_allow & 1) && attn_mfma_applicable(p.L, p.S, p.d, p.ldq, p.ldk, p.ldv, p.ldo, fwd_only) && in16 && out_ok) {
             ++g_attn_paths[0];
-            return bwd ? attn_mfma_bwd(p, s) : varlen ? attn_mfma_fwd<true>(p, s) : attn_mfma_fwd<false>(p, s);
+            return bwd ? (varlen ? attn_mfma_bwd<true>(p, s) : attn_mfma_bwd<false>(p, s)) : varlen ? attn_mfma_fwd<true>(p, s) : attn_mfma_fwd<false>(p, s);
         }
     } else {
         const bool out_ok = bwd ? (ldg & 3) == 0 && aligned16(p.o) && aligned16(p.dout) && aligned16(p.dq) && aligned16(p.dk) && aligned16(p.dv)
                                 : aligned16(p.out);
-        if ((g_attn_allow & 2) && f32_mfma_on() && attn_f32_applicable(p.L, p.S, p.d, p.ldq, p.ldk, p.ldv, p.ldo, varlen) && in16 && out_ok) {
+        if ((g_attn_allow & 2) && f32_mfma_on() && attn_f32_applicable(p.L, p.S, p.d, p.ldq, p.ldk, p.ldv, p.ldo, fwd_only) && in16 && out_ok) {
             ++g_attn_paths[2];
-            return bwd ? attn_f32_bwd(p, s) : varlen ? attn_f32_fwd<true>(p, s) : attn_f32_fwd<false>(p, s);
+            return bwd ? (varlen ? attn_f32_bwd<true>(p, s) : attn_f32_bwd<false>(p, s)) : varlen ? attn_f32_fwd<true>(p, s) : attn_f32_fwd<false>(p, s);
         }
     }
     ++g_attn_paths[1];
@@ -370,8 +426,14 @@ static int attn_route(AttnPass pass, const AttnArgs<T>& p, hipStream_t s) {
     if (bwd) {
         const int64_t rows = (int64_t)p.B * p.H * p.L;
         hipLaunchKernelGGL(attn_delta_kernel<T>, dim3((int)((rows + 3) / 4)), dim3(256), 0, s, p);
-        hipLaunchKernelGGL(attn_dq_kernel<T>, grid, dim3(256), dq_lds(p.S, p.d), s, p);
-        hipLaunchKernelGGL(attn_dkv_kernel<T>, dim3((p.S + AT_Q - 1) / AT_Q, p.B * p.H), dim3(256), dkv_lds(p.d), s, p);
+        const dim3 kgrid((p.S + AT_Q - 1) / AT_Q, p.B * p.H);
+        if (varlen) {
+            hipLaunchKernelGGL((attn_dq_kernel<T, true>), grid, dim3(256), dq_lds(p.S, p.d), s, p);
+            hipLaunchKernelGGL((attn_dkv_kernel<T, true>), kgrid, dim3(256), dkv_lds(p.d), s, p);
+        } else {
+            hipLaunchKernelGGL((attn_dq_kernel<T, false>), grid, dim3(256), dq_lds(p.S, p.d), s, p);
+            hipLaunchKernelGGL((attn_dkv_kernel<T, false>), kgrid, dim3(256), dkv_lds(p.d), s, p);
+        }
         PSG_LAUNCH_CHECK("attn_bwd");
     } else if (varlen) {
         hipLaunchKernelGGL((attn_fwd_kernel<T, true>), grid, dim3(256), fwd_lds(p.S, p.d), s, p);
@@ -386,6 +448,30 @@ static int attn_route(AttnPass pass, const AttnArgs<T>& p, hipStream_t s) {
 // f((T*)nullptr) for the element type T of dtype (PSG_F32 or PSG_BF16: attn_check has accepted it)
 template <typename F>
 static int with_elem(int dtype, F&& f) { return dtype == PSG_BF16 ? f((bf16_t*)nullptr) : f((float*)nullptr); }
+
+static int attn_bwd_entry(const char* who, const int32_t* kv_len, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o,
+                 int64_t ldo, const void* dout, int64_t lddo, const float* lse, float* delta, void* dq, int64_t lddq,
+                 void* dk, int64_t lddk, void* dv, int64_t lddv, int B, int heads, int L, int S, int d, float scale,
+                 float drop_p, uint64_t seed, int dtype, psg_stream_t stream) {
+    PSG_REQUIRE(q && k && v && o && dout && lse && delta && dq && dk && dv, PSG_ERR_ARG, "%s: null pointer", who);
+    int rc = attn_check(who, B, heads, L, S, d, dtype, ldq, ldk, ldv, ldo);
+    if (rc) return rc;
+    PSG_REQUIRE(lddo >= heads * d && lddq >= heads * d && lddk >= heads * d && lddv >= heads * d && ((lddo | lddq | lddk | lddv) & 3) == 0,
+                PSG_ERR_SHAPE, "%s: gradient row strides", who);
+    PSG_REQUIRE(drop_p >= 0.f && drop_p < 1.f, PSG_ERR_ARG, "%s: drop_p", who);
+    const size_t l1 = dq_lds(S, d), l2 = dkv_lds(d);
+    PSG_REQUIRE(l1 <= 150 * 1024 && l2 <= 150 * 1024, PSG_ERR_SHAPE, "%s: LDS need too large", who);
+    return with_elem(dtype, [&](auto* tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        AttnArgs<T> p = {};
+        p.q = (const T*)q; p.k = (const T*)k; p.v = (const T*)v; p.o = (const T*)o; p.dout = (const T*)dout; p.lse = const_cast<float*>(lse); p.delta = delta;
+        p.dq = (T*)dq; p.dk = (T*)dk; p.dv = (T*)dv;
+        p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
+        p.B = B; p.H = heads; p.L = L; p.S = S; p.d = d; p.scale = scale;
+        p.drop_thresh = drop_p > 0.f ? drop_thresh(drop_p) : 0u; p.drop_scale = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f; p.seed = seed; p.seed_dev = seed_source(); p.kv_len = kv_len;
+        return attn_route(kv_len ? ATTN_BWD_VARLEN : ATTN_BWD, p, (hipStream_t)stream);
+    });
+}
 
 }  // namespace psg
 using namespace psg;
@@ -445,28 +531,41 @@ int psg_attn_fwd_varlen(const void* q, int64_t ldq, const void* k, int64_t ldk, 
     });
 }
 
+int psg_attn_fwd_varlen_train(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o,
+                              int64_t ldo, float* lse, int B, int heads, int L, int S, int d, float scale, float drop_p, uint64_t seed,
+                              int dtype, const int32_t* kv_len, psg_stream_t stream) {
+    PSG_REQUIRE(q && k && v && o && lse && kv_len, PSG_ERR_ARG, "attn_fwd_varlen_train: null pointer");
+    int rc = attn_check("attn_fwd_varlen_train", B, heads, L, S, d, dtype, ldq, ldk, ldv, ldo);
+    if (rc) return rc;
+    PSG_REQUIRE(drop_p >= 0.f && drop_p < 1.f, PSG_ERR_ARG, "attn_fwd_varlen_train: drop_p");
+    const size_t lds = fwd_lds(S, d);
+    PSG_REQUIRE(lds <= 150 * 1024, PSG_ERR_SHAPE, "attn_fwd_varlen_train: LDS need %zu too large", lds);
+    return with_elem(dtype, [&](auto* tag) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        AttnArgs<T> p = {};
+        p.q = (const T*)q; p.k = (const T*)k; p.v = (const T*)v; p.out = (T*)o; p.lse = lse; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
+        p.B = B; p.H = heads; p.L = L; p.S = S; p.d = d; p.scale = scale;
+        p.drop_thresh = drop_p > 0.f ? drop_thresh(drop_p) : 0u; p.drop_scale = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f; p.seed = seed; p.seed_dev = seed_source();
+        p.kv_len = kv_len;
+        return attn_route(ATTN_FWD_VARLEN_TRAIN, p, (hipStream_t)stream);
+    });
+}
+
 int psg_attn_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o,
                  int64_t ldo, const void* dout, int64_t lddo, const float* lse, float* delta, void* dq, int64_t lddq,
                  void* dk, int64_t lddk, void* dv, int64_t lddv, int B, int heads, int L, int S, int d, float scale,
                  float drop_p, uint64_t seed, int dtype, psg_stream_t stream) {
-    PSG_REQUIRE(q && k && v && o && dout && lse && delta && dq && dk && dv, PSG_ERR_ARG, "attn_bwd: null pointer");
-    int rc = attn_check("attn_bwd", B, heads, L, S, d, dtype, ldq, ldk, ldv, ldo);
-    if (rc) return rc;
-    PSG_REQUIRE(lddo >= heads * d && lddq >= heads * d && lddk >= heads * d && lddv >= heads * d && ((lddo | lddq | lddk | lddv) & 3) == 0,
-                PSG_ERR_SHAPE, "attn_bwd: gradient row strides");
-    PSG_REQUIRE(drop_p >= 0.f && drop_p < 1.f, PSG_ERR_ARG, "attn_bwd: drop_p");
-    const size_t l1 = dq_lds(S, d), l2 = dkv_lds(d);
-    PSG_REQUIRE(l1 <= 150 * 1024 && l2 <= 150 * 1024, PSG_ERR_SHAPE, "attn_bwd: LDS need too large");
-    return with_elem(dtype, [&](auto* tag) {
-        using T = std::remove_pointer_t<decltype(tag)>;
-        AttnArgs<T> p = {};
-        p.q = (const T*)q; p.k = (const T*)k; p.v = (const T*)v; p.o = (const T*)o; p.dout = (const T*)dout; p.lse = const_cast<float*>(lse); p.delta = delta;
-        p.dq = (T*)dq; p.dk = (T*)dk; p.dv = (T*)dv;
-        p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
-        p.B = B; p.H = heads; p.L = L; p.S = S; p.d = d; p.scale = scale;
-        p.drop_thresh = drop_p > 0.f ? drop_thresh(drop_p) : 0u; p.drop_scale = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f; p.seed = seed; p.seed_dev = seed_source();
-        return attn_route(ATTN_BWD, p, (hipStream_t)stream);
-    });
+    return attn_bwd_entry("attn_bwd", nullptr, q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, delta, dq, lddq, dk, lddk, dv, lddv, B, heads, L, S, d,
+                          scale, drop_p, seed, dtype, stream);
+}
+
+int psg_attn_bwd_varlen(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o,
+                        int64_t ldo, const void* dout, int64_t lddo, const float* lse, float* delta, void* dq, int64_t lddq,
+                        void* dk, int64_t lddk, void* dv, int64_t lddv, int B, int heads, int L, int S, int d, float scale,
+                        float drop_p, uint64_t seed, int dtype, const int32_t* kv_len, psg_stream_t stream) {
+    PSG_REQUIRE(kv_len, PSG_ERR_ARG, "attn_bwd_varlen: null pointer");
+    return attn_bwd_entry("attn_bwd_varlen", kv_len, q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, delta, dq, lddq, dk, lddk, dv, lddv, B, heads, L, S,
+                          d, scale, drop_p, seed, dtype, stream);
 }
 
 }  // extern "C"

@@ -167,7 +167,8 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_f32(const AttnArgs<float> p) 
 }
 
 // ------------------------------------------------------------------------------------------------ dQ (query on the lane)
-template <int ND>
+// VARLEN: only the key tiles below kv_len[b] are staged and computed
+template <int ND, bool VARLEN = false>
 __global__ __launch_bounds__(256, 1) void attn_dq_f32(const AttnArgs<float> p) {
     constexpr int D = ND * 16, HD = D / 2, NDT = (D + 31) / 32, STR = D * 4 + 16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -182,11 +183,13 @@ __global__ __launch_bounds__(256, 1) void attn_dq_f32(const AttnArgs<float> p) {
     const float* gg = p.dout + (int64_t)b * p.L * p.lddo + hd * D;
     const float* og = p.o + (int64_t)b * p.L * p.ldo + hd * D;
     float* dqg = p.dq + (int64_t)b * p.L * p.lddq + hd * D;
-    stage_f32(Ks, kg, p.ldk, 0, Sp, p.S, D, STR, tid, (int)blockDim.x);
-    stage_f32(Vs, vg, p.ldv, 0, Sp, p.S, D, STR, tid, (int)blockDim.x);
+    int Se = p.S, Spe = Sp;
+    if (VARLEN) { const int n = p.kv_len[b]; Se = n < 1 ? 1 : (n > p.S ? p.S : n); Spe = (Se + 31) & ~31; }
+    stage_f32(Ks, kg, p.ldk, 0, Spe, Se, D, STR, tid, (int)blockDim.x);
+    stage_f32(Vs, vg, p.ldv, 0, Spe, Se, D, STR, tid, (int)blockDim.x);
     __syncthreads();
     const int fr = lane & 31, fh = lane >> 5;
-    const int nkt = Sp >> 5;
+    const int nkt = Spe >> 5;
     for (int qt = wave; qt * 32 < p.L; qt += (int)(blockDim.x >> 6)) {
         const int l = qt * 32 + fr;
         const bool lok = l < p.L;
@@ -208,6 +211,33 @@ __global__ __launch_bounds__(256, 1) void attn_dq_f32(const AttnArgs<float> p) {
         const float lse = lok ? p.lse[(int64_t)bh * p.L + l] : 0.f;
         del += __shfl_xor(del, 32, 64);
         if (!lok) del = 0.f;
+        if (VARLEN && Se < p.S) {                  // (workgroup-uniform) a sample with masked keys: delta = sum_s drop(P) dP from
+            // the recomputed probabilities instead of rowsum(dO O), as in attention_mfma.hip (one rule for the three families;
+            // samples at full length keep psg_attn_bwd's delta and its bits)
+            float part = 0.f;
+            const uint64_t prow0 = ((uint64_t)bh * p.L + l) * (uint64_t)((p.S + 1) >> 1);
+            for (int kt = 0; kt < nkt; ++kt) {
+                f32x16 st, dp;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) { st[e] = 0.f; dp[e] = 0.f; }
+                st = dot_rows<HD>(Ks, STR, kt * 32 + fr, fh, qf, st);
+                dp = dot_rows<HD>(Vs, STR, kt * 32 + fr, fh, gf, dp);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int key = kt * 32 + acc_row32(r, fh);
+                    if (lok && key < Se) {
+                        float dpr = dp[r];
+                        if (p.drop_thresh) {
+                            const uint32_t hh = drop_hash_pair(eff_seed(p.seed, p.seed_dev), prow0 + (uint32_t)(key >> 1));
+                            dpr = drop_keep_half(hh, key & 1, p.drop_thresh) ? dpr * p.drop_scale : 0.f;
+                        }
+                        part += __expf(st[r] * p.scale - lse) * dpr;
+                    }
+                }
+            }
+            part += __shfl_xor(part, 32, 64);
+            del = lok ? part : 0.f;
+        }
         if (lok && fh == 0) p.delta[(int64_t)bh * p.L + l] = del;
         f32x16 dacc[NDT];
 #pragma unroll
@@ -225,7 +255,7 @@ __global__ __launch_bounds__(256, 1) void attn_dq_f32(const AttnArgs<float> p) {
             for (int r = 0; r < 16; ++r) {
                 const int key = kt * 32 + acc_row32(r, fh);
                 float ds = 0.f;
-                if (lok && key < p.S) {
+                if (lok && key < Se) {
                     const float pr = __expf(st[r] * p.scale - lse);
                     float dpr = dp[r];
                     if (p.drop_thresh) {
@@ -254,7 +284,9 @@ __global__ __launch_bounds__(256, 1) void attn_dq_f32(const AttnArgs<float> p) {
 }
 
 // ------------------------------------------------------------------------------------------------ dK, dV (key on the lane)
-template <int ND>
+// VARLEN: keys at or past kv_len[b] are absent (never read); their dK / dV rows are stored as zeros while s < S, and a key
+// tile wholly past the bound walks no query tile
+template <int ND, bool VARLEN = false>
 __global__ __launch_bounds__(256, 1) void attn_dkv_f32(const AttnArgs<float> p) {
     constexpr int D = ND * 16, HD = D / 2, NDT = (D + 31) / 32, STR = D * 4 + 16;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -281,9 +313,11 @@ __global__ __launch_bounds__(256, 1) void attn_dkv_f32(const AttnArgs<float> p) 
     const int fr = lane & 31, fh = lane >> 5;
     const int Sp = (p.S + 31) & ~31;
     const int nqt = Lp >> 5;
+    int Se = p.S;
+    if (VARLEN) { const int n = p.kv_len[b]; Se = n < 1 ? 1 : (n > p.S ? p.S : n); }
     for (int kt = wave; kt * 32 < Sp; kt += (int)(blockDim.x >> 6)) {
         const int key = kt * 32 + fr;
-        const bool kok = key < p.S;
+        const bool kok = key < Se;
         const int kr = kok ? key : 0;
         float kreg[HD], vreg[HD];
 #pragma unroll
@@ -298,7 +332,7 @@ __global__ __launch_bounds__(256, 1) void attn_dkv_f32(const AttnArgs<float> p) 
         for (int t = 0; t < NDT; ++t)
 #pragma unroll
             for (int e = 0; e < 16; ++e) { dk[t][e] = 0.f; dv[t][e] = 0.f; }
-        for (int qt = 0; qt < nqt; ++qt) {
+        for (int qt = (!VARLEN || kt * 32 < Se) ? 0 : nqt; qt < nqt; ++qt) {
             f32x16 st, dp;
 #pragma unroll
             for (int e = 0; e < 16; ++e) { st[e] = 0.f; dp[e] = 0.f; }
@@ -327,7 +361,7 @@ __global__ __launch_bounds__(256, 1) void attn_dkv_f32(const AttnArgs<float> p) 
             acc_cols<NDT>(Gs, STR, qt * 32, fr, fh, pd, dv);            // dV^T[dcol][key] += dO^T[dcol][q] P[q][key]
             acc_cols<NDT>(Qs, STR, qt * 32, fr, fh, st, dk);            // dK^T[dcol][key] += Q^T[dcol][q] dS[q][key]
         }
-        if (kok) {
+        if (VARLEN ? key < p.S : kok) {
 #pragma unroll
             for (int t = 0; t < NDT; ++t)
 #pragma unroll
@@ -336,6 +370,7 @@ __global__ __launch_bounds__(256, 1) void attn_dkv_f32(const AttnArgs<float> p) 
                     if (dd < D) {
                         f32x4 a = {dk[t][4 * g4], dk[t][4 * g4 + 1], dk[t][4 * g4 + 2], dk[t][4 * g4 + 3]};
                         f32x4 c = {dv[t][4 * g4], dv[t][4 * g4 + 1], dv[t][4 * g4 + 2], dv[t][4 * g4 + 3]};
+                        if (VARLEN && !kok) { a = f32x4{0.f, 0.f, 0.f, 0.f}; c = a; }
                         *reinterpret_cast<f32x4*>(dkg + (int64_t)key * p.lddk + dd) = a;
                         *reinterpret_cast<f32x4*>(dvg + (int64_t)key * p.lddv + dd) = c;
                     }
@@ -358,7 +393,8 @@ bool attn_f32_applicable(int L, int S, int d, int64_t ldq, int64_t ldk, int64_t 
 int attn_f32_init_attrs() {
     return for_each_nd(F32NDs{}, [](auto nd) {
         constexpr int ND = decltype(nd)::value;
-        return set_max_lds((int)F32_LDS_CAP, attn_fwd_f32<ND, false>, attn_fwd_f32<ND, true>, attn_dq_f32<ND>, attn_dkv_f32<ND>);
+        return set_max_lds((int)F32_LDS_CAP, attn_fwd_f32<ND, false>, attn_fwd_f32<ND, true>, attn_dq_f32<ND, false>, attn_dq_f32<ND, true>,
+                           attn_dkv_f32<ND, false>, attn_dkv_f32<ND, true>);
     });
 }
 
@@ -374,17 +410,20 @@ int attn_f32_fwd(const AttnArgs<float>& p, hipStream_t s) {
 template int attn_f32_fwd<false>(const AttnArgs<float>&, hipStream_t);
 template int attn_f32_fwd<true>(const AttnArgs<float>&, hipStream_t);
 
+template <bool VARLEN>
 int attn_f32_bwd(const AttnArgs<float>& p, hipStream_t s) {
     if (!with_nd(F32NDs{}, p.d, [&](auto nd) {
-            hipLaunchKernelGGL(attn_dq_f32<decltype(nd)::value>, dim3(p.B * p.H), dim3(64 * f32_waves(p.L)), f32_lds(p.S, p.d), s, p);
+            hipLaunchKernelGGL((attn_dq_f32<decltype(nd)::value, VARLEN>), dim3(p.B * p.H), dim3(64 * f32_waves(p.L)), f32_lds(p.S, p.d), s, p);
         }))
         return set_error(PSG_ERR_SHAPE, "attn_dq_f32: head_dim %d", p.d);
     PSG_LAUNCH_CHECK("attn_dq_f32");
     with_nd(F32NDs{}, p.d, [&](auto nd) {
-        hipLaunchKernelGGL(attn_dkv_f32<decltype(nd)::value>, dim3(p.B * p.H), dim3(64 * f32_waves(p.S)), f32_lds(p.L, p.d), s, p);
+        hipLaunchKernelGGL((attn_dkv_f32<decltype(nd)::value, VARLEN>), dim3(p.B * p.H), dim3(64 * f32_waves(p.S)), f32_lds(p.L, p.d), s, p);
     });
     PSG_LAUNCH_CHECK("attn_dkv_f32");
     return PSG_OK;
 }
+template int attn_f32_bwd<false>(const AttnArgs<float>&, hipStream_t);
+template int attn_f32_bwd<true>(const AttnArgs<float>&, hipStream_t);
 
 }  // namespace psg

@@ -203,7 +203,9 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_fwd_mfma(const At
 // ------------------------------------------------------------------------------------------------
 // dQ: same query-on-lane structure
 // ------------------------------------------------------------------------------------------------
-template <int ND>
+// VARLEN (psg_attn_bwd_varlen): as in the forward, only the key tiles below kv_len[b] are staged and computed; the rows of
+// the last one at or past the bound are staged as zeros, which is all the branch-free loop below needs
+template <int ND, bool VARLEN = false>
 __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dq_mfma(const AttnArgs<bf16_t> p) {
     constexpr int NDT = (ND + 1) / 2;
     constexpr int D32 = NDT * 32;
@@ -222,12 +224,14 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dq_mfma(const Att
     const bf16_t* gg = p.dout + (int64_t)b * p.L * p.lddo + hd * d;
     const bf16_t* og = p.o + (int64_t)b * p.L * p.ldo + hd * d;
     bf16_t* dqg = p.dq + (int64_t)b * p.L * p.lddq + hd * d;
-    stage_tile(Ks, kg, p.ldk, 0, Sp, p.S, d, d, STR, tid, (int)blockDim.x);
-    stage_tile(Vs, vg, p.ldv, 0, Sp, p.S, d, d, STR, tid, (int)blockDim.x);
+    int Se = p.S, Spe = Sp;
+    if (VARLEN) { const int n = p.kv_len[b]; Se = n < 1 ? 1 : (n > p.S ? p.S : n); Spe = (Se + 31) & ~31; }
+    stage_tile(Ks, kg, p.ldk, 0, Spe, Se, d, d, STR, tid, (int)blockDim.x);
+    stage_tile(Vs, vg, p.ldv, 0, Spe, Se, d, d, STR, tid, (int)blockDim.x);
     __syncthreads();
 
     const int fr = lane & 31, fh = lane >> 5;
-    const int nkt = Sp >> 5;
+    const int nkt = Spe >> 5;
     for (int qt = wave; qt * 32 < p.L; qt += (int)(blockDim.x >> 6)) {
         const int l = qt * 32 + fr;
         const bool lok = l < p.L;
@@ -253,6 +257,38 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dq_mfma(const Att
         }
         del += __shfl_xor(del, 32, 64);
         if (!lok) del = 0.f;
+        if (VARLEN && Se < p.S) {                  // (workgroup-uniform) a sample with masked keys: delta = sum_s drop(P) dP in
+            // fp32 from the recomputed probabilities instead of rowsum(dO O).  Few live keys concentrate P; dS = P (dP' - delta)
+            // then cancels (exactly, at kv_len = 1) and O's bf16 rounding inside delta would be all that is left of dk.  Samples at
+            // full length keep psg_attn_bwd's delta (and its bits).  The staged-as-zero rows of the last tile add P * 0.
+            float part = 0.f;
+            const DropRow dr = drop_row(seed, ((uint64_t)bh * p.L + l) * (uint64_t)((p.S + 1) >> 1));
+            const uint32_t t16 = p.drop_thresh >> 16;
+            for (int kt = 0; kt < nkt; ++kt) {
+                f32x16 st, dp;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) { st[e] = 0.f; dp[e] = 0.f; }
+#pragma unroll
+                for (int ks = 0; ks < ND; ++ks) {
+                    const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + (kt * 32 + fr) * STR + (16 * ks + 8 * fh) * 2);
+                    const bf16x8 vf = *reinterpret_cast<const bf16x8*>(Vs + (kt * 32 + fr) * STR + (16 * ks + 8 * fh) * 2);
+                    st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], st, 0, 0, 0);
+                    dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, gf[ks], dp, 0, 0, 0);
+                }
+                if (p.drop_thresh) {
+#pragma unroll
+                    for (int r = 0; r < 16; r += 2) {
+                        const uint32_t hh = drop_hash_row(dr, (uint32_t)(kt * 16 + (acc_row(r, fh) >> 1)));
+                        dp[r] = (hh & 0xFFFFu) >= t16 ? dp[r] * p.drop_scale : 0.f;
+                        dp[r + 1] = (hh >> 16) >= t16 ? dp[r + 1] * p.drop_scale : 0.f;
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) part += kt * 32 + acc_row(r, fh) < Se ? __expf(st[r] * p.scale - lse) * dp[r] : 0.f;
+            }
+            part += __shfl_xor(part, 32, 64);
+            del = lok ? part : 0.f;
+        }
         if (lok && fh == 0) p.delta[(int64_t)bh * p.L + l] = del;
         f32x16 dacc[NDT];
 #pragma unroll
@@ -315,7 +351,9 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dq_mfma(const Att
 // dK, dV: key on the lane.  Q and dO of the whole head live in LDS; each wave stages its own 32-key
 // K/V tile (row reads for the B operands) into a private LDS region.
 // ------------------------------------------------------------------------------------------------
-template <int ND>
+// VARLEN (psg_attn_bwd_varlen): a key at or past kv_len[b] is an absent key (zero K / V operands, never read from memory
+// past the bound) whose dK / dV rows are STORED as zeros while s < S; a key tile wholly past the bound walks no query tile.
+template <int ND, bool VARLEN = false>
 __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dkv_mfma(const AttnArgs<bf16_t> p) {
     constexpr int NDT = (ND + 1) / 2;
     constexpr int D32 = NDT * 32;
@@ -349,6 +387,8 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dkv_mfma(const At
     const int fr = lane & 31, fh = lane >> 5;
     const int Sp = (p.S + 31) & ~31;
     const int nqt = Lp >> 5;
+    int Se = p.S;
+    if (VARLEN) { const int n = p.kv_len[b]; Se = n < 1 ? 1 : (n > p.S ? p.S : n); }
     char* Kw = KVw + wave * (2 * 32 * STR);
     char* Vw = Kw + 32 * STR;
     // Waves = KW key tiles x QW query groups.  With more waves than key tiles (cross-attention: S = 32 is ONE key tile, and the
@@ -361,7 +401,7 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dkv_mfma(const At
     const bool active = qw < QW;
     for (int kt = kw; kt * 32 < Sp; kt += KW) {
         const int key = kt * 32 + fr;
-        const bool kok = key < p.S;
+        const bool kok = key < Se;
         bf16x8 kreg[KV_REG ? ND : 1], vreg[KV_REG ? ND : 1];
         if constexpr (KV_REG) {
 #pragma unroll
@@ -375,8 +415,8 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dkv_mfma(const At
             }
         } else {
             // private K/V tile (only this wave touches Kw/Vw: wave-level ordering suffices)
-            stage_tile(Kw, kg, p.ldk, kt * 32, 32, p.S, d, d, STR, lane, 64);
-            stage_tile(Vw, vg, p.ldv, kt * 32, 32, p.S, d, d, STR, lane, 64);
+            stage_tile(Kw, kg, p.ldk, kt * 32, 32, Se, d, d, STR, lane, 64);
+            stage_tile(Vw, vg, p.ldv, kt * 32, 32, Se, d, d, STR, lane, 64);
             __builtin_amdgcn_s_waitcnt(0);     // all counters: the wave's own LDS writes have landed
             __builtin_amdgcn_wave_barrier();
         }
@@ -391,7 +431,7 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dkv_mfma(const At
         for (int t = 0; t < TH; ++t)
 #pragma unroll
             for (int e = 0; e < 16; ++e) { dk[t][e] = 0.f; dv[t][e] = 0.f; }
-        for (int qt = active ? qw : nqt; qt < nqt; qt += QW) {
+        for (int qt = (active && (!VARLEN || kt * 32 < Se)) ? qw : nqt; qt < nqt; qt += QW) {
             f32x16 st, dp;
 #pragma unroll
             for (int e = 0; e < 16; ++e) { st[e] = 0.f; dp[e] = 0.f; }
@@ -478,7 +518,7 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dkv_mfma(const At
                 }
             }
         }
-        if (kok && qw == 0) {
+        if ((VARLEN ? key < p.S : kok) && qw == 0) {
 #pragma unroll
             for (int t = 0; t < TH; ++t)
 #pragma unroll
@@ -487,6 +527,7 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dkv_mfma(const At
                     if (dd < d) {
                         f32x4 a = {dk[t][4 * g4], dk[t][4 * g4 + 1], dk[t][4 * g4 + 2], dk[t][4 * g4 + 3]};
                         f32x4 c = {dv[t][4 * g4], dv[t][4 * g4 + 1], dv[t][4 * g4 + 2], dv[t][4 * g4 + 3]};
+                        if (VARLEN && !kok) { a = f32x4{0.f, 0.f, 0.f, 0.f}; c = a; }
                         store4<bf16_t>(dkg + (int64_t)key * p.lddk + dd, a);
                         store4<bf16_t>(dvg + (int64_t)key * p.lddv + dd, c);
                     }
@@ -539,7 +580,8 @@ bool attn_mfma_applicable(int L, int S, int d, int64_t ldq, int64_t ldk, int64_t
 int attn_mfma_init_attrs() {
     return for_each_nd(MfmaNDs{}, [](auto nd) {
         constexpr int ND = decltype(nd)::value;
-        return set_max_lds((int)MFMA_LDS_CAP, attn_fwd_mfma<ND, false>, attn_fwd_mfma<ND, true>, attn_dq_mfma<ND>, attn_dkv_mfma<ND>);
+        return set_max_lds((int)MFMA_LDS_CAP, attn_fwd_mfma<ND, false>, attn_fwd_mfma<ND, true>, attn_dq_mfma<ND, false>, attn_dq_mfma<ND, true>,
+                           attn_dkv_mfma<ND, false>, attn_dkv_mfma<ND, true>);
     });
 }
 
@@ -555,17 +597,20 @@ int attn_mfma_fwd(const AttnArgs<bf16_t>& p, hipStream_t s) {
 template int attn_mfma_fwd<false>(const AttnArgs<bf16_t>&, hipStream_t);
 template int attn_mfma_fwd<true>(const AttnArgs<bf16_t>&, hipStream_t);
 
+template <bool VARLEN>
 int attn_mfma_bwd(const AttnArgs<bf16_t>& p, hipStream_t s) {
     if (!with_nd(MfmaNDs{}, p.d, [&](auto nd) {
-            hipLaunchKernelGGL(attn_dq_mfma<decltype(nd)::value>, dim3(p.B * p.H), dim3(64 * attn_waves(p.L)), fwd_lds_m(p.S, p.d), s, p);
+            hipLaunchKernelGGL((attn_dq_mfma<decltype(nd)::value, VARLEN>), dim3(p.B * p.H), dim3(64 * attn_waves(p.L)), fwd_lds_m(p.S, p.d), s, p);
         }))
         return set_error(PSG_ERR_SHAPE, "attn_dq_mfma: head_dim %d", p.d);
     PSG_LAUNCH_CHECK("attn_dq_mfma");
     with_nd(MfmaNDs{}, p.d, [&](auto nd) {
-        hipLaunchKernelGGL(attn_dkv_mfma<decltype(nd)::value>, dim3(p.B * p.H), dim3(64 * dkv_waves(p.L, p.S, p.d)), dkv_lds_m(p.L, p.S, p.d), s, p);
+        hipLaunchKernelGGL((attn_dkv_mfma<decltype(nd)::value, VARLEN>), dim3(p.B * p.H), dim3(64 * dkv_waves(p.L, p.S, p.d)), dkv_lds_m(p.L, p.S, p.d), s, p);
     });
     PSG_LAUNCH_CHECK("attn_dkv_mfma");
     return PSG_OK;
 }
+template int attn_mfma_bwd<false>(const AttnArgs<bf16_t>&, hipStream_t);
+template int attn_mfma_bwd<true>(const AttnArgs<bf16_t>&, hipStream_t);
 
 }  // namespace psg

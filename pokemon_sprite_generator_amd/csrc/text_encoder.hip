@@ -1,6 +1,7 @@
-// Row kernels of the frozen BERT text encoder (reference: src/models/text_encoder.py, a transformers BertModel):
+// Row kernels of the BERT text encoder (reference: src/models/text_encoder.py, a transformers BertModel):
 //   psg_layernorm      y = LN(x [+ r]) * gamma + beta over rows of width N (BERT's two post-LNs per layer, the final
 //                      nn.LayerNorm of the TextEncoder);
+//   psg_layernorm_bwd  its backward (fine-tuning): dz, dgamma, dbeta from the forward's operands and dy;
 //   psg_bert_embed_ln  BertEmbeddings: LN(word_emb[id] + type_emb[type] + pos_emb[s]).
 // One wave per row (N = 768: 64 lanes x 12 values), four rows per workgroup and many workgroups per CU in flight.  A lane
 // holds its chunks of 8 consecutive values in registers from the load to the store: one pass over HBM each way.
@@ -37,24 +38,32 @@ template <> __device__ __forceinline__ void st8<bf16_t>(bf16_t* p, const float (
     *reinterpret_cast<bf16x8*>(p) = a;
 }
 
-// normalise the row a wave holds (chunk i of the lane = columns 8*(lane + 64*i) .. +7, valid while < nch) and store it
-template <int CPL, typename TO>
-__device__ __forceinline__ void ln_store(float (&v)[CPL][8], int lane, int nch, int N, const float* __restrict__ gamma,
-                                         const float* __restrict__ beta, float eps, TO* yrow) {
+// mean and 1/sqrt(var + eps) of the row a wave holds (chunk i of the lane = columns 8*(lane + 64*i) .. +7, valid while
+// < nch): the one statement of the statistics - the backward recomputes them with this code, so its x_hat has the forward's bits
+template <int CPL>
+__device__ __forceinline__ void ln_stats(const float (&v)[CPL][8], int lane, int nch, int N, float eps, float& mean, float& rstd) {
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < CPL; ++i)
         if (lane + 64 * i < nch)
 #pragma unroll
             for (int j = 0; j < 8; ++j) s += v[i][j];
-    const float mean = wave_sum(s) / (float)N;
+    mean = wave_sum(s) / (float)N;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < CPL; ++i)
         if (lane + 64 * i < nch)
 #pragma unroll
             for (int j = 0; j < 8; ++j) { const float c = v[i][j] - mean; q += c * c; }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)N + eps);
+    rstd = 1.0f / sqrtf(wave_sum(q) / (float)N + eps);
+}
+
+// normalise the row a wave holds and store it
+template <int CPL, typename TO>
+__device__ __forceinline__ void ln_store(float (&v)[CPL][8], int lane, int nch, int N, const float* __restrict__ gamma,
+                                         const float* __restrict__ beta, float eps, TO* yrow) {
+    float mean, rstd;
+    ln_stats<CPL>(v, lane, nch, N, eps, mean, rstd);
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {
         const int c = lane + 64 * i;
@@ -138,6 +147,131 @@ __global__ __launch_bounds__(64 * LN_ROWS) void embed_ln_kernel(const int64_t* _
     ln_store<CPL, TO>(v, lane, nch, N, gamma, beta, eps, yrow);
 }
 
+// ------------------------------------------------------------------------------------------------ LayerNorm backward
+// z = x (+ r), x_hat = (z - mean) rstd (statistics recomputed by ln_stats: nothing but the inputs is saved), g = dy gamma:
+//   dz     = rstd (g - mean_N(g) - x_hat mean_N(g x_hat))        one wave per row, chunks in registers from load to store
+//   dgamma = sum_rows dy x_hat,  dbeta = sum_rows dy             (PG) a wave walks LNB_RPW consecutive rows and keeps its columns'
+// sums in registers; the four waves of a workgroup meet in LDS in wave order, and the workgroup's partial row goes to the
+// workspace [2][workgroups][N] (ln_param_sum_kernel adds the workgroups in a fixed order).  No atomics; the grid depends on
+// (rows, N) alone, so the bits do not depend on the device.
+constexpr int LNB_RPW = 16;                         // rows per wave
+constexpr int LNB_WG_ROWS = LN_ROWS * LNB_RPW;      // rows per workgroup
+
+template <typename TI, typename TDY, int CPL, bool PG>
+__global__ __launch_bounds__(64 * LN_ROWS) void layernorm_bwd_kernel(const TI* __restrict__ x, int64_t ldx, const TI* __restrict__ r,
+                                                                      int64_t ldr, const TDY* __restrict__ dy, int64_t lddy,
+                                                                      const float* __restrict__ gamma, TI* __restrict__ dz, int64_t lddz,
+                                                                      float* __restrict__ part, int64_t rows, int N, float eps) {
+    __shared__ float red[LN_ROWS - 1][2][8][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nch = N >> 3;
+    const float invN = 1.0f / (float)N;
+    float ag[PG ? CPL : 1][8], ab[PG ? CPL : 1][8];
+    if (PG) {
+#pragma unroll
+        for (int i = 0; i < CPL; ++i)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { ag[i][j] = 0.f; ab[i][j] = 0.f; }
+    }
+    const int64_t row0 = ((int64_t)blockIdx.x * LN_ROWS + wave) * LNB_RPW;
+    for (int it = 0; it < LNB_RPW; ++it) {
+        const int64_t row = row0 + it;
+        if (row >= rows) break;                                   // (wave-uniform)
+        float v[CPL][8], g[CPL][8];
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const int c = lane + 64 * i;
+            if (c < nch) {
+                ld8<TI>(x + row * ldx + 8 * c, v[i]);
+                if (r) {                                          // (uniform)
+                    float t[8];
+                    ld8<TI>(r + row * ldr + 8 * c, t);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[i][j] += t[j];
+                }
+                ld8<TDY>(dy + row * lddy + 8 * c, g[i]);
+            }
+        }
+        float mean, rstd;
+        ln_stats<CPL>(v, lane, nch, N, eps, mean, rstd);
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const int c = lane + 64 * i;
+            if (c < nch) {
+                float gm[8];
+                ld8<float>(gamma + 8 * c, gm);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float xh = (v[i][j] - mean) * rstd;
+                    if (PG) { ag[i][j] += g[i][j] * xh; ab[i][j] += g[i][j]; }
+                    v[i][j] = xh;
+                    g[i][j] *= gm[j];
+                    s1 += g[i][j];
+                    s2 += g[i][j] * xh;
+                }
+            }
+        }
+        s1 = wave_sum(s1) * invN;
+        s2 = wave_sum(s2) * invN;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const int c = lane + 64 * i;
+            if (c < nch) {
+                float o[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) o[j] = rstd * ((g[i][j] - s1) - v[i][j] * s2);
+                st8<TI>(dz + row * lddz + 8 * c, o);
+            }
+        }
+    }
+    if (PG) {
+        float* pg = part + (int64_t)blockIdx.x * N;
+        float* pb = part + ((int64_t)gridDim.x + blockIdx.x) * N;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const int c = lane + 64 * i;
+            __syncthreads();
+            if (wave > 0) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { red[wave - 1][0][j][lane] = ag[i][j]; red[wave - 1][1][j][lane] = ab[i][j]; }
+            }
+            __syncthreads();
+            if (wave == 0 && c < nch) {
+#pragma unroll
+                for (int w = 0; w < LN_ROWS - 1; ++w)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) { ag[i][j] += red[w][0][j][lane]; ab[i][j] += red[w][1][j][lane]; }
+                st8<float>(pg + 8 * c, ag[i]);
+                st8<float>(pb + 8 * c, ab[i]);
+            }
+        }
+    }
+}
+
+// out[c] (+)= sum over the nwg workgroup partials of column c, for dgamma (blockIdx.y = 0) and dbeta (1): 64 columns x 4
+// partial lanes per workgroup, each lane in ascending order, the four lanes in LDS order
+__global__ __launch_bounds__(256) void ln_param_sum_kernel(const float* __restrict__ part, int nwg, int N, float* __restrict__ dgamma,
+                                                            float* __restrict__ dbeta, int accumulate) {
+    __shared__ float red[4][64];
+    float* out = blockIdx.y ? dbeta : dgamma;
+    if (!out) return;                                             // (workgroup-uniform)
+    const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + cl;
+    float a = 0.f;
+    if (c < N) {
+        const float* base = part + (int64_t)blockIdx.y * nwg * N + c;
+        for (int w = rl; w < nwg; w += 4) a += base[(int64_t)w * N];
+    }
+    red[rl][cl] = a;
+    __syncthreads();
+    if (rl == 0 && c < N) {
+        float v = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
+        if (accumulate) v += out[c];
+        out[c] = v;
+    }
+}
+
 using LnCpls = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8>;      // 16-byte chunks per lane: every N row_width_check admits
 
 static int row_width_check(const char* who, int N) {
@@ -171,6 +305,45 @@ int psg_layernorm(const void* x, int64_t ldx, const void* r, int64_t ldr, void* 
                            (const TI*)r, r ? ldr : (int64_t)0, (TO*)y, ldy, gamma, beta, rows, N, eps);
     }); }); }); });
     PSG_LAUNCH_CHECK("layernorm");
+    return PSG_OK;
+}
+
+int64_t psg_layernorm_bwd_workspace_bytes(int64_t rows, int N) {
+    if (rows <= 0 || N <= 0) return 0;
+    return 2 * ((rows + LNB_WG_ROWS - 1) / LNB_WG_ROWS) * (int64_t)N * (int64_t)sizeof(float);
+}
+
+int psg_layernorm_bwd(const void* x, int64_t ldx, const void* r, int64_t ldr, const void* dy, int64_t lddy, const float* gamma,
+                      void* dz, int64_t lddz, float* dgamma, float* dbeta, int accumulate, int64_t rows, int N, float eps,
+                      int x_dtype, int dy_dtype, void* ws, int64_t ws_bytes, psg_stream_t stream) {
+    PSG_REQUIRE(x && dy && gamma && dz, PSG_ERR_ARG, "layernorm_bwd: null pointer");
+    PSG_REQUIRE((x_dtype == PSG_F32 || x_dtype == PSG_BF16) && (dy_dtype == PSG_F32 || dy_dtype == PSG_BF16), PSG_ERR_DTYPE,
+                "layernorm_bwd: dtypes x %d, dy %d", x_dtype, dy_dtype);
+    { const int rc = row_width_check("layernorm_bwd", N); if (rc) return rc; }
+    PSG_REQUIRE(rows > 0 && rows <= (int64_t)LNB_WG_ROWS * 0x7FFFFFFF, PSG_ERR_SHAPE, "layernorm_bwd: rows=%ld", (long)rows);
+    PSG_REQUIRE(eps >= 0.f, PSG_ERR_ARG, "layernorm_bwd: eps %g", (double)eps);
+    PSG_REQUIRE(ldx >= N && lddy >= N && lddz >= N && (!r || ldr >= N), PSG_ERR_SHAPE, "layernorm_bwd: row stride < N");
+    PSG_REQUIRE(((ldx | lddy | lddz | (r ? ldr : 0)) & 7) == 0 && aligned16(x) && aligned16(dy) && aligned16(dz) && (!r || aligned16(r)) &&
+                aligned16(gamma), PSG_ERR_ALIGN, "layernorm_bwd: rows must start on 16-byte boundaries (strides multiples of 8)");
+    const bool pg = dgamma || dbeta;
+    PSG_REQUIRE(!pg || ws, PSG_ERR_ARG, "layernorm_bwd: dgamma / dbeta need a workspace");
+    PSG_REQUIRE(!pg || aligned16(ws), PSG_ERR_ALIGN, "layernorm_bwd: workspace must start on a 16-byte boundary");
+    PSG_REQUIRE(!pg || ws_bytes >= psg_layernorm_bwd_workspace_bytes(rows, N), PSG_ERR_WORKSPACE, "layernorm_bwd: workspace of %ld bytes, need %ld",
+                (long)ws_bytes, (long)psg_layernorm_bwd_workspace_bytes(rows, N));
+    const int cpl = (N / 8 + 63) / 64;
+    const int nwg = (int)((rows + LNB_WG_ROWS - 1) / LNB_WG_ROWS);
+    hipStream_t s = (hipStream_t)stream;
+    with_dtype(x_dtype, [&](auto ti) { with_dtype(dy_dtype, [&](auto tdy) {
+    with_const(LnCpls{}, cpl, [&](auto c) { with_const(Bools{}, pg, [&](auto p) {
+        using TI = decltype(ti); using TDY = decltype(tdy);
+        hipLaunchKernelGGL((layernorm_bwd_kernel<TI, TDY, decltype(c)::value, decltype(p)::value>), dim3((unsigned)nwg), dim3(64 * LN_ROWS), 0, s,
+                           (const TI*)x, ldx, (const TI*)r, r ? ldr : (int64_t)0, (const TDY*)dy, lddy, gamma, (TI*)dz, lddz, (float*)ws, rows, N, eps);
+    }); }); }); });
+    PSG_LAUNCH_CHECK("layernorm_bwd");
+    if (pg) {
+        hipLaunchKernelGGL(ln_param_sum_kernel, dim3((unsigned)((N + 63) / 64), 2), dim3(256), 0, s, (const float*)ws, nwg, N, dgamma, dbeta, accumulate);
+        PSG_LAUNCH_CHECK("layernorm_bwd_param_sum");
+    }
     return PSG_OK;
 }
 

@@ -681,6 +681,76 @@ def linear(x, weight, bias=None, residual=None, act=ACT_NONE, alpha=1.0, drop_p=
     return _ConvFn.apply(x, weight, bias, None, residual, 1, act, alpha, drop_p, seed, out)
 
 
+class _QKVFn(torch.autograd.Function):
+    """qkv = x . [Wq; Wk; Wv]^T + [bq; bk; bv] as ONE GEMM over a packed prepared weight (BERT's self-attention input:
+    query, key and value stay three parameters with three gradients).  `packed` = (wf [3H][Kpad], fp32 bias [3H],
+    wd [Cin][Kpad'] for the data gradient), prepared by the caller from the three weights.  Backward: one data-gradient
+    GEMM over wd, three weight-gradient launches reading the column slices of dqkv (bias gradients fused)."""
+
+    @staticmethod
+    def forward(ctx, x, wq, bq, wk, bk, wv, bv, packed):
+        lib = _lib_for(x)
+        wf, bcat, wd = packed
+        xr, ldx = _rows(x)
+        Cin, H = wq.shape[1], wq.shape[0]
+        M = xr.numel() // xr.shape[-1]
+        y = torch.empty(tuple(x.shape[:-1]) + (3 * H,), dtype=x.dtype, device=x.device)
+        geom = (M, 1, 1, 1, 1, 1, 1, 0)
+        _conv_launch(lib, x.dtype, xr, ldx, wf, 0, y, 3 * H, geom, Cin, 3 * H, bias=bcat)
+        ctx.save_for_backward(xr, wd)
+        ctx.params = (wq, bq, wk, bk, wv, bv)
+        ctx.meta = (geom, Cin, H, ldx, tuple(x.shape))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xr, wd = ctx.saved_tensors
+        geom, Cin, H, ldx, x_shape = ctx.meta
+        lib = _lib_for(dy)
+        dtype = dy.dtype
+        g, ldg = _rows(dy)
+        g2 = g.view(-1, g.shape[-1]) if ldg == g.shape[-1] else g
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(x_shape, dtype=dtype, device=dy.device)
+            _conv_launch(lib, dtype, g, ldg, wd, 0, dx, Cin, geom, 3 * H, Cin, transposed=True)
+        grads = []
+        for i in range(3):
+            w, b = ctx.params[2 * i], ctx.params[2 * i + 1]
+            need_w, need_b = ctx.needs_input_grad[1 + 2 * i], ctx.needs_input_grad[2 + 2 * i]
+            gi = g2[..., i * H:(i + 1) * H]                  # a column slice of dqkv: same row stride, start moved
+            dw = db = None
+            if need_w:
+                wo, wacc, we = _param_out(w)
+                bo, bacc, be = _param_out(b) if need_b else (None, False, None)
+                _wgrad_launch(lib, dtype, xr, ldx, gi, ldg, wo, geom, Cin, H, accumulate=wacc, dbias=bo, accumulate_bias=bacc)
+                dw = _param_ret(wo, we)
+                if need_b:
+                    db = _param_ret(bo, be)
+            elif need_b:
+                db = _param_grad(b, lambda out, acc, gi=gi: _colsum(lib, gi, ldg, geom[0], 1, H, dtype, torch.float32, out=out, accumulate=acc))
+            grads += [dw, db]
+        return (dx, *grads, None)
+
+
+def qkv_linear(x, wq, bq, wk, bk, wv, bv, packed):
+    """x [..., Cin] -> packed [..., 3H] projections (query | key | value columns), see _QKVFn."""
+    return _QKVFn.apply(x, wq, bq, wk, bk, wv, bv, packed)
+
+
+def prep_qkv(wq, wk, wv, bq, bk, bv, dtype, need_wd):
+    """The `packed` operand of qkv_linear: the three [H][Cin] fp32 weights as one prepared forward weight, the fp32 bias,
+    and (need_wd) the prepared data-gradient weight."""
+    lib = _lib_for(wq)
+    src = torch.cat([wq.detach(), wk.detach(), wv.detach()], 0).float().contiguous()
+    O, I = src.shape
+    code = dtype_code(dtype)
+    wf = torch.empty((O, lib.psg_kpad(I, code)), dtype=dtype, device=src.device)
+    wd = torch.empty((I, lib.psg_kpad(O, code)), dtype=dtype, device=src.device) if need_wd else None
+    check(lib.psg_prep_weight(ptr(src), dtype_code(torch.float32), W_OIHW, ptr(wf), ptr(wd), O, I, 1, code, stream_ptr()), "psg_prep_weight")
+    return wf, torch.cat([bq.detach(), bk.detach(), bv.detach()]).float().contiguous(), wd
+
+
 _FFN_SAVE_DACT = os.environ.get("PSG_FFN_SAVE_DACT", "1") != "0"     # 0: save u, re-evaluate gelu'(u) and the mask in backward (A/B)
 _GN_SPLIT = os.environ.get("PSG_GN_SPLIT", "1") != "0"               # 0: plain GroupNorm node, autograd adds the bypass gradient (A/B)
 
@@ -1013,13 +1083,71 @@ def group_norm_split(x, gamma, beta, groups, eps=1e-5, silu=False):
 
 
 # ---------------------------------------------------------------------------
+# LayerNorm
+# ---------------------------------------------------------------------------
+class _LayerNormFn(torch.autograd.Function):
+    """y = LayerNorm(x [+ residual]) * gamma + beta over the last dimension: psg_layernorm / psg_layernorm_bwd.  Only the
+    inputs are saved (the backward recomputes the statistics); the one dz serves x and the residual."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, residual, out_dtype):
+        lib = _lib_for(x)
+        N = x.shape[-1]
+        rows = x.numel() // N
+        xr, ldx = _rows(x)
+        rr, ldr = _rows(residual) if residual is not None else (None, 0)
+        out_dtype = x.dtype if out_dtype is None else out_dtype
+        y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+        check(lib.psg_layernorm(ptr(xr), ldx, ptr(rr), ldr, ptr(y), N, ptr(gamma), ptr(beta), rows, N, float(eps), dtype_code(x.dtype),
+                                dtype_code(out_dtype), stream_ptr()), "psg_layernorm")
+        ctx.save_for_backward(xr, rr, gamma)
+        ctx.gamma_param, ctx.beta_param = gamma, beta
+        ctx.meta = (rows, N, float(eps), ldx, ldr, tuple(x.shape))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xr, rr, gamma = ctx.saved_tensors
+        rows, N, eps, ldx, ldr, shape = ctx.meta
+        lib = _lib_for(dy)
+        dyr, lddy = _rows(dy)
+        dz = torch.empty(shape, dtype=xr.dtype, device=dy.device)
+        want_g, want_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        go, gacc, ge = _param_out(ctx.gamma_param) if want_g else (None, False, None)
+        bo, bacc, be = _param_out(ctx.beta_param) if want_b else (None, False, None)
+        if want_g and want_b and gacc != bacc:         # one accumulate flag per launch: beta goes through a zeroed tensor, joined after
+            bo2 = torch.zeros_like(bo)
+        else:
+            bo2 = bo
+        need = lib.psg_layernorm_bwd_workspace_bytes(rows, N) if (want_g or want_b) else 0
+        ws = _lib.workspace(need, dy.device) if need else None
+        check(lib.psg_layernorm_bwd(ptr(xr), ldx, ptr(rr), ldr, ptr(dyr), lddy, ptr(gamma), ptr(dz), N, ptr(go), ptr(bo2),
+                                    int(gacc if want_g else bacc), rows, N, eps, dtype_code(xr.dtype), dtype_code(dy.dtype), ptr(ws),
+                                    ws.numel() if ws is not None else 0, stream_ptr()), "psg_layernorm_bwd")
+        if bo2 is not bo:
+            bo.add_(bo2) if bacc else bo.copy_(bo2)
+        dg = _param_ret(go, ge) if want_g else None
+        db = _param_ret(bo, be) if want_b else None
+        need_x = ctx.needs_input_grad[0]
+        need_r = rr is not None and ctx.needs_input_grad[4]
+        return (dz if need_x else None), dg, db, None, (dz if need_r else None), None
+
+
+def layer_norm(x, weight, bias, eps, residual=None, out_dtype=None):
+    """nn.LayerNorm over the last dimension of x [..., N] (+ a residual added first: BERT's post-LN), fp32 parameters;
+    `out_dtype`: the result's dtype (x's by default).  The forward values are text_encoder.layer_norm's."""
+    return _LayerNormFn.apply(x, weight, bias, eps, residual, out_dtype)
+
+
+# ---------------------------------------------------------------------------
 # attention core
 # ---------------------------------------------------------------------------
 class _AttnFn(torch.autograd.Function):
-    """softmax((q/sqrt(d)) k^T) v for packed projections.  self: qkv [B,L,3E]; cross: q [B,L,E], kv [B,S,2E]."""
+    """softmax((q/sqrt(d)) k^T) v for packed projections.  self: qkv [B,L,3E]; cross: q [B,L,E], kv [B,S,2E].
+    With `kv_len` (int32 [B] on the device) the keys of sample b end at kv_len[b]: psg_attn_fwd_varlen_train / psg_attn_bwd_varlen."""
 
     @staticmethod
-    def forward(ctx, q_src, kv_src, heads, drop_p, seed):
+    def forward(ctx, q_src, kv_src, heads, drop_p, seed, kv_len=None):
         lib = _lib_for(q_src)
         dtype = q_src.dtype
         self_mode = kv_src is None
@@ -1040,8 +1168,14 @@ class _AttnFn(torch.autograd.Function):
         scale = float(d) ** -0.5
         o = torch.empty((B, L, E), dtype=dtype, device=q_src.device)
         lse = torch.empty((B, heads, L), dtype=torch.float32, device=q_src.device)
-        check(lib.psg_attn_fwd(qr.data_ptr(), ldq, kp, ldk, vp, ldk, ptr(o), E, ptr(lse), B, heads, L, S, d, scale, float(drop_p),
-                               int(seed), dtype_code(dtype), stream_ptr()), "psg_attn_fwd")
+        if kv_len is None:
+            check(lib.psg_attn_fwd(qr.data_ptr(), ldq, kp, ldk, vp, ldk, ptr(o), E, ptr(lse), B, heads, L, S, d, scale, float(drop_p),
+                                   int(seed), dtype_code(dtype), stream_ptr()), "psg_attn_fwd")
+        else:
+            check(lib.psg_attn_fwd_varlen_train(qr.data_ptr(), ldq, kp, ldk, vp, ldk, ptr(o), E, ptr(lse), B, heads, L, S, d, scale,
+                                                float(drop_p), int(seed), dtype_code(dtype), ptr(kv_len), stream_ptr()),
+                  "psg_attn_fwd_varlen_train")
+        ctx.kv_len = kv_len
         ctx.save_for_backward(qr, kvr, o, lse)
         ctx.meta = (self_mode, B, L, S, E, heads, d, scale, drop_p, seed, ldq, ldk, tuple(q_src.shape), None if self_mode else tuple(kv_src.shape))
         return o
@@ -1066,14 +1200,22 @@ class _AttnFn(torch.autograd.Function):
             dkv = torch.empty(kvshape, dtype=dtype, device=do.device)
             kp, vp = kvr.data_ptr(), kvr.data_ptr() + E * esz
             dqp, dkp, dvp, lddq, lddk = dqkv.data_ptr(), dkv.data_ptr(), dkv.data_ptr() + E * esz, E, 2 * E
-        check(lib.psg_attn_bwd(qr.data_ptr(), ldq, kp, ldk, vp, ldk, ptr(o), E, ptr(dor), lddo, ptr(lse), ptr(delta), dqp, lddq, dkp,
-                               lddk, dvp, lddk, B, heads, L, S, d, scale, float(drop_p), int(seed), dtype_code(dtype), stream_ptr()),
-              "psg_attn_bwd")
-        return dqkv, dkv, None, None, None
+        if ctx.kv_len is None:
+            check(lib.psg_attn_bwd(qr.data_ptr(), ldq, kp, ldk, vp, ldk, ptr(o), E, ptr(dor), lddo, ptr(lse), ptr(delta), dqp, lddq, dkp,
+                                   lddk, dvp, lddk, B, heads, L, S, d, scale, float(drop_p), int(seed), dtype_code(dtype), stream_ptr()),
+                  "psg_attn_bwd")
+        else:
+            check(lib.psg_attn_bwd_varlen(qr.data_ptr(), ldq, kp, ldk, vp, ldk, ptr(o), E, ptr(dor), lddo, ptr(lse), ptr(delta), dqp, lddq,
+                                          dkp, lddk, dvp, lddk, B, heads, L, S, d, scale, float(drop_p), int(seed), dtype_code(dtype),
+                                          ptr(ctx.kv_len), stream_ptr()), "psg_attn_bwd_varlen")
+        return dqkv, dkv, None, None, None, None
 
 
-def attention_self(qkv, heads, drop_p=0.0, seed=0):
-    return _AttnFn.apply(qkv, None, heads, drop_p, seed)
+def attention_self(qkv, heads, drop_p=0.0, seed=0, kv_len=None):
+    """Self-attention over packed qkv [B, L, 3E]; `kv_len` (int32 [B], device): the keys of sample b end at kv_len[b]."""
+    if kv_len is None:
+        return _AttnFn.apply(qkv, None, heads, drop_p, seed)
+    return _AttnFn.apply(qkv, None, heads, drop_p, seed, kv_len)
 
 
 def attention_cross(q, kv, heads, drop_p=0.0, seed=0):

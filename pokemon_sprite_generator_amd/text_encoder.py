@@ -1,9 +1,9 @@
-"""Frozen BERT text encoder on the MI355X kernels (reference: src/models/text_encoder.py).
+"""BERT text encoder on the MI355X kernels, frozen or fine-tuned in its last layers (reference: src/models/text_encoder.py).
 
 The reference wraps a transformers `BertModel` (+ `projection`, Linear or Identity, + `layer_norm`) and returns the
 normalised `last_hidden_state` [B, S, hidden_dim] of a right-padded token batch.  Stage 2 calls it for every training
 and validation batch and every monitoring sample (improved_diffusion_trainer.py:155,202-208,352,461,583) with the model
-frozen; this class computes that forward on the library's kernels:
+frozen; stages 1 and 3 train it under `finetune_strategy`.  This class computes the forward on the library's kernels:
 
   psg_bert_embed_ln        word + token-type + position embeddings, LayerNorm                   1 launch
   per layer (post-LN):     QKV Linear over one packed [3H][H] prepared weight (fp32 bias)        7 launches
@@ -19,22 +19,34 @@ Parameters carry the reference module's names and shapes (`bert.embeddings.*`, `
 `projection.*` when present, `layer_norm.*`), so a stage-1 checkpoint's 'text_encoder_state_dict' loads unchanged.  The
 pooler is kept for checkpoint interchange only: the reference returns `last_hidden_state`, never the pooled output.
 
-Inference only (`torch.no_grad()`): `finetune_strategy` is accepted for signature compatibility and validated, but the
-parameters stay frozen here - fine-tuning the text encoder (stage 3) stays on the reference class.  `transformers` is used
-on the host only, to load a pretrained tokenizer / config / state dict (`model_name`) and to tokenize (`forward`);
-`encode_ids` needs neither it nor any host synchronisation.
+By default (`trainable=False`) the class is inference only: every parameter frozen, `torch.no_grad()`, `.train()` ignored;
+`finetune_strategy` is validated and otherwise unused.  With `trainable=True` the strategy is applied as the reference
+applies it ('none': BERT frozen; 'minimal': last 2 encoder layers + pooler; 'partial': last 4 + pooler; `projection` and
+`layer_norm` always trainable; 'full' raises - the embedding gradients are not built).  When grad mode is on, the frozen
+prefix runs under no_grad on the inference launches and the trainable suffix through the autograd nodes of `ops`
+(`qkv_linear`, `attention_self(kv_len=)`, `linear`, `layer_norm`): autograd stops at the first trainable layer's input, and
+nothing of the prefix is kept.  Parameters and gradients are fp32 (`p.grad`), the activations `compute_dtype`.  `.train()`
+draws BERT's dropouts (hidden_dropout_prob after the embedding LayerNorm and the two output denses of every layer,
+attention_probs_dropout_prob on the probabilities - `bert_config` keys of those names, default 0.1) in frozen and trainable
+layers alike, with per-site seeds from the stream the U-Net's attention blocks use.  The pooler's parameters are trainable
+under 'minimal' / 'partial' as in the reference and, as there, never receive a gradient: `last_hidden_state` is returned.
+
+`transformers` is used on the host only, to load a pretrained tokenizer / config / state dict (`model_name`) and to
+tokenize (`forward`); `encode_ids` needs neither it nor any host synchronisation.
 """
 import torch
 import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import ACT_GELU, ACT_NONE, check, dtype_code, ptr, stream_ptr
+from .unet import _SeedStream
 from .vae import _prep, _prepared
 
 # keys of a `bert_config` dict (transformers.BertConfig attribute names)
 CONFIG_KEYS = ("hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size", "vocab_size",
                "max_position_embeddings", "type_vocab_size", "layer_norm_eps")
 FINETUNE_STRATEGIES = ("none", "minimal", "partial", "full")
+DROPOUT_KEYS = ("hidden_dropout_prob", "attention_probs_dropout_prob")      # optional `bert_config` keys (BertConfig defaults: 0.1)
 MAX_LENGTH = 256                    # the reference tokenizer call's max_length (text_encoder.py forward)
 
 
@@ -42,6 +54,10 @@ def config_dict(cfg):
     """A transformers BertConfig (or a dict) -> the plain dict this class takes; rejects what the kernels do not compute."""
     get = (lambda k: cfg[k]) if isinstance(cfg, dict) else (lambda k: getattr(cfg, k))
     out = {k: get(k) for k in CONFIG_KEYS}
+    for k in DROPOUT_KEYS:
+        v = cfg.get(k) if isinstance(cfg, dict) else getattr(cfg, k, None)
+        if v is not None:
+            out[k] = float(v)
     out["layer_norm_eps"] = float(out["layer_norm_eps"])
     for k in CONFIG_KEYS[:-1]:
         out[k] = int(out[k])
@@ -170,13 +186,17 @@ def attention_varlen(qkv, kv_len, heads):
 
 
 class TextEncoder(nn.Module):
-    """src/models/text_encoder.py:TextEncoder (same constructor arguments, same state-dict keys, same forward), frozen."""
+    """src/models/text_encoder.py:TextEncoder (same constructor arguments, same state-dict keys, same forward): frozen, or
+    with `trainable=True` fine-tuned under `finetune_strategy`."""
 
     def __init__(self, model_name='google-bert/bert-base-uncased', hidden_dim=768, finetune_strategy='minimal', *,
-                 compute_dtype=torch.float32, tokenizer=None, bert_config=None):
+                 compute_dtype=torch.float32, tokenizer=None, bert_config=None, trainable=False):
         super().__init__()
         if finetune_strategy not in FINETUNE_STRATEGIES:
             raise ValueError(f"Unknown finetune_strategy: {finetune_strategy}")
+        if trainable and finetune_strategy == "full":
+            raise _lib.PsgError("TextEncoder(trainable=True, finetune_strategy='full'): the embedding gradients (word / position / "
+                                "token-type tables and their LayerNorm) are not built; use 'none', 'minimal' or 'partial'")
         state = None
         if bert_config is None:                          # pretrained weights and tokenizer from the local HF cache
             tok, cfg, state = _from_pretrained(model_name)
@@ -185,6 +205,9 @@ class TextEncoder(nn.Module):
             cfg = config_dict(bert_config)
         self.model_name, self.finetune_strategy = model_name, finetune_strategy
         self.compute_dtype = compute_dtype
+        self.trainable = bool(trainable)
+        self.hidden_dropout_prob = float(cfg.get("hidden_dropout_prob", 0.1))
+        self.attention_probs_dropout_prob = float(cfg.get("attention_probs_dropout_prob", 0.1))
         self.tokenizer = tokenizer
         self.bert = _Bert(cfg)
         self.bert_hidden_size = cfg["hidden_size"]
@@ -194,16 +217,43 @@ class TextEncoder(nn.Module):
         if state is not None:
             own = self.bert.state_dict()
             self.bert.load_state_dict({k: v for k, v in state.items() if k in own}, strict=True)
+        self._cache = {}
+        self._apply_finetune_strategy()
+        self.eval()
+
+    def _apply_finetune_strategy(self):
+        """Set requires_grad as the reference's method of this name and its __init__ do (frozen class: everything off)."""
         for p in self.parameters():
             p.requires_grad = False
-        self.eval()
-        self._cache = {}
+        if not self.trainable:
+            return
+        n = len(self.bert.encoder.layer)
+        last = {"none": 0, "minimal": 2, "partial": 4}[self.finetune_strategy]
+        for i in range(max(0, n - last), n):
+            for p in self.bert.encoder.layer[i].parameters():
+                p.requires_grad = True
+        if last:
+            for p in self.bert.pooler.parameters():
+                p.requires_grad = True
+        for p in list(self.projection.parameters()) + list(self.layer_norm.parameters()):
+            p.requires_grad = True
+
+    def first_trainable_layer(self):
+        """Index of the first encoder layer with a trainable parameter (the layer count when BERT is frozen)."""
+        for i, lay in enumerate(self.bert.encoder.layer):
+            if any(p.requires_grad for p in lay.parameters()):
+                return i
+        return len(self.bert.encoder.layer)
+
+    def train(self, mode=True):
+        """Honoured when trainable; the frozen class stays in eval mode."""
+        return super().train(mode and self.trainable)
 
     @classmethod
-    def from_reference(cls, enc, compute_dtype=torch.float32):
+    def from_reference(cls, enc, compute_dtype=torch.float32, trainable=False):
         """A reference TextEncoder instance -> this class with its tokenizer, configuration and weights (copied)."""
         obj = cls(hidden_dim=enc.layer_norm.normalized_shape[0], finetune_strategy=getattr(enc, "finetune_strategy", "minimal"),
-                  compute_dtype=compute_dtype, tokenizer=enc.tokenizer, bert_config=config_dict(enc.bert.config))
+                  compute_dtype=compute_dtype, tokenizer=enc.tokenizer, bert_config=config_dict(enc.bert.config), trainable=trainable)
         own = obj.state_dict()
         obj.load_state_dict({k: v.detach().clone() for k, v in enc.state_dict().items() if k in own}, strict=True)
         return obj.to(next(enc.parameters()).device)
@@ -226,39 +276,103 @@ class TextEncoder(nn.Module):
         """Kernel launches of one encode_ids call."""
         return 1 + 7 * len(self.bert.encoder.layer) + (1 if isinstance(self.projection, nn.Linear) else 0) + 1
 
-    @torch.no_grad()
-    def encode_ids(self, input_ids, attention_mask, token_type_ids=None):
-        """Token ids [B, S] + attention mask [B, S] (right padding: ones then zeros) -> [B, S, hidden_dim] fp32."""
-        dev = self.layer_norm.weight.device
-        if dev.type != "cuda":
-            raise _lib.PsgError("TextEncoder (MI355X build) needs its parameters on the GPU; there is no CPU fallback")
+    def _qkv_packed(self, i, dt):
+        """(wf, bias, wd) of layer i for ops.qkv_linear: the inference path's packed forward weight + the data-gradient one."""
+        sa = self.bert.encoder.layer[i].attention.self
+        ps = [sa.query.weight, sa.key.weight, sa.value.weight, sa.query.bias, sa.key.bias, sa.value.bias]
+        return _prepared(self._cache, ("qkv_train", i, dt), ps, lambda: ops.prep_qkv(*ps, dt, True))
+
+    def _embed(self, ids, tt, B, S, dt, dev):
         c = self.bert.config
-        dt = self.compute_dtype
-        H, heads, I = c["hidden_size"], c["num_attention_heads"], c["intermediate_size"]
+        H = c["hidden_size"]
         lib = ops._lib_for(self.layer_norm.weight)
-        ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
-        B, S = ids.shape
-        kv_len = attention_mask.to(dev).sum(1, dtype=torch.int32).contiguous()      # stays on the device
-        tt = None if token_type_ids is None else token_type_ids.to(device=dev, dtype=torch.int64).contiguous()
         emb = self.bert.embeddings
         x = torch.empty((B * S, H), dtype=dt, device=dev)
         check(lib.psg_bert_embed_ln(ptr(ids), ptr(tt), ptr(emb.word_embeddings.weight), ptr(emb.position_embeddings.weight),
                                     ptr(emb.token_type_embeddings.weight), ptr(emb.LayerNorm.weight), ptr(emb.LayerNorm.bias), ptr(x), H,
                                     B, S, H, c["vocab_size"], c["max_position_embeddings"], c["type_vocab_size"], c["layer_norm_eps"],
                                     dtype_code(dt), stream_ptr()), "psg_bert_embed_ln")
-        eps = c["layer_norm_eps"]
-        for i, lay in enumerate(self.bert.encoder.layer):
-            (wqkv, bqkv), wo, w1, w2 = self._layer_weights(i, dt)
-            ao, it, ou = lay.attention.output, lay.intermediate.dense, lay.output
-            qkv = _linear(x, wqkv, bqkv, 3 * H)
-            ctx = attention_varlen(qkv.view(B, S, 3 * H), kv_len, heads).view(B * S, H)
-            h = layer_norm(_linear(ctx, wo, ao.dense.bias, H, residual=x), ao.LayerNorm.weight, ao.LayerNorm.bias, eps)
-            u = _linear(h, w1, it.bias, I, act=ACT_GELU)
-            x = layer_norm(_linear(u, w2, ou.dense.bias, H, residual=h), ou.LayerNorm.weight, ou.LayerNorm.bias, eps)
+        return x
+
+    def _layer_infer(self, i, x, kv_len, B, S):
+        """Encoder layer i on the inference launches (nothing kept for a backward)."""
+        c = self.bert.config
+        dt = self.compute_dtype
+        H, heads, I, eps = c["hidden_size"], c["num_attention_heads"], c["intermediate_size"], c["layer_norm_eps"]
+        lay = self.bert.encoder.layer[i]
+        (wqkv, bqkv), wo, w1, w2 = self._layer_weights(i, dt)
+        ao, it, ou = lay.attention.output, lay.intermediate.dense, lay.output
+        qkv = _linear(x, wqkv, bqkv, 3 * H)
+        ctx = attention_varlen(qkv.view(B, S, 3 * H), kv_len, heads).view(B * S, H)
+        h = layer_norm(_linear(ctx, wo, ao.dense.bias, H, residual=x), ao.LayerNorm.weight, ao.LayerNorm.bias, eps)
+        u = _linear(h, w1, it.bias, I, act=ACT_GELU)
+        return layer_norm(_linear(u, w2, ou.dense.bias, H, residual=h), ou.LayerNorm.weight, ou.LayerNorm.bias, eps)
+
+    def _layer_autograd(self, i, x, kv_len, B, S, ph, pa):
+        """Encoder layer i through the autograd nodes of `ops` (dropouts ph / pa drawn when > 0)."""
+        c = self.bert.config
+        dt = self.compute_dtype
+        H, heads, eps = c["hidden_size"], c["num_attention_heads"], c["layer_norm_eps"]
+        lay = self.bert.encoder.layer[i]
+        sa, ao, it, ou = lay.attention.self, lay.attention.output, lay.intermediate.dense, lay.output
+        s_attn = _SeedStream.next() if pa > 0 else 0
+        s_o, s_f = (_SeedStream.next(), _SeedStream.next()) if ph > 0 else (0, 0)
+        qkv = ops.qkv_linear(x, sa.query.weight, sa.query.bias, sa.key.weight, sa.key.bias, sa.value.weight, sa.value.bias,
+                             self._qkv_packed(i, dt))
+        ctx = ops.attention_self(qkv.view(B, S, 3 * H), heads, drop_p=pa, seed=s_attn, kv_len=kv_len).view(B * S, H)
+        # BertSelfOutput / BertOutput: LayerNorm(dropout(dense(.)) + input) - dropout and residual ride the GEMM epilogue, as on
+        # the inference launches (same bits in eval mode)
+        h = ops.layer_norm(ops.linear(ctx, ao.dense.weight, ao.dense.bias, residual=x, drop_p=ph, seed=s_o), ao.LayerNorm.weight,
+                           ao.LayerNorm.bias, eps)
+        u = ops.linear(h, it.weight, it.bias, act=ACT_GELU)
+        return ops.layer_norm(ops.linear(u, ou.dense.weight, ou.dense.bias, residual=h, drop_p=ph, seed=s_f), ou.LayerNorm.weight,
+                              ou.LayerNorm.bias, eps)
+
+    def encode_ids(self, input_ids, attention_mask, token_type_ids=None):
+        """Token ids [B, S] + attention mask [B, S] (right padding: ones then zeros) -> [B, S, hidden_dim] fp32."""
+        dev = self.layer_norm.weight.device
+        if dev.type != "cuda":
+            raise _lib.PsgError("TextEncoder (MI355X build) needs its parameters on the GPU; there is no CPU fallback")
+        ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
+        kv_len = attention_mask.to(dev).sum(1, dtype=torch.int32).contiguous()      # stays on the device
+        tt = None if token_type_ids is None else token_type_ids.to(device=dev, dtype=torch.int64).contiguous()
+        drop = self.trainable and self.training and (self.hidden_dropout_prob > 0 or self.attention_probs_dropout_prob > 0)
+        if not (self.trainable and (torch.is_grad_enabled() or drop)):
+            with torch.no_grad():
+                return self._encode_frozen(ids, kv_len, tt)
+        return self._encode_train(ids, kv_len, tt, drop)
+
+    def _encode_frozen(self, ids, kv_len, tt):
+        dev, dt = ids.device, self.compute_dtype
+        B, S = ids.shape
+        x = self._embed(ids, tt, B, S, dt, dev)
+        for i in range(len(self.bert.encoder.layer)):
+            x = self._layer_infer(i, x, kv_len, B, S)
         if isinstance(self.projection, nn.Linear):
             wp = _prepared(self._cache, ("proj", dt), [self.projection.weight], lambda: _prep(self.projection.weight[:, :, None, None], dt))
             x = _linear(x, wp, self.projection.bias, self.hidden_dim)
         y = layer_norm(x, self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps, out_dtype=torch.float32)
+        return y.view(B, S, self.hidden_dim)
+
+    def _encode_train(self, ids, kv_len, tt, drop):
+        dev, dt = ids.device, self.compute_dtype
+        B, S = ids.shape
+        ph, pa = (self.hidden_dropout_prob, self.attention_probs_dropout_prob) if drop else (0.0, 0.0)
+        first = self.first_trainable_layer()
+        with torch.no_grad():                       # the frozen prefix: no graph, no saved activation
+            x = self._embed(ids, tt, B, S, dt, dev)
+            if ph > 0:                              # BertEmbeddings' dropout, in place
+                lib = ops._lib_for(x)
+                H = x.shape[1]
+                check(lib.psg_dropout_apply(ptr(x), H, ptr(x), H, B * S, H, ph, _SeedStream.next(), 1.0 / (1.0 - ph), dtype_code(dt),
+                                            stream_ptr()), "psg_dropout_apply")
+            for i in range(first):
+                x = self._layer_autograd(i, x, kv_len, B, S, ph, pa) if drop else self._layer_infer(i, x, kv_len, B, S)
+        for i in range(first, len(self.bert.encoder.layer)):
+            x = self._layer_autograd(i, x, kv_len, B, S, ph, pa)
+        if isinstance(self.projection, nn.Linear):
+            x = ops.linear(x, self.projection.weight, self.projection.bias)
+        y = ops.layer_norm(x, self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps, out_dtype=torch.float32)
         return y.view(B, S, self.hidden_dim)
 
     def tokenize(self, text_list):
@@ -268,7 +382,6 @@ class TextEncoder(nn.Module):
         self.tokenizer.padding_side = "right"          # the key-length form of the mask assumes it (BERT's default)
         return self.tokenizer(list(text_list), return_tensors="pt", padding=True, truncation=True, max_length=MAX_LENGTH)
 
-    @torch.no_grad()
     def forward(self, text_list):
         inputs = self.tokenize(text_list)
         return self.encode_ids(inputs["input_ids"], inputs["attention_mask"], inputs.get("token_type_ids"))

