@@ -116,6 +116,15 @@ int psg_smooth_l1_f32(const float* pred, const float* target, float* grad, float
                       psg_stream_t stream);
 int64_t psg_reduce_workspace_bytes(void);
 
+/* Stage 3's reconstruction loss and its gradient in one pass - compute_generation_loss, final_trainer.py:425-440
+ * (F.l1_loss + 0.1 * F.mse_loss, both means over all n elements):
+ *   out3 (3 fp32 device scalars) = { w_l1 * mean|d| + w_mse * mean d^2, mean|d|, mean d^2 },  d = pred - target
+ *   grad (may be NULL) = (w_l1 * sign(d) + 2 * w_mse * d) / n
+ * Deterministic two-stage reduction.  ws: >= psg_recon_loss_workspace_bytes() bytes. */
+int psg_recon_loss_f32(const float* pred, const float* target, float* grad, float* out3, int64_t n, float w_l1,
+                       float w_mse, void* ws, psg_stream_t stream);
+int64_t psg_recon_loss_workspace_bytes(void);
+
 /* ---------------------------------------------------------------------------
  * Layout / small ops at the boundary (NCHW fp32 <-> channels-last dtype)
  * ------------------------------------------------------------------------- */
@@ -340,6 +349,23 @@ int psg_attn_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const v
                  float* delta, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv,
                  int B, int heads, int L, int S, int d, float scale, float drop_p, uint64_t seed,
                  int dtype, psg_stream_t stream);
+
+/* psg_attn_bwd for FEW keys and VERY MANY queries: the backward of the VAE decoder's text cross-attention
+ * (src/models/vae_decoder.py:49-65: S = 32 tokens against L = 27^2 ... 215^2 pixels, head_dim 64 ... 4), which stage 3
+ * differentiates to train the text encoder through the frozen decoder (final_trainer.py:215-236, :444-485).
+ * Arguments as psg_attn_bwd (same layouts and strides, fp32 and bf16; q, k, v, o, dout and dq start on a 4-element
+ * boundary).  head_dim is one of 4, 8, 16, 32, 64, 1 <= S <= 256, any L >= 1; drop_p must be 0 (PSG_ERR_ARG otherwise).
+ * The grid is over query slabs x (b, head): each workgroup stages K / V once, recomputes P from lse for its slab, writes
+ * its dq rows and one fp32 partial [2][S][d] of dk / dv into ws; a second kernel sums the partials in slab order.  No
+ * atomics: the same inputs give the same bits.  ws: 16-byte aligned, at least
+ * psg_attn_bwd_longq_workspace_bytes(B, heads, L, S, d) bytes (PSG_ERR_WORKSPACE otherwise).  Its own entry: psg_attn_bwd
+ * never routes here, and psg_attn_path_counts does not count it. */
+int psg_attn_bwd_longq(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                       const void* o, int64_t ldo, const void* dout, int64_t lddo, const float* lse,
+                       float* delta, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv, int64_t lddv,
+                       int B, int heads, int L, int S, int d, float scale, float drop_p, uint64_t seed,
+                       int dtype, void* ws, int64_t ws_bytes, psg_stream_t stream);
+int64_t psg_attn_bwd_longq_workspace_bytes(int B, int heads, int L, int S, int d);
 
 /* psg_attn_bwd with psg_attn_fwd_varlen_train's key lengths: key tiles at or past kv_len[b] are neither staged nor
  * computed, and dk / dv rows kv_len[b] <= s < S are written as zeros (a Linear's weight gradient sums over every row).

@@ -15,8 +15,10 @@ from .trainer import DiffusionStepper, DiffusionTrainer, ImprovedDiffusionTraine
 from .inference import LatentGenerator, LinearNoiseScheduler, gradio_ddpm_sample
 from .vae import PokemonVAE, VAEDecoder, VAEEncoder
 from .text_encoder import TextEncoder
+from .final import FinalPokemonGenerator, FinalStepper
 
 __all__ = ["UNet", "UNetBlock", "ResBlock", "CrossAttentionBlock", "TimestepEmbedding", "NoiseScheduler",
            "ImprovedDiffusionTrainer", "DiffusionTrainer", "DiffusionStepper", "FusedAdamW", "GradArena", "ParamArena",
-           "BucketedAllReduce", "LatentGenerator", "LinearNoiseScheduler", "gradio_ddpm_sample", "PokemonVAE", "VAEEncoder", "VAEDecoder", "TextEncoder", "PsgError", "LIB_PATH"]
+           "BucketedAllReduce", "LatentGenerator", "LinearNoiseScheduler", "gradio_ddpm_sample", "PokemonVAE", "VAEEncoder", "VAEDecoder", "TextEncoder",
+           "FinalPokemonGenerator", "FinalStepper", "PsgError", "LIB_PATH"]
 __version__ = "0.1.0"

@@ -103,6 +103,11 @@ SIGNATURES = {
     "psg_attn_set_paths": (c_int, [c_int]),
     "psg_attn_bwd": (c_int, [c_void_p, c_int64] * 5 + [c_void_p, c_void_p] + [c_void_p, c_int64] * 3
                      + [c_int] * 5 + [c_float, c_float, c_uint64, c_int, c_void_p]),
+    "psg_attn_bwd_longq": (c_int, [c_void_p, c_int64] * 5 + [c_void_p, c_void_p] + [c_void_p, c_int64] * 3
+                           + [c_int] * 5 + [c_float, c_float, c_uint64, c_int, c_void_p, c_int64, c_void_p]),
+    "psg_attn_bwd_longq_workspace_bytes": (c_int64, [c_int] * 5),
+    "psg_recon_loss_f32": (c_int, [c_void_p] * 4 + [c_int64, c_float, c_float, c_void_p, c_void_p]),
+    "psg_recon_loss_workspace_bytes": (c_int64, []),
     "psg_layernorm": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_float,
                               c_int, c_int, c_void_p]),
     "psg_layernorm_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,

@@ -44,4 +44,7 @@ int attn_f32_init_attrs();
 template <bool VARLEN> int attn_f32_fwd(const AttnArgs<float>& p, hipStream_t s);
 template <bool VARLEN> int attn_f32_bwd(const AttnArgs<float>& p, hipStream_t s);
 
+// attention_longq.hip (psg_attn_bwd_longq: few keys, very many queries); its own entry point, never chosen by the routing above
+int attn_longq_init_attrs();
+
 }  // namespace psg

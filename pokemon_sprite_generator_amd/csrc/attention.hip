@@ -481,6 +481,7 @@ extern "C" {
 int psg_attn_init_attrs(void) {
     { int rc = attn_mfma_init_attrs(); if (rc) return rc; }
     { int rc = attn_f32_init_attrs(); if (rc) return rc; }
+    { int rc = attn_longq_init_attrs(); if (rc) return rc; }
     { int rc = valu_init_attrs<float>(); if (rc) return rc; }
     return valu_init_attrs<bf16_t>();
 }

@@ -136,6 +136,36 @@ __global__ void smooth_l1_kernel(const float* __restrict__ pred, const float* __
     if (bad && nan_flag) atomicOr(nan_flag, PSG_FLAG_PRED_BAD);
 }
 
+// L1 + MSE in one pass: partial[block] = sum |d|, partial[RED_BLOCKS + block] = sum d^2
+__global__ void recon_loss_kernel(const float* __restrict__ pred, const float* __restrict__ target, float* __restrict__ grad,
+                                  float* __restrict__ partial, float w_l1, float w_mse, int64_t n) {
+    __shared__ float red[16];
+    float a1 = 0.f, a2 = 0.f;
+    const float inv_n = 1.0f / (float)n;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float d = pred[i] - target[i];
+        a1 += fabsf(d);
+        a2 += d * d;
+        if (grad) grad[i] = (w_l1 * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) + 2.0f * w_mse * d) * inv_n;
+    }
+    const float s1 = block_sum(a1, red);
+    const float s2 = block_sum(a2, red);
+    if (threadIdx.x == 0) { partial[blockIdx.x] = s1; partial[RED_BLOCKS + blockIdx.x] = s2; }
+}
+
+// one block sums the `count` partials of each term in a fixed order: out3 = {w_l1 * l1 + w_mse * mse, l1, mse}
+__global__ void recon_finish_kernel(const float* __restrict__ partial, int count, float* out3, float w_l1, float w_mse, float inv_n) {
+    __shared__ float red[16];
+    float a1 = 0.f, a2 = 0.f;
+    for (int i = threadIdx.x; i < count; i += blockDim.x) { a1 += partial[i]; a2 += partial[RED_BLOCKS + i]; }
+    const float s1 = block_sum(a1, red);
+    const float s2 = block_sum(a2, red);
+    if (threadIdx.x == 0) {
+        const float l1 = s1 * inv_n, mse = s2 * inv_n;
+        out3[0] = w_l1 * l1 + w_mse * mse; out3[1] = l1; out3[2] = mse;
+    }
+}
+
 __global__ void sumsq_kernel(const float* __restrict__ g, float* __restrict__ partial, int64_t n) {
     __shared__ float red[16];
     float acc = 0.f;
@@ -847,6 +877,20 @@ int psg_smooth_l1_f32(const float* pred, const float* target, float* grad, float
     hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws, g, loss_out,
                        1.0f / (float)n, 0, nan_flag);
     PSG_LAUNCH_CHECK("smooth_l1_finish");
+    return PSG_OK;
+}
+
+int64_t psg_recon_loss_workspace_bytes(void) { return (int64_t)2 * RED_BLOCKS * sizeof(float); }
+
+int psg_recon_loss_f32(const float* pred, const float* target, float* grad, float* out3, int64_t n, float w_l1, float w_mse, void* ws,
+                       psg_stream_t stream) {
+    PSG_REQUIRE(pred && target && out3 && ws, PSG_ERR_ARG, "recon_loss: null pointer");
+    PSG_REQUIRE(n > 0, PSG_ERR_SHAPE, "recon_loss: n=%ld", (long)n);
+    const int g = grid_for(n, RED_THREADS, RED_BLOCKS);
+    hipLaunchKernelGGL(recon_loss_kernel, dim3(g), dim3(RED_THREADS), 0, (hipStream_t)stream, pred, target, grad, (float*)ws, w_l1, w_mse, n);
+    PSG_LAUNCH_CHECK("recon_loss");
+    hipLaunchKernelGGL(recon_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws, g, out3, w_l1, w_mse, 1.0f / (float)n);
+    PSG_LAUNCH_CHECK("recon_loss_finish");
     return PSG_OK;
 }
 

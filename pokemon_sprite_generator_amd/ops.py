@@ -15,8 +15,8 @@ import torch
 from . import _lib
 from ._lib import ACT_GELU, ACT_NONE, ACT_SILU, ConvDesc, WgradDesc, check, dtype_code, ptr, stream_ptr
 
-__all__ = ["conv2d", "linear", "group_norm", "group_norm_split", "attention_self", "attention_cross", "cross_in_proj", "upsample_bilinear",
-           "nchw_to_nhwc", "nhwc_to_nchw", "text_pool", "timestep_sinusoid", "WeightCache", "ACT_NONE", "ACT_SILU", "ACT_GELU"]
+__all__ = ["conv2d", "linear", "group_norm", "group_norm_split", "attention_self", "attention_cross", "attention_cross_longq",
+           "cross_in_proj", "upsample_bilinear", "nchw_to_nhwc", "nchw_to_nhwc_grad", "nhwc_to_nchw", "image_out", "recon_loss", "text_pool", "timestep_sinusoid", "WeightCache", "ACT_NONE", "ACT_SILU", "ACT_GELU"]
 
 
 def _lib_for(t):
@@ -1222,6 +1222,85 @@ def attention_cross(q, kv, heads, drop_p=0.0, seed=0):
     return _AttnFn.apply(q, kv, heads, drop_p, seed)
 
 
+class _AttnLongQFn(torch.autograd.Function):
+    """Cross-attention of very many queries over few keys (the VAE decoder's text attention): q [B,L,E], kv [B,S,2E], no
+    dropout.  Forward: psg_attn_fwd, the launch of `attention_cross`; backward: psg_attn_bwd_longq."""
+
+    @staticmethod
+    def forward(ctx, q_src, kv_src, heads):
+        lib = _lib_for(q_src)
+        dtype = q_src.dtype
+        qr, ldq = _rows(q_src)
+        kvr, ldk = _rows(kv_src)
+        B, L, E = q_src.shape
+        S = kv_src.shape[1]
+        d = E // heads
+        scale = float(d) ** -0.5
+        esz = qr.element_size()
+        o = torch.empty((B, L, E), dtype=dtype, device=q_src.device)
+        lse = torch.empty((B, heads, L), dtype=torch.float32, device=q_src.device)
+        check(lib.psg_attn_fwd(qr.data_ptr(), ldq, kvr.data_ptr(), ldk, kvr.data_ptr() + E * esz, ldk, ptr(o), E, ptr(lse), B, heads, L, S, d,
+                               scale, 0.0, 0, dtype_code(dtype), stream_ptr()), "psg_attn_fwd")
+        ctx.save_for_backward(qr, kvr, o, lse)
+        ctx.meta = (B, L, S, E, heads, d, scale, ldq, ldk)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qr, kvr, o, lse = ctx.saved_tensors
+        B, L, S, E, heads, d, scale, ldq, ldk = ctx.meta
+        lib = _lib_for(do)
+        dtype = do.dtype
+        dor, lddo = _rows(do)
+        esz = qr.element_size()
+        delta = torch.empty((B, heads, L), dtype=torch.float32, device=do.device)
+        dq = torch.empty((B, L, E), dtype=dtype, device=do.device)
+        dkv = torch.empty((B, S, 2 * E), dtype=dtype, device=do.device)
+        need = lib.psg_attn_bwd_longq_workspace_bytes(B, heads, L, S, d)
+        if need < 0:
+            check(-1, "psg_attn_bwd_longq_workspace_bytes")
+        ws = _lib.workspace(need, do.device)
+        check(lib.psg_attn_bwd_longq(qr.data_ptr(), ldq, kvr.data_ptr(), ldk, kvr.data_ptr() + E * esz, ldk, ptr(o), E, ptr(dor), lddo, ptr(lse),
+                                     ptr(delta), dq.data_ptr(), E, dkv.data_ptr(), 2 * E, dkv.data_ptr() + E * esz, 2 * E, B, heads, L, S, d,
+                                     scale, 0.0, 0, dtype_code(dtype), ptr(ws), ws.numel(), stream_ptr()), "psg_attn_bwd_longq")
+        return dq, dkv, None
+
+
+def attention_cross_longq(q, kv, heads):
+    """`attention_cross` (no dropout) whose backward is the long-query kernel pair: vae_decoder.py:49-65 under stage 3."""
+    return _AttnLongQFn.apply(q, kv, heads)
+
+
+class _ReconLossFn(torch.autograd.Function):
+    """(w_l1 * L1 + w_mse * MSE, L1, MSE) of fp32 tensors, each a mean over all elements: psg_recon_loss_f32.  The gradient is
+    produced by the forward's own pass and belongs to the first of the three results."""
+
+    @staticmethod
+    def forward(ctx, pred, target, w_l1, w_mse):
+        lib = _lib_for(pred)
+        p, t = pred.detach().contiguous().float(), target.detach().to(pred.device).contiguous().float()
+        if p.shape != t.shape:
+            raise _lib.PsgError(f"recon_loss: shapes {tuple(p.shape)} and {tuple(t.shape)} differ")
+        want = ctx.needs_input_grad[0]
+        grad = torch.empty_like(p) if want else None
+        out3 = torch.empty(3, dtype=torch.float32, device=p.device)
+        ws = _lib.workspace(lib.psg_recon_loss_workspace_bytes(), p.device)
+        check(lib.psg_recon_loss_f32(ptr(p), ptr(t), ptr(grad), ptr(out3), p.numel(), float(w_l1), float(w_mse), ptr(ws), stream_ptr()),
+              "psg_recon_loss_f32")
+        ctx.grad, ctx.shape = grad, tuple(pred.shape)
+        return out3
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.grad.view(ctx.shape) * g[0], None, None, None
+
+
+def recon_loss(pred, target, w_l1=1.0, w_mse=0.1):
+    """final_trainer.py:425-440: (l1 + 0.1 * mse, l1, mse) as fp32 device scalars; one pass produces loss and gradient."""
+    out3 = _ReconLossFn.apply(pred, target, w_l1, w_mse)
+    return out3[0], out3[1].detach(), out3[2].detach()
+
+
 # ---------------------------------------------------------------------------
 # small ops
 # ---------------------------------------------------------------------------
@@ -1287,6 +1366,49 @@ def nchw_to_nhwc(x, dtype):
     y = torch.empty((B, H, W, Cc), dtype=dtype, device=x.device)
     check(lib.psg_nchw_to_nhwc(ptr(xc), ptr(y), Cc, B, Cc, H * W, dtype_code(dtype), stream_ptr()), "psg_nchw_to_nhwc")
     return y
+
+
+class _ToNHWCFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, dtype):
+        return nchw_to_nhwc(x, dtype)
+
+    @staticmethod
+    def backward(ctx, dy):
+        with torch.no_grad():
+            return nhwc_to_nchw(dy), None
+
+
+def nchw_to_nhwc_grad(x, dtype):
+    """`nchw_to_nhwc` with the gradient carried back to the fp32 NCHW input (the VAE decoder's latent)."""
+    return _ToNHWCFn.apply(x, dtype)
+
+
+class _ImageOutFn(torch.autograd.Function):
+    """The first `cout` of the C columns of y [B,H,W,C] -> fp32 [B,cout,H,W] (the decoder's image: 3 channels computed in padded
+    columns); backward writes zeros into the padding columns."""
+
+    @staticmethod
+    def forward(ctx, y, cout):
+        lib = _lib_for(y)
+        B, H, W, Cc = y.shape
+        img = torch.empty((B, cout, H, W), dtype=torch.float32, device=y.device)
+        check(lib.psg_nhwc_to_nchw(ptr(y), Cc, ptr(img), B, cout, H * W, dtype_code(y.dtype), stream_ptr()), "psg_nhwc_to_nchw")
+        ctx.meta = (B, H, W, Cc, cout, y.dtype)
+        return img
+
+    @staticmethod
+    def backward(ctx, dimg):
+        B, H, W, Cc, cout, dtype = ctx.meta
+        lib = _lib_for(dimg)
+        dc = dimg.contiguous().float()
+        dy = torch.zeros((B, H, W, Cc), dtype=dtype, device=dimg.device)
+        check(lib.psg_nchw_to_nhwc(ptr(dc), ptr(dy), Cc, B, cout, H * W, dtype_code(dtype), stream_ptr()), "psg_nchw_to_nhwc")
+        return dy, None
+
+
+def image_out(y, cout):
+    return _ImageOutFn.apply(y.contiguous(), cout)
 
 
 def text_pool(text, dtype):

@@ -2,8 +2,12 @@
 
 The VAE sits either side of the U-Net path: stage 2 encodes every image batch with the FROZEN encoder before the train
 step (improved_diffusion_trainer.py:198-208,357-358) and decodes sampled latents for monitoring (:598); stage 3 and the
-demo decode with it.  It is inference-only here (`torch.no_grad()` inside; parameters are containers with the
-reference's names and shapes, so `load_state_dict` takes a stage-1 checkpoint's 'vae_state_dict' halves unchanged).
+demo decode with it.  Its parameters are never trained here (they are containers with the reference's names and shapes, so
+`load_state_dict` takes a stage-1 checkpoint's 'vae_state_dict' halves unchanged), and the encoder runs under
+`torch.no_grad()`.  The DECODER is differentiable with respect to its inputs: stage 3 trains the text encoder through it
+(final_trainer.py:215-236), so when grad mode is on and `text_emb` or `latent` requires grad, `VAEDecoder.forward` runs the
+autograd nodes of `ops` (data gradients only; the cross-attention backward is psg_attn_bwd_longq).  Every other call runs the
+inference launches, unchanged.
 
 Same classes / constructor and forward signatures as the reference: `ResNetBlock`, `CrossAttentionBlock`, `VAEEncoder`,
 `VAEDecoder`, `PokemonVAE`.  Everything runs channels-last in `compute_dtype` on the kernels of the U-Net path:
@@ -29,6 +33,18 @@ def _prepared(cache, key, param_list, build):
         ent = (stamp, build())
         cache[key] = ent
     return ent[1]
+
+
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _require_frozen(module):
+    """The differentiable path produces data gradients only: a trainable VAE parameter would silently get none."""
+    for n, p in module.named_parameters():
+        if p.requires_grad:
+            raise _lib.PsgError(f"{type(module).__name__}: parameter {n} has requires_grad=True, but VAE weight gradients (stage 1, "
+                                "and the joint phase of stage 3) are not built; freeze the VAE")
 
 
 def _conv(x, wf, bias, Cin, Cout, ks, stride, pad, act=ACT_NONE, residual=None, out_dtype=None):
@@ -89,10 +105,21 @@ class ResNetBlock(nn.Module):
             skip = x
         return _conv(h, w2, self.conv2.bias, cout, cout, 3, 1, 1, residual=skip)
 
-    @torch.no_grad()
+    def nhwc_grad(self, x):
+        """`nhwc` on the autograd nodes of `ops` (frozen weights: data gradients only)."""
+        h, xs = ops.group_norm_split(x, self.norm1.weight, self.norm1.bias, self.norm1.num_groups, self.norm1.eps, silu=True)
+        h = ops.conv2d(h, self.conv1.weight, self.conv1.bias)
+        h = ops.group_norm(h, self.norm2.weight, self.norm2.bias, self.norm2.num_groups, self.norm2.eps, silu=True)
+        skip = ops.conv2d(xs, self.shortcut.weight, self.shortcut.bias) if isinstance(self.shortcut, nn.Conv2d) else xs
+        return ops.conv2d(h, self.conv2.weight, self.conv2.bias, residual=skip)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         dt = getattr(self, "compute_dtype", torch.float32)
-        return ops.nhwc_to_nchw(self.nhwc(ops.nchw_to_nhwc(x, dt)))
+        if _wants_grad(x):
+            _require_frozen(self)
+            return ops.nhwc_to_nchw(self.nhwc_grad(ops.nchw_to_nhwc_grad(x, dt)))
+        with torch.no_grad():
+            return ops.nhwc_to_nchw(self.nhwc(ops.nchw_to_nhwc(x, dt)))
 
 
 class CrossAttentionBlock(nn.Module):
@@ -130,10 +157,27 @@ class CrossAttentionBlock(nn.Module):
         y = _conv(o.reshape(B, H, W, C), wp, self.proj.bias, C, C, 1, 1, 0, residual=x)
         return y
 
-    @torch.no_grad()
+    def nhwc_grad(self, x, text):
+        """`nhwc` on the autograd nodes of `ops`.  The [B,S,C] -> [C][S] reinterpretation is a reshape + transpose of views,
+        differentiated by autograd as such; the attention core's backward is psg_attn_bwd_longq."""
+        B, H, W, C = x.shape
+        S = text.shape[1]
+        xn, xs = ops.group_norm_split(x, self.norm.weight, self.norm.bias, self.norm.num_groups, self.norm.eps)
+        q = ops.conv2d(xn, self.q.weight, self.q.bias).reshape(B, H * W, C)
+        k = ops.linear(text, self.k.weight, self.k.bias)
+        v = ops.linear(text, self.v.weight, self.v.bias)
+        kv = torch.cat([k.reshape(B, C, S).transpose(1, 2), v.reshape(B, C, S).transpose(1, 2)], dim=-1).contiguous()
+        o = ops.attention_cross_longq(q, kv, self.num_heads)
+        return ops.conv2d(o.reshape(B, H, W, C), self.proj.weight, self.proj.bias, residual=xs)
+
     def forward(self, x: torch.Tensor, text_emb: torch.Tensor) -> torch.Tensor:
         dt = getattr(self, "compute_dtype", torch.float32)
-        return ops.nhwc_to_nchw(self.nhwc(ops.nchw_to_nhwc(x, dt), text_emb.to(dt)))
+        if _wants_grad(x, text_emb):
+            _require_frozen(self)
+            xin = ops.nchw_to_nhwc_grad(x, dt) if x.requires_grad else ops.nchw_to_nhwc(x, dt)
+            return ops.nhwc_to_nchw(self.nhwc_grad(xin, text_emb.to(dt).contiguous()))
+        with torch.no_grad():
+            return ops.nhwc_to_nchw(self.nhwc(ops.nchw_to_nhwc(x, dt), text_emb.to(dt)))
 
 
 class VAEEncoder(nn.Module):
@@ -209,10 +253,40 @@ class VAEDecoder(nn.Module):
         self.compute_dtype = compute_dtype
         self._cache = {}
 
-    @torch.no_grad()
     def forward(self, latent: torch.Tensor, text_emb: torch.Tensor) -> torch.Tensor:
         if not latent.is_cuda:
             raise _lib.PsgError("VAEDecoder (MI355X build) needs GPU tensors; there is no CPU fallback")
+        if _wants_grad(latent, text_emb):
+            return self._forward_grad(latent, text_emb)
+        with torch.no_grad():
+            return self._forward_infer(latent, text_emb)
+
+    def _forward_grad(self, latent, text_emb):
+        """The decoder on the autograd nodes of `ops`: gradients reach `text_emb` and `latent`, never a VAE parameter."""
+        _require_frozen(self)
+        dt = self.compute_dtype
+        text = text_emb.to(device=latent.device, dtype=dt).contiguous()
+        lat = ops.nchw_to_nhwc_grad(latent, dt) if latent.requires_grad else ops.nchw_to_nhwc(latent, dt)
+        x = ops.conv2d(lat, self.latent_proj.weight, self.latent_proj.bias)
+        for i in range(1, 6):
+            x = getattr(self, f"block{i}_resnet1").nhwc_grad(x)
+            x = getattr(self, f"block{i}_attn").nhwc_grad(x, text)
+            x = getattr(self, f"block{i}_resnet2").nhwc_grad(x)
+            up = getattr(self, f"block{i}_upsample", None)
+            if up is not None:
+                size = up.size if up.size is not None else (int(x.shape[1] * up.scale_factor), int(x.shape[2] * up.scale_factor))
+                x = ops.upsample_bilinear(x, size)
+        gn, conv = self.final_conv[0], self.final_conv[2]
+        x = ops.group_norm(x, gn.weight, gn.bias, gn.num_groups, gn.eps, silu=True)
+        cout = conv.out_channels
+        opad = (-cout) % 8          # 3 image channels in 8 columns (zero rows of weight): the data gradient gathers 16-byte chunks of dY
+        w8, b8 = _prepared(self._cache, ("fc_grad",), [conv.weight, conv.bias],
+                           lambda: (torch.nn.functional.pad(conv.weight.detach().float(), (0, 0, 0, 0, 0, 0, 0, opad)).contiguous(),
+                                    torch.nn.functional.pad(conv.bias.detach().float(), (0, opad)).contiguous()))
+        y = ops.conv2d(x, w8, b8, act=ACT_TANH)
+        return ops.image_out(y, cout)               # d tanh rides the conv node's epilogue backward; the padding columns get zeros
+
+    def _forward_infer(self, latent, text_emb):
         dt = self.compute_dtype
         text = text_emb.detach().to(device=latent.device, dtype=dt).contiguous()
         wl = _prepared(self._cache, ("lp", dt), [self.latent_proj.weight], lambda: _prep(self.latent_proj.weight, dt))
