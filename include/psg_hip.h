@@ -188,6 +188,13 @@ int psg_groupnorm_bwd_res(const void* dy, int64_t lddy, const void* x, int64_t l
                           int64_t lddres, void* dx, int64_t lddx, float* dgamma, float* dbeta, int B, int HW,
                           int C, int G, int silu, int accumulate, int dtype, void* ws, psg_stream_t stream);
 int64_t psg_groupnorm_bwd_workspace_bytes(int B, int C);
+/* What a forward (backward = 0) or backward launch of this shape runs, from the launches' own routing functions and with
+ * their shape checks and error codes; host only, no device is touched.  has_dres: a backward launch with dres != NULL.
+ * out[12] = fused (1: one register-resident kernel, 0: the split kernels), N (channels per chunk), R (chunks per lane of
+ * the slab plan, 0 if none; fused = 0 with R != 0: a plan was found but its LDS did not fit), grid, threads, lds (bytes,
+ * the fused or the first split kernel), lds2 (second split kernel), slabC, nslab, PP (pixel lanes), NS (pixel splits),
+ * pps (pixels per split).  slabC / nslab are 0 on the split route, NS / pps / lds2 on the fused one. */
+int psg_groupnorm_route(int backward, int dtype, int B, int HW, int C, int G, int has_dres, int32_t* out);
 
 /* ---------------------------------------------------------------------------
  * Implicit-GEMM convolution / linear on MFMA — nn.Conv2d 3x3 s1/s2 p1 and 1x1

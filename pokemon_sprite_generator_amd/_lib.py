@@ -76,6 +76,7 @@ SIGNATURES = {
     "psg_groupnorm_bwd_res": (c_int, [c_void_p, c_int64, c_void_p, c_int64] + [c_void_p] * 4 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]
                               + [c_int] * 7 + [c_void_p, c_void_p]),
     "psg_groupnorm_bwd_workspace_bytes": (c_int64, [c_int, c_int]),
+    "psg_groupnorm_route": (c_int, [c_int] * 7 + [c_void_p]),
     "psg_conv_fwd": (c_int, [C.POINTER(ConvDesc), c_void_p]),
     "psg_conv_fwd_workspace_bytes": (c_int64, [C.POINTER(ConvDesc)]),
     "psg_conv_set_pw": (c_int, [c_int]),

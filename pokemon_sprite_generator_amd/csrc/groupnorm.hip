@@ -20,7 +20,7 @@
 // 16-byte channel chunk and walks pixels), so loads/stores are fully coalesced for every
 // channels-per-group value (10, 20, 40, 80: a chunk may straddle two groups - handled per
 // element).  Work is split over (sample, pixel-split) workgroups to fill the chip:
-//   forward : stats kernel -> per-(b, split, group) partial (sum, sum of squares)
+//   forward : stats kernel -> per-(b, split, group) partial (sum, sum of squares; lane sums fp32, added in double)
 //             apply kernel -> combines the partials (double), writes mean/rstd, normalises
 //   backward: reduce kernel -> per-(b, split, channel) partial (sum dz*xhat, sum dz)
 //             apply kernel  -> combines them per sample, forms the two group sums, writes dx
@@ -105,11 +105,13 @@ __global__ void gn_stats_kernel(const GnArgs p) {
     __syncthreads();
     if (threadIdx.x < p.G) {
         const int g = threadIdx.x;
-        float a0 = 0.f, a1 = 0.f;
+        // in double: PP x Cg dependent fp32 additions were the largest error of E[x^2] - mean^2, which the variance of a
+        // group far off centre (|mean| >> sigma) magnifies by E[x^2] / var - into rstd and, through it, into every y
+        double a0 = 0.0, a1 = 0.0;
         for (int l = 0; l < p.PP; ++l)
-            for (int ch = g * p.Cg; ch < (g + 1) * p.Cg; ++ch) { a0 += sm[((int64_t)l * p.C + ch) * 2]; a1 += sm[((int64_t)l * p.C + ch) * 2 + 1]; }
+            for (int ch = g * p.Cg; ch < (g + 1) * p.Cg; ++ch) { a0 += (double)sm[((int64_t)l * p.C + ch) * 2]; a1 += (double)sm[((int64_t)l * p.C + ch) * 2 + 1]; }
         float* o = p.ws + ((int64_t)blockIdx.x * p.G + g) * 2;
-        o[0] = a0; o[1] = a1;
+        o[0] = (float)a0; o[1] = (float)a1;
     }
 }
 
@@ -759,6 +761,20 @@ extern "C" {
 
 int64_t psg_groupnorm_fwd_workspace_bytes(int B, int G) { return (int64_t)B * GN_MAXSPLIT * G * 2 * sizeof(float); }
 int64_t psg_groupnorm_bwd_workspace_bytes(int B, int C) { return (int64_t)B * (GN_MAXSPLIT + 1) * C * 2 * sizeof(float); }
+
+int psg_groupnorm_route(int backward, int dtype, int B, int HW, int C, int G, int has_dres, int32_t* out) {
+    PSG_REQUIRE(out, PSG_ERR_ARG, "groupnorm_route: null pointer");
+    PSG_REQUIRE(dtype == PSG_F32 || dtype == PSG_BF16, PSG_ERR_DTYPE, "groupnorm_route: dtype %d", dtype);
+    const int N = dtype == PSG_BF16 ? 8 : 4;      // elements per 16-byte chunk
+    { const int rc = gn_check_shape(N, B, HW, C, G); if (rc) return rc; }
+    const GnRoute rt = backward ? gn_route_bwd(dtype, B, HW, C, G, has_dres != 0) : gn_route_fwd(dtype, B, HW, C, G);
+    const GnArgs& p = rt.p;
+    // (R stays that of a slab plan whose LDS did not fit: fused == 0 with R != 0 is that fall-back to the split kernels)
+    const int32_t v[12] = {rt.fused, rt.fused ? rt.N : N, rt.R, rt.grid, rt.threads, (int32_t)rt.lds, (int32_t)rt.lds2,
+                           p.slabC, p.nslab, p.PP, p.NS, p.pps};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return PSG_OK;
+}
 
 int psg_groupnorm_fwd(const void* x, int64_t ldx, void* y, int64_t ldy, const float* gamma, const float* beta,
                       float* mean, float* rstd, int B, int HW, int C, int G, float eps, int silu, int dtype, void* ws,
