@@ -350,6 +350,21 @@ int psg_attn_path_counts(int64_t* mfma, int64_t* valu, int64_t* mfma_f32);
  * the exact-fp32 MFMA kernels; a cleared bit sends those launches to the VALU kernels (default 3).  The parity tests pin
  * each family against the same reference this way (a process-wide switch: not for concurrent use). */
 int psg_attn_set_paths(int allow_mask);
+/* Diagnostic, host only: what a call of this shape launches.  Initialises no device, launches nothing and leaves the
+ * counters of psg_attn_path_counts alone; honours psg_attn_set_paths and PSG_ATTN_F32_MFMA.  pass: 0 psg_attn_fwd,
+ * 1 psg_attn_fwd_varlen, 2 psg_attn_bwd, 3 psg_attn_fwd_varlen_train, 4 psg_attn_bwd_varlen.  ld_grads: the OR of the four
+ * gradient row strides lddo | lddq | lddk | lddv (ignored for a forward); ptrs_aligned16: whether every pointer of the call
+ * is 16-byte aligned (when not, the call runs on the VALU kernels).  Applies the shape, stride and dtype checks of the
+ * pass's own entry point and returns its error codes (the gradient strides are checked on their OR).  out: int32
+ * [PSG_ATTN_ROUTE_FIELDS] =
+ *   family (0 bf16 MFMA, 1 VALU, 2 fp32 MFMA), ND (16-column slices of head_dim), waves per workgroup of the forward / dQ
+ *   kernel, KW, QW (key-tile x query-group waves of the MFMA dK/dV kernels; 0 on the VALU kernels), waves of the dK/dV
+ *   launch, QW reduced by the partial-sum fit, waves reduced by the private-tile fit, NH (passes over head_dim), KV_REG
+ *   (K/V operands in registers), dynamic LDS bytes of the forward, dQ and dK/dV launches, grid x, y of the forward, dQ and
+ *   dK/dV launches, VARLEN.  A forward pass leaves the backward fields 0 and a backward pass the forward fields. */
+#define PSG_ATTN_ROUTE_FIELDS 20
+int psg_attn_route(int pass, int dtype, int B, int heads, int L, int S, int d, int64_t ldq, int64_t ldk, int64_t ldv,
+                   int64_t ldo, int64_t ld_grads, int ptrs_aligned16, int32_t* out);
 /* delta: fp32 [B, heads, L] scratch.  dq/dk/dv have the strides of q/k/v. */
 int psg_attn_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                  const void* o, int64_t ldo, const void* dout, int64_t lddo, const float* lse,

@@ -31,15 +31,30 @@ inline int for_each_nd(std::integer_sequence<int, NDs...>, F&& f) {
     return rc;
 }
 
+// What the host decides about the launches of one call, written by the family that serves it (attn_mfma_plan, attn_f32_plan,
+// attention.hip's valu_plan).  The launches take their grids, workgroup sizes and dynamic LDS from it and psg_attn_route
+// reports it: no number here is computed a second time elsewhere.
+struct AttnPlan {
+    int nd;                      // 16-column slices of head_dim: the ND of an MFMA instantiation, the VALU kernels' ceil(d / 16)
+    int waves;                   // waves per workgroup of the forward and of the dQ kernel
+    int kw, qw, dkv_waves;       // dK/dV kernel: key-tile waves x query-group waves as the kernel derives them, and the waves launched
+    int qw_cut, w_cut;           // qw was reduced until the partial sums fit / the wave count until the private K/V tiles fit
+    int nh, kv_reg;              // dK/dV kernel: passes over the head dimension; K/V operands in registers (else private LDS tiles)
+    size_t lds_fwd, lds_dq, lds_dkv;
+    int grid_q[2], grid_kv[2];   // grid (x, y) of the forward / dQ launch and of the dK/dV launch
+};
+
 // whether the family's kernels take this problem: its head_dim and row strides, and the LDS fit of its forward kernel and,
 // unless forward_only (psg_attn_fwd_varlen; the training pair psg_attn_fwd_varlen_train / psg_attn_bwd_varlen is not), of its
 // backward kernels
 bool attn_mfma_applicable(int L, int S, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, bool forward_only);
+AttnPlan attn_mfma_plan(int B, int H, int L, int S, int d);
 int attn_mfma_init_attrs();
 template <bool VARLEN> int attn_mfma_fwd(const AttnArgs<bf16_t>& p, hipStream_t s);
 template <bool VARLEN> int attn_mfma_bwd(const AttnArgs<bf16_t>& p, hipStream_t s);
 
 bool attn_f32_applicable(int L, int S, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, bool forward_only);
+AttnPlan attn_f32_plan(int B, int H, int L, int S, int d);
 int attn_f32_init_attrs();
 template <bool VARLEN> int attn_f32_fwd(const AttnArgs<float>& p, hipStream_t s);
 template <bool VARLEN> int attn_f32_bwd(const AttnArgs<float>& p, hipStream_t s);

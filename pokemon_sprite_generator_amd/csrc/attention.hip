@@ -391,55 +391,92 @@ static int f32_mfma_on() {
 }
 static int g_attn_allow = 3;                         // psg_attn_set_paths: bit 0 bf16 MFMA, bit 1 exact-fp32 MFMA
 
-enum AttnPass { ATTN_FWD, ATTN_FWD_VARLEN, ATTN_BWD, ATTN_FWD_VARLEN_TRAIN, ATTN_BWD_VARLEN };
+enum AttnPass { ATTN_FWD, ATTN_FWD_VARLEN, ATTN_BWD, ATTN_FWD_VARLEN_TRAIN, ATTN_BWD_VARLEN, ATTN_PASSES };
+enum AttnFamily { ATTN_MFMA_BF16 = 0, ATTN_VALU = 1, ATTN_MFMA_F32 = 2 };      // (the index in g_attn_paths)
+static inline bool pass_bwd(int pass) { return pass == ATTN_BWD || pass == ATTN_BWD_VARLEN; }
+static inline bool pass_varlen(int pass) { return pass != ATTN_FWD && pass != ATTN_BWD; }
 
-// The kernel family of one call - the bf16 MFMA kernels, the exact-fp32 MFMA kernels or the VALU kernels - counted in
-// g_attn_paths.  A forward that a backward may follow (plain or varlen_train) and a backward take an MFMA family where both
-// its forward and its backward kernels fit LDS, so a training pair stays on one family; the forward-only varlen entry where
-// its forward kernel does.
+// the shape checks of a pass's entry point after attn_check: the LDS need of the VALU kernels (every call must be able to
+// run on them)
+static int attn_check_lds(const char* who, int pass, int S, int d) {
+    if (pass_bwd(pass)) {
+        const size_t l1 = dq_lds(S, d), l2 = dkv_lds(d);
+        PSG_REQUIRE(l1 <= 150 * 1024 && l2 <= 150 * 1024, PSG_ERR_SHAPE, "%s: LDS need too large", who);
+    } else {
+        const size_t lds = fwd_lds(S, d);
+        PSG_REQUIRE(lds <= 150 * 1024, PSG_ERR_SHAPE, "%s: LDS need %zu too large", who, lds);
+    }
+    return PSG_OK;
+}
+
+// The kernel family of one call - the bf16 MFMA kernels, the exact-fp32 MFMA kernels or the VALU kernels.  A forward that a
+// backward may follow (plain or varlen_train) and a backward take an MFMA family where both its forward and its backward
+// kernels fit LDS, so a training pair stays on one family; the forward-only varlen entry where its forward kernel does.
+// ldg: the OR of the gradient row strides (0 for a forward); ptrs_ok: every pointer of the call is aligned as the family's
+// vector loads and stores need (attn_route), or what psg_attn_route was told.
+static AttnFamily attn_family(int pass, int dtype, int L, int S, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t ldg,
+                              bool ptrs_ok) {
+    const bool bwd = pass_bwd(pass), fwd_only = pass == ATTN_FWD_VARLEN;
+    if (dtype == PSG_BF16) {
+        if ((g_attn_allow & 1) && attn_mfma_applicable(L, S, d, ldq, ldk, ldv, ldo, fwd_only) && (!bwd || (ldg & 7) == 0) && ptrs_ok)
+            return ATTN_MFMA_BF16;
+    } else if ((g_attn_allow & 2) && f32_mfma_on() && attn_f32_applicable(L, S, d, ldq, ldk, ldv, ldo, fwd_only) && (!bwd || (ldg & 3) == 0) && ptrs_ok) {
+        return ATTN_MFMA_F32;
+    }
+    return ATTN_VALU;
+}
+
+// the VALU kernels' launches: workgroups of 256 threads, one per 16-query tile (forward, dQ) or 16-key tile (dK/dV) and (b, head)
+static AttnPlan valu_plan(int B, int H, int L, int S, int d) {
+    AttnPlan pl = {};
+    pl.nd = (d + 15) >> 4; pl.waves = pl.dkv_waves = 4;
+    pl.nh = 1;
+    pl.lds_fwd = fwd_lds(S, d); pl.lds_dq = dq_lds(S, d); pl.lds_dkv = dkv_lds(d);
+    pl.grid_q[0] = (L + AT_Q - 1) / AT_Q; pl.grid_kv[0] = (S + AT_Q - 1) / AT_Q; pl.grid_q[1] = pl.grid_kv[1] = B * H;
+    return pl;
+}
+
+// Launches the call on its family (attn_family), counted in g_attn_paths.
 template <typename T>
 static int attn_route(AttnPass pass, const AttnArgs<T>& p, hipStream_t s) {
-    const bool bwd = pass == ATTN_BWD || pass == ATTN_BWD_VARLEN, varlen = pass != ATTN_FWD && pass != ATTN_BWD;
-    const bool fwd_only = pass == ATTN_FWD_VARLEN;
+    const bool bwd = pass_bwd(pass), varlen = pass_varlen(pass);
     // (varlen: the FLOP count is the padded problem's, the key lengths live on the device)
     ProfScope prof(PROF_ATTN, (bwd ? 10.0 : 4.0) * (double)p.B * p.H * p.L * p.S * p.d, s,
                    (double)p.B * p.H * p.d * (bwd ? 4.0 * p.L + 4.0 * p.S : 2.0 * p.L + 2.0 * p.S) * (double)sizeof(T));
+    constexpr bool BF = std::is_same<T, bf16_t>::value;
     const bool in16 = aligned16(p.q) && aligned16(p.k) && aligned16(p.v);
     const int64_t ldg = p.lddo | p.lddq | p.lddk | p.lddv;
-    if constexpr (std::is_same<T, bf16_t>::value) {
-        const bool out_ok = bwd ? (ldg & 7) == 0 && aligned16(p.o) && aligned16(p.dout) && aligned8(p.dq) && aligned8(p.dk) && aligned8(p.dv)
-                                : aligned8(p.out);
-        if ((g_attn_allow & 1) && attn_mfma_applicable(p.L, p.S, p.d, p.ldq, p.ldk, p.ldv, p.ldo, fwd_only) && in16 && out_ok) {
-            ++g_attn_paths[0];
+    bool out_ok;
+    if constexpr (BF) out_ok = bwd ? aligned16(p.o) && aligned16(p.dout) && aligned8(p.dq) && aligned8(p.dk) && aligned8(p.dv) : aligned8(p.out);
+    else out_ok = bwd ? aligned16(p.o) && aligned16(p.dout) && aligned16(p.dq) && aligned16(p.dk) && aligned16(p.dv) : aligned16(p.out);
+    const AttnFamily fam = attn_family(pass, BF ? PSG_BF16 : PSG_F32, p.L, p.S, p.d, p.ldq, p.ldk, p.ldv, p.ldo, ldg, in16 && out_ok);
+    ++g_attn_paths[fam];
+    if constexpr (BF) {
+        if (fam == ATTN_MFMA_BF16)
             return bwd ? (varlen ? attn_mfma_bwd<true>(p, s) : attn_mfma_bwd<false>(p, s)) : varlen ? attn_mfma_fwd<true>(p, s) : attn_mfma_fwd<false>(p, s);
-        }
     } else {
-        const bool out_ok = bwd ? (ldg & 3) == 0 && aligned16(p.o) && aligned16(p.dout) && aligned16(p.dq) && aligned16(p.dk) && aligned16(p.dv)
-                                : aligned16(p.out);
-        if ((g_attn_allow & 2) && f32_mfma_on() && attn_f32_applicable(p.L, p.S, p.d, p.ldq, p.ldk, p.ldv, p.ldo, fwd_only) && in16 && out_ok) {
-            ++g_attn_paths[2];
+        if (fam == ATTN_MFMA_F32)
             return bwd ? (varlen ? attn_f32_bwd<true>(p, s) : attn_f32_bwd<false>(p, s)) : varlen ? attn_f32_fwd<true>(p, s) : attn_f32_fwd<false>(p, s);
-        }
     }
-    ++g_attn_paths[1];
-    const dim3 grid((p.L + AT_Q - 1) / AT_Q, p.B * p.H);
+    const AttnPlan pl = valu_plan(p.B, p.H, p.L, p.S, p.d);
+    const dim3 grid(pl.grid_q[0], pl.grid_q[1]), block(64 * pl.waves);
     if (bwd) {
         const int64_t rows = (int64_t)p.B * p.H * p.L;
         hipLaunchKernelGGL(attn_delta_kernel<T>, dim3((int)((rows + 3) / 4)), dim3(256), 0, s, p);
-        const dim3 kgrid((p.S + AT_Q - 1) / AT_Q, p.B * p.H);
+        const dim3 kgrid(pl.grid_kv[0], pl.grid_kv[1]), kblock(64 * pl.dkv_waves);
         if (varlen) {
-            hipLaunchKernelGGL((attn_dq_kernel<T, true>), grid, dim3(256), dq_lds(p.S, p.d), s, p);
-            hipLaunchKernelGGL((attn_dkv_kernel<T, true>), kgrid, dim3(256), dkv_lds(p.d), s, p);
+            hipLaunchKernelGGL((attn_dq_kernel<T, true>), grid, block, pl.lds_dq, s, p);
+            hipLaunchKernelGGL((attn_dkv_kernel<T, true>), kgrid, kblock, pl.lds_dkv, s, p);
         } else {
-            hipLaunchKernelGGL((attn_dq_kernel<T, false>), grid, dim3(256), dq_lds(p.S, p.d), s, p);
-            hipLaunchKernelGGL((attn_dkv_kernel<T, false>), kgrid, dim3(256), dkv_lds(p.d), s, p);
+            hipLaunchKernelGGL((attn_dq_kernel<T, false>), grid, block, pl.lds_dq, s, p);
+            hipLaunchKernelGGL((attn_dkv_kernel<T, false>), kgrid, kblock, pl.lds_dkv, s, p);
         }
         PSG_LAUNCH_CHECK("attn_bwd");
     } else if (varlen) {
-        hipLaunchKernelGGL((attn_fwd_kernel<T, true>), grid, dim3(256), fwd_lds(p.S, p.d), s, p);
+        hipLaunchKernelGGL((attn_fwd_kernel<T, true>), grid, block, pl.lds_fwd, s, p);
         PSG_LAUNCH_CHECK("attn_fwd_varlen");
     } else {
-        hipLaunchKernelGGL((attn_fwd_kernel<T, false>), grid, dim3(256), fwd_lds(p.S, p.d), s, p);
+        hipLaunchKernelGGL((attn_fwd_kernel<T, false>), grid, block, pl.lds_fwd, s, p);
         PSG_LAUNCH_CHECK("attn_fwd");
     }
     return PSG_OK;
@@ -457,10 +494,10 @@ static int attn_bwd_entry(const char* who, const int32_t* kv_len, const void* q,
     int rc = attn_check(who, B, heads, L, S, d, dtype, ldq, ldk, ldv, ldo);
     if (rc) return rc;
     PSG_REQUIRE(lddo >= heads * d && lddq >= heads * d && lddk >= heads * d && lddv >= heads * d && ((lddo | lddq | lddk | lddv) & 3) == 0,
-                PSG_ERR_SHAPE, "%s: gradient row strides", who);
+                PSG_ERR_SHAPE, "%s: gradient row strides", who);        // (psg_attn_route: the same on their OR)
     PSG_REQUIRE(drop_p >= 0.f && drop_p < 1.f, PSG_ERR_ARG, "%s: drop_p", who);
-    const size_t l1 = dq_lds(S, d), l2 = dkv_lds(d);
-    PSG_REQUIRE(l1 <= 150 * 1024 && l2 <= 150 * 1024, PSG_ERR_SHAPE, "%s: LDS need too large", who);
+    rc = attn_check_lds(who, ATTN_BWD, S, d);
+    if (rc) return rc;
     return with_elem(dtype, [&](auto* tag) {
         using T = std::remove_pointer_t<decltype(tag)>;
         AttnArgs<T> p = {};
@@ -494,6 +531,29 @@ int psg_attn_path_counts(int64_t* mfma, int64_t* valu, int64_t* mfma_f32) {
     return PSG_OK;
 }
 
+int psg_attn_route(int pass, int dtype, int B, int heads, int L, int S, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                   int64_t ld_grads, int ptrs_aligned16, int32_t* out) {
+    PSG_REQUIRE(out, PSG_ERR_ARG, "attn_route: null pointer");
+    PSG_REQUIRE(pass >= 0 && pass < ATTN_PASSES, PSG_ERR_ARG, "attn_route: pass %d", pass);
+    int rc = attn_check("attn_route", B, heads, L, S, d, dtype, ldq, ldk, ldv, ldo);
+    if (rc) return rc;
+    const bool bwd = pass_bwd(pass);
+    if (bwd) PSG_REQUIRE(ld_grads >= heads * d && (ld_grads & 3) == 0, PSG_ERR_SHAPE, "attn_route: gradient row strides");
+    rc = attn_check_lds("attn_route", pass, S, d);
+    if (rc) return rc;
+    const AttnFamily fam = attn_family(pass, dtype, L, S, d, ldq, ldk, ldv, ldo, bwd ? ld_grads : 0, ptrs_aligned16 != 0);
+    const AttnPlan pl = fam == ATTN_MFMA_BF16 ? attn_mfma_plan(B, heads, L, S, d) : fam == ATTN_MFMA_F32 ? attn_f32_plan(B, heads, L, S, d)
+                                                                                  : valu_plan(B, heads, L, S, d);
+    // a forward launches no dQ / dK/dV kernel and a backward no forward kernel: their fields are 0
+    const int32_t v[PSG_ATTN_ROUTE_FIELDS] = {
+        fam, pl.nd, pl.waves, bwd ? pl.kw : 0, bwd ? pl.qw : 0, bwd ? pl.dkv_waves : 0, bwd ? pl.qw_cut : 0, bwd ? pl.w_cut : 0,
+        bwd ? pl.nh : 0, bwd ? pl.kv_reg : 0, bwd ? 0 : (int32_t)pl.lds_fwd, bwd ? (int32_t)pl.lds_dq : 0, bwd ? (int32_t)pl.lds_dkv : 0,
+        bwd ? 0 : pl.grid_q[0], bwd ? 0 : pl.grid_q[1], bwd ? pl.grid_q[0] : 0, bwd ? pl.grid_q[1] : 0, bwd ? pl.grid_kv[0] : 0,
+        bwd ? pl.grid_kv[1] : 0, pass_varlen(pass) ? 1 : 0};
+    for (int i = 0; i < PSG_ATTN_ROUTE_FIELDS; ++i) out[i] = v[i];
+    return PSG_OK;
+}
+
 int psg_attn_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* o, int64_t ldo,
                  float* lse, int B, int heads, int L, int S, int d, float scale, float drop_p, uint64_t seed, int dtype,
                  psg_stream_t stream) {
@@ -501,8 +561,8 @@ int psg_attn_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const v
     int rc = attn_check("attn_fwd", B, heads, L, S, d, dtype, ldq, ldk, ldv, ldo);
     if (rc) return rc;
     PSG_REQUIRE(drop_p >= 0.f && drop_p < 1.f, PSG_ERR_ARG, "attn_fwd: drop_p");
-    const size_t lds = fwd_lds(S, d);
-    PSG_REQUIRE(lds <= 150 * 1024, PSG_ERR_SHAPE, "attn_fwd: LDS need %zu too large", lds);
+    rc = attn_check_lds("attn_fwd", ATTN_FWD, S, d);
+    if (rc) return rc;
     return with_elem(dtype, [&](auto* tag) {
         using T = std::remove_pointer_t<decltype(tag)>;
         AttnArgs<T> p = {};
@@ -520,8 +580,8 @@ int psg_attn_fwd_varlen(const void* q, int64_t ldq, const void* k, int64_t ldk, 
     int rc = attn_check("attn_fwd_varlen", B, heads, L, S, d, dtype, ldq, ldk, ldv, ldo);
     if (rc) return rc;
     PSG_REQUIRE(drop_p == 0.f, PSG_ERR_ARG, "attn_fwd_varlen: forward-only entry, drop_p must be 0 (got %g)", (double)drop_p);
-    const size_t lds = fwd_lds(S, d);
-    PSG_REQUIRE(lds <= 150 * 1024, PSG_ERR_SHAPE, "attn_fwd_varlen: LDS need %zu too large", lds);
+    rc = attn_check_lds("attn_fwd_varlen", ATTN_FWD_VARLEN, S, d);
+    if (rc) return rc;
     return with_elem(dtype, [&](auto* tag) {
         using T = std::remove_pointer_t<decltype(tag)>;
         AttnArgs<T> p = {};
@@ -539,8 +599,8 @@ int psg_attn_fwd_varlen_train(const void* q, int64_t ldq, const void* k, int64_t
     int rc = attn_check("attn_fwd_varlen_train", B, heads, L, S, d, dtype, ldq, ldk, ldv, ldo);
     if (rc) return rc;
     PSG_REQUIRE(drop_p >= 0.f && drop_p < 1.f, PSG_ERR_ARG, "attn_fwd_varlen_train: drop_p");
-    const size_t lds = fwd_lds(S, d);
-    PSG_REQUIRE(lds <= 150 * 1024, PSG_ERR_SHAPE, "attn_fwd_varlen_train: LDS need %zu too large", lds);
+    rc = attn_check_lds("attn_fwd_varlen_train", ATTN_FWD_VARLEN_TRAIN, S, d);
+    if (rc) return rc;
     return with_elem(dtype, [&](auto* tag) {
         using T = std::remove_pointer_t<decltype(tag)>;
         AttnArgs<T> p = {};

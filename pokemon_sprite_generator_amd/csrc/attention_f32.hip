@@ -390,6 +390,16 @@ bool attn_f32_applicable(int L, int S, int d, int64_t ldq, int64_t ldk, int64_t 
     return f32_lds(S, d) <= F32_LDS_CAP && (forward_only || f32_lds(L, d) <= F32_LDS_CAP);
 }
 
+AttnPlan attn_f32_plan(int B, int H, int L, int S, int d) {
+    AttnPlan pl = {};
+    pl.nd = d / 16; pl.waves = f32_waves(L);
+    pl.kw = pl.dkv_waves = f32_waves(S); pl.qw = 1;          // one wave per key tile, each walking every query tile
+    pl.nh = 1; pl.kv_reg = 1;
+    pl.lds_fwd = pl.lds_dq = f32_lds(S, d); pl.lds_dkv = f32_lds(L, d);
+    pl.grid_q[0] = pl.grid_kv[0] = B * H; pl.grid_q[1] = pl.grid_kv[1] = 1;
+    return pl;
+}
+
 int attn_f32_init_attrs() {
     return for_each_nd(F32NDs{}, [](auto nd) {
         constexpr int ND = decltype(nd)::value;
@@ -400,8 +410,9 @@ int attn_f32_init_attrs() {
 
 template <bool VARLEN>
 int attn_f32_fwd(const AttnArgs<float>& p, hipStream_t s) {
+    const AttnPlan pl = attn_f32_plan(p.B, p.H, p.L, p.S, p.d);
     if (!with_nd(F32NDs{}, p.d, [&](auto nd) {
-            hipLaunchKernelGGL((attn_fwd_f32<decltype(nd)::value, VARLEN>), dim3(p.B * p.H), dim3(64 * f32_waves(p.L)), f32_lds(p.S, p.d), s, p);
+            hipLaunchKernelGGL((attn_fwd_f32<decltype(nd)::value, VARLEN>), dim3(pl.grid_q[0], pl.grid_q[1]), dim3(64 * pl.waves), pl.lds_fwd, s, p);
         }))
         return set_error(PSG_ERR_SHAPE, "attn_fwd_f32: head_dim %d", p.d);
     PSG_LAUNCH_CHECK(VARLEN ? "attn_fwd_f32_varlen" : "attn_fwd_f32");
@@ -412,13 +423,14 @@ template int attn_f32_fwd<true>(const AttnArgs<float>&, hipStream_t);
 
 template <bool VARLEN>
 int attn_f32_bwd(const AttnArgs<float>& p, hipStream_t s) {
+    const AttnPlan pl = attn_f32_plan(p.B, p.H, p.L, p.S, p.d);
     if (!with_nd(F32NDs{}, p.d, [&](auto nd) {
-            hipLaunchKernelGGL((attn_dq_f32<decltype(nd)::value, VARLEN>), dim3(p.B * p.H), dim3(64 * f32_waves(p.L)), f32_lds(p.S, p.d), s, p);
+            hipLaunchKernelGGL((attn_dq_f32<decltype(nd)::value, VARLEN>), dim3(pl.grid_q[0], pl.grid_q[1]), dim3(64 * pl.waves), pl.lds_dq, s, p);
         }))
         return set_error(PSG_ERR_SHAPE, "attn_dq_f32: head_dim %d", p.d);
     PSG_LAUNCH_CHECK("attn_dq_f32");
     with_nd(F32NDs{}, p.d, [&](auto nd) {
-        hipLaunchKernelGGL((attn_dkv_f32<decltype(nd)::value, VARLEN>), dim3(p.B * p.H), dim3(64 * f32_waves(p.S)), f32_lds(p.L, p.d), s, p);
+        hipLaunchKernelGGL((attn_dkv_f32<decltype(nd)::value, VARLEN>), dim3(pl.grid_kv[0], pl.grid_kv[1]), dim3(64 * pl.dkv_waves), pl.lds_dkv, s, p);
     });
     PSG_LAUNCH_CHECK("attn_dkv_f32");
     return PSG_OK;

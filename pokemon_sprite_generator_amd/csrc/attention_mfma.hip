@@ -40,6 +40,10 @@ __device__ __forceinline__ bf16x8 pack8(const f32x16& x, int s2) {   // register
     for (int j = 0; j < 8; ++j) r[j] = (bf16_t)x[8 * s2 + j];
     return r;
 }
+// dK/dV kernel, by ND: K/V B-operands straight from HBM into registers (else a private LDS tile per wave), and the passes
+// over the head dimension (see the kernel); the host's LDS arithmetic below reads the same two
+constexpr bool mfma_kv_reg(int nd) { return nd <= 5; }
+constexpr int mfma_nh(int nd) { return nd > 10 ? 2 : 1; }
 __device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // stage rows [0, nrows) of a [*, d] bf16 matrix into LDS rows of `stride` bytes, zero-filling rows >= nvalid
@@ -359,7 +363,7 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dkv_mfma(const At
     constexpr int D32 = NDT * 32;
     constexpr int STR = 2 * ND * 16 + 16;      // row = d values + one 16-byte slot (odd slot count: conflict-free row reads)
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr bool KV_REG = ND <= 5;                          // K/V B-operands straight from HBM into registers
+    constexpr bool KV_REG = mfma_kv_reg(ND);
     const int Lp = (p.L + 31) & ~31;
     char* Qs = smem;
     char* Gs = Qs + Lp * STR;
@@ -422,7 +426,7 @@ __global__ __launch_bounds__(256, (ND <= 5 ? 2 : 1)) void attn_dkv_mfma(const At
         }
         // head_dim 320: the 2 x 10 output tiles of dK and dV (320 accumulator registers) do not fit next to the score
         // tiles, so the head dimension is produced in two halves, each recomputing the (cheap) score / dP tiles
-        constexpr int NH = ND > 10 ? 2 : 1, TH = NDT / NH;
+        constexpr int NH = mfma_nh(ND), TH = NDT / NH;
         static_assert(NDT % NH == 0, "head-dim halves");
 #pragma unroll 1
         for (int hp = 0; hp < NH; ++hp) {
@@ -547,34 +551,48 @@ static inline int attn_waves(int rows) { const int t = (rows + 31) / 32; return 
 constexpr size_t MFMA_LDS_CAP = 158 * 1024;
 static inline size_t dkv_lds_w(int L, int d, int waves) {
     const size_t Lp = (L + 31) & ~31;
-    return 2 * Lp * str_bytes(d) + 32 + (d > 80 ? (size_t)waves * 2 * 32 * str_bytes(d) + 32 : 0);
+    return 2 * Lp * str_bytes(d) + 32 + (mfma_kv_reg(d / 16) ? 0 : (size_t)waves * 2 * 32 * str_bytes(d) + 32);
 }
 // waves of the dK/dV kernel: one per 32-key tile, fewer when their private K/V tiles would not fit LDS next to the
 // Q / dO images (head_dim 320 = the reference CLI's 4 heads at 1280 channels: 7x7 self-attention runs 1 wave)
-static inline int dkv_waves(int L, int S, int d) {
+struct DkvSplit { int kw, qw, waves; bool qw_cut, w_cut; };      // kw x qw as the kernel derives them from `waves` and S
+static inline DkvSplit dkv_split(int L, int S, int d) {
     const int nkt = (S + 31) / 32, nqt = (L + 31) / 32;
     int kw = attn_waves(S);
     // query groups per key tile (round 3): only when the key tiles do not fill the workgroup (S = 32: one tile; 49: two), the
     // partial sums fit the dead Q / dO images, and K / V ride in registers (head_dim <= 80: at 160 every extra wave stages a
     // private K / V tile, and the 7x7 cross-attention backward went from 125 to 154 us with two query groups)
     int qw = 1;
+    bool qw_cut = false, w_cut = false;
     if (d <= 80 && nkt <= 2 && kw == nkt) {
         qw = 4 / kw;
         if (qw > nqt) qw = nqt;
         if (qw < 1) qw = 1;
         const size_t th = (size_t)((d / 16 + 1) / 2);
-        while (qw > 1 && ((size_t)(qw - 1) * kw * th * 8192 > dkv_lds_w(L, d, kw * qw) || dkv_lds_w(L, d, kw * qw) > MFMA_LDS_CAP)) --qw;
+        while (qw > 1 && ((size_t)(qw - 1) * kw * th * 8192 > dkv_lds_w(L, d, kw * qw) || dkv_lds_w(L, d, kw * qw) > MFMA_LDS_CAP)) { --qw; qw_cut = true; }
     }
     int w = kw * qw;
-    if (qw == 1) while (w > 1 && dkv_lds_w(L, d, w) > MFMA_LDS_CAP) --w;
-    return w;
+    if (qw == 1) while (w > 1 && dkv_lds_w(L, d, w) > MFMA_LDS_CAP) { --w; w_cut = true; }
+    return {qw == 1 ? w : kw, qw, w, qw_cut, w_cut};         // (qw == 1: w <= kw <= key tiles, the kernel's KW = min(key tiles, waves) = w)
 }
+static inline int dkv_waves(int L, int S, int d) { return dkv_split(L, S, d).waves; }
 static inline size_t dkv_lds_m(int L, int S, int d) { return dkv_lds_w(L, d, dkv_waves(L, S, d)); }
 
 bool attn_mfma_applicable(int L, int S, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, bool forward_only) {
     if (!with_nd(MfmaNDs{}, d, [](auto) {})) return false;
     if (((ldq | ldk | ldv | ldo) & 7) != 0) return false;                // 16-byte row fragments
     return fwd_lds_m(S, d) <= MFMA_LDS_CAP && (forward_only || dkv_lds_m(L, S, d) <= MFMA_LDS_CAP);
+}
+
+AttnPlan attn_mfma_plan(int B, int H, int L, int S, int d) {
+    const DkvSplit w = dkv_split(L, S, d);
+    AttnPlan pl = {};
+    pl.nd = d / 16; pl.waves = attn_waves(L);
+    pl.kw = w.kw; pl.qw = w.qw; pl.dkv_waves = w.waves; pl.qw_cut = w.qw_cut; pl.w_cut = w.w_cut;
+    pl.nh = mfma_nh(d / 16); pl.kv_reg = mfma_kv_reg(d / 16);
+    pl.lds_fwd = pl.lds_dq = fwd_lds_m(S, d); pl.lds_dkv = dkv_lds_w(L, d, w.waves);
+    pl.grid_q[0] = pl.grid_kv[0] = B * H; pl.grid_q[1] = pl.grid_kv[1] = 1;
+    return pl;
 }
 
 int attn_mfma_init_attrs() {
@@ -587,8 +605,9 @@ int attn_mfma_init_attrs() {
 
 template <bool VARLEN>
 int attn_mfma_fwd(const AttnArgs<bf16_t>& p, hipStream_t s) {
+    const AttnPlan pl = attn_mfma_plan(p.B, p.H, p.L, p.S, p.d);
     if (!with_nd(MfmaNDs{}, p.d, [&](auto nd) {
-            hipLaunchKernelGGL((attn_fwd_mfma<decltype(nd)::value, VARLEN>), dim3(p.B * p.H), dim3(64 * attn_waves(p.L)), fwd_lds_m(p.S, p.d), s, p);
+            hipLaunchKernelGGL((attn_fwd_mfma<decltype(nd)::value, VARLEN>), dim3(pl.grid_q[0], pl.grid_q[1]), dim3(64 * pl.waves), pl.lds_fwd, s, p);
         }))
         return set_error(PSG_ERR_SHAPE, "attn_fwd_mfma: head_dim %d", p.d);
     PSG_LAUNCH_CHECK(VARLEN ? "attn_fwd_mfma_varlen" : "attn_fwd_mfma");
@@ -599,13 +618,14 @@ template int attn_mfma_fwd<true>(const AttnArgs<bf16_t>&, hipStream_t);
 
 template <bool VARLEN>
 int attn_mfma_bwd(const AttnArgs<bf16_t>& p, hipStream_t s) {
+    const AttnPlan pl = attn_mfma_plan(p.B, p.H, p.L, p.S, p.d);
     if (!with_nd(MfmaNDs{}, p.d, [&](auto nd) {
-            hipLaunchKernelGGL((attn_dq_mfma<decltype(nd)::value, VARLEN>), dim3(p.B * p.H), dim3(64 * attn_waves(p.L)), fwd_lds_m(p.S, p.d), s, p);
+            hipLaunchKernelGGL((attn_dq_mfma<decltype(nd)::value, VARLEN>), dim3(pl.grid_q[0], pl.grid_q[1]), dim3(64 * pl.waves), pl.lds_dq, s, p);
         }))
         return set_error(PSG_ERR_SHAPE, "attn_dq_mfma: head_dim %d", p.d);
     PSG_LAUNCH_CHECK("attn_dq_mfma");
     with_nd(MfmaNDs{}, p.d, [&](auto nd) {
-        hipLaunchKernelGGL((attn_dkv_mfma<decltype(nd)::value, VARLEN>), dim3(p.B * p.H), dim3(64 * dkv_waves(p.L, p.S, p.d)), dkv_lds_m(p.L, p.S, p.d), s, p);
+        hipLaunchKernelGGL((attn_dkv_mfma<decltype(nd)::value, VARLEN>), dim3(pl.grid_kv[0], pl.grid_kv[1]), dim3(64 * pl.dkv_waves), pl.lds_dkv, s, p);
     });
     PSG_LAUNCH_CHECK("attn_dkv_mfma");
     return PSG_OK;
