@@ -456,6 +456,37 @@ int psg_adamw_dev_f32(float* p, const float* g, float* m, float* v, int64_t n, c
 int psg_clip_scale_f32(float* g, int64_t n, const float* normsq, float max_norm, psg_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Sprite batches from a device-resident dataset (sprites.hip): the train pipeline of the reference's loader
+ * (src/data/dataset_improved.py:150-158 + :144-148: RandomHorizontalFlip, RandomRotation(10), ColorJitter,
+ * RandomResizedCrop, ToTensor, Normalize) as one gather per output pixel, with the intermediate uint8 roundings of
+ * the PIL chain removed and its clipping kept.
+ *
+ * src: uint8 [N, S, S, 4] (R, G, B, unused: one dword per pixel), composited on the background colour.
+ * idx: int64 [B], the row of src each sample reads; a value outside [0, N) yields NaN for that sample, never an
+ *      out-of-bounds read.
+ * params: fp32 [B, PSG_SPRITE_PARAMS], per sample
+ *   [0]      flip (0 or 1)
+ *   [1..6]   a b c d e f of the inverse rotation: xin = a(u+.5) + b(v+.5) + c, yin = d(u+.5) + e(v+.5) + f; the rotated
+ *            image's pixel (u, v) is the flipped image's pixel (floor xin, floor yin), black outside
+ *   [7]      order of the four colour ops: index 0..23 of the lexicographic permutations of (0 brightness, 1 contrast,
+ *            2 saturation, 3 hue); the k-th entry of the permutation is the k-th op applied
+ *   [8..11]  brightness, contrast, saturation factors and the hue shift in turns; factor 1 (hue 0) skips the op
+ *   [12..15] crop box top i, left j, height h, width w (integers; 1 <= h, w and i + h, j + w <= S)
+ * The identity row (0, 1,0,0,0,1,0, 0, 1,1,1,0, 0,0,S,S) gives ((p / 255) - 0.5) / 0.5 of the stored pixel, bitwise.
+ * ------------------------------------------------------------------------- */
+#define PSG_SPRITE_PARAMS 16
+/* mean[b]: mean luma ((19595 R + 38470 G + 7471 B) / 65536) over the S*S pixels of sample b's image as the contrast
+ * op meets it: flipped, rotated (black corners included), the colour ops in front of contrast applied.  Fixed-order
+ * reduction (lane, wave, block): bitwise reproducible.  A sample whose contrast factor is 1 gets 0. */
+int psg_sprite_contrast_mean(const uint8_t* src, int64_t N, const int64_t* idx, const float* params, float* mean,
+                             int B, int S, psg_stream_t stream);
+/* out: fp32 [B, 3, S, S] in [-1, 1].  Output pixel (y, x): 2-tap bilinear up-scale of the crop box (taps clamped to the
+ * box), each of the four taps fetched through rotation and flip and run through the colour ops (contrast blends with
+ * mean[b]), then combined and normalised. */
+int psg_sprite_augment(const uint8_t* src, int64_t N, const int64_t* idx, const float* params, const float* mean,
+                       float* out, int B, int S, psg_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Measurement hooks (bench.py): between begin and end every launch of the matrix / attention /
  * GroupNorm kernel families is bracketed by hipEvents on its stream.  end() drains once and
  * returns, per family k < nkinds (0 conv fwd gather, 1 conv data-gradient gather, 2 wgrad,

@@ -16,9 +16,10 @@ from .inference import LatentGenerator, LinearNoiseScheduler, gradio_ddpm_sample
 from .vae import PokemonVAE, VAEDecoder, VAEEncoder
 from .text_encoder import TextEncoder
 from .final import FinalPokemonGenerator, FinalStepper
+from .data import SpriteDataset, SpriteLoader, create_data_loaders, draw_params
 
 __all__ = ["UNet", "UNetBlock", "ResBlock", "CrossAttentionBlock", "TimestepEmbedding", "NoiseScheduler",
            "ImprovedDiffusionTrainer", "DiffusionTrainer", "DiffusionStepper", "FusedAdamW", "GradArena", "ParamArena",
            "BucketedAllReduce", "LatentGenerator", "LinearNoiseScheduler", "gradio_ddpm_sample", "PokemonVAE", "VAEEncoder", "VAEDecoder", "TextEncoder",
-           "FinalPokemonGenerator", "FinalStepper", "PsgError", "LIB_PATH"]
+           "FinalPokemonGenerator", "FinalStepper", "SpriteDataset", "SpriteLoader", "create_data_loaders", "draw_params", "PsgError", "LIB_PATH"]
 __version__ = "0.1.0"

@@ -477,6 +477,7 @@ class ImprovedDiffusionTrainer:
         self._grad_bucket_dtype = {"fp32": torch.float32, "bf16": torch.bfloat16}[str(mi.get("grad_bucket_dtype", "fp32"))]
         # data parallel: measure the gradient-exchange mode on the first training batch (state is restored: no training happens)
         self._ddp_autotune = bool(mi.get("ddp_autotune", True))
+        self._gpu_data = bool(mi.get("gpu_data", False))     # this package's loader even inside the reference tree
         if not torch.cuda.is_available():
             raise _lib.PsgError("ImprovedDiffusionTrainer (MI355X build) needs a GPU; there is no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device())
@@ -524,10 +525,20 @@ class ImprovedDiffusionTrainer:
         if name == "TextEncoder":                        # the frozen BERT text encoder as well (text_encoder.py)
             from .text_encoder import TextEncoder
             return lambda *a, **k: TextEncoder(*a, compute_dtype=self.text_dtype, **k)
+        if name == "create_data_loaders":
+            # the reference tree's loader when this class is dropped into it (as before); anywhere else, or with
+            # `mi355x.gpu_data: true`, this package's device-resident loader (data.py)
+            if not self._gpu_data:
+                try:
+                    import importlib
+                    return getattr(importlib.import_module("src.data"), name)
+                except Exception:              # noqa: BLE001
+                    pass
+            from .data import create_data_loaders
+            return create_data_loaders
         try:                                   # the reference package, when this class is dropped into its tree
             import importlib
-            mod = importlib.import_module({"create_data_loaders": "src.data"}.get(name, "src.models"))
-            return getattr(mod, name)
+            return getattr(importlib.import_module("src.models"), name)
         except Exception as e:                 # noqa: BLE001
             raise _lib.PsgError(f"component '{name}' is outside the accelerated hot path: provide it via components= "
                                 f"or run inside the reference tree ({e})")
