@@ -262,6 +262,29 @@ int64_t psg_conv_pw_launches(void);
  * psg_conv_tapclass_launches counts the launches that ran in class order. */
 int psg_conv_set_tapclass(int on);
 int64_t psg_conv_tapclass_launches(void);
+/* Tile pin: c = 0..4 makes every psg_conv_fwd launch use the candidate tile 128x128, 128x64, 64x64, 128x160 or 64x160
+ * instead of the plan's choice (kernel A/B runs, the route tests); -1 (any other value) gives the choice back to the plan.
+ * The initial value is the environment variable PSG_CONV_TILE.  A pinned launch is never split along K (workspace or
+ * not); the 160-wide tiles exist only for bf16 and not for the parity-class launches of a stride-2 3x3 data gradient:
+ * pinned there, psg_conv_fwd (and psg_conv_route) return PSG_ERR_ARG and launch nothing. */
+int psg_conv_set_tile(int c);
+/* Host-only: which kernels psg_conv_fwd(d) would launch, and how.  Runs the descriptor checks of psg_conv_fwd (same error
+ * codes) and the same planning code - honouring d->ws / ws_bytes, psg_conv_set_tile / _set_tapclass / _set_pw,
+ * psg_set_available_cus and psg_set_reserve_rounds - but reads no operand, launches nothing and leaves the launch
+ * counters alone (the pointers of d must only be non-NULL and aligned as psg_conv_fwd asks).
+ * out[0] = number of launches (1; up to 4, one per non-empty parity class, for the data gradient of a stride-2 3x3 conv),
+ * then PSG_CONV_ROUTE_FIELDS values per launch, the unused launches zero:
+ *   BM, BN       tile (pixels x channels)
+ *   mode         gather: 0 fast forward, 1 fast stride-1 data gradient, 2 generic per-thread decode, 3 parity class
+ *   splits, kt_per_split   split-K: workgroups per tile (1 = unsplit) and K steps of each but the last
+ *   tapcls       1: border-class order        pw: 1: the persistent pointwise kernel (csrc/conv_pw.hip)
+ *   epi_lds      1: stores staged through LDS (bf16, unsplit, every row stride a multiple of 8); 0: direct / fp32 / split-K finish
+ *   mtiles, ntiles, grid   tile counts (mtiles in class order with tapcls) and workgroups launched
+ *   M, KT        GEMM rows and K steps of this launch (a parity class has its own)
+ *   sub_h0, sub_w0, sub_nH, sub_nW, ntap   mode 3: first result row / column of the class, its grid, its filter taps */
+#define PSG_CONV_ROUTE_FIELDS 18
+#define PSG_CONV_ROUTE_MAX_LAUNCHES 4
+int psg_conv_route(const psg_conv_desc* d, int32_t* out);   /* out: 1 + 4 * PSG_CONV_ROUTE_FIELDS values */
 
 /* Weight gradient — convolution_backward's wgrad for the same layers.
  * dw (fp32) = sum_m dy[m,co] * x[pix(m,kh,kw), ci], stored in the parameter's own memory order:

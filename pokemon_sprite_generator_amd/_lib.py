@@ -83,6 +83,8 @@ SIGNATURES = {
     "psg_conv_pw_launches": (c_int64, []),
     "psg_conv_set_tapclass": (c_int, [c_int]),
     "psg_conv_tapclass_launches": (c_int64, []),
+    "psg_conv_set_tile": (c_int, [c_int]),
+    "psg_conv_route": (c_int, [C.POINTER(ConvDesc), c_void_p]),
     "psg_conv_wgrad": (c_int, [C.POINTER(WgradDesc), c_void_p]),
     "psg_conv_wgrad_workspace_bytes": (c_int64, [C.POINTER(WgradDesc)]),
     "psg_prep_weight": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

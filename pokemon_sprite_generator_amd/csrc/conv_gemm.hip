@@ -24,17 +24,22 @@ PSG_CONV_TILES(X)
 
 // persistent pointwise kernel (conv_pw.hip)
 bool conv_pw_applicable(const ConvP& p, int dtype);
+void conv_pw_grid(const ConvP& p, int& mtiles, int& ntiles, int& grid);
 int launch_conv_pw(const ConvP& p, hipStream_t stream);
 int conv_pw_set_attrs();
 
 // tile choice: maximise (useful fraction of the tile grid) x (chip fill of the last wave) x (tile efficiency); then, for
 // grids that leave most of the chip idle (small M: sampling, small batches), split-K on top
 struct ConvPlan { int BM, BN, splits, kt_per_split; };
+static int g_tile = -2;                                // PSG_CONV_TILE=0..4 / psg_conv_set_tile pins a candidate (kernel A/B runs, tests)
+static int tile_setting() {
+    if (g_tile == -2) { const char* e = getenv("PSG_CONV_TILE"); const int v = e ? atoi(e) : -1; g_tile = (v >= 0 && v <= 4) ? v : -1; }
+    return g_tile;
+}
 static ConvPlan conv_plan(const ConvP& p, int dtype, bool may_split) {
     const int64_t M = p.M;
     ConvPlan pl = {128, 128, 1, p.KT};
-    static int force = -2;                             // PSG_CONV_TILE=0..4 pins a candidate (kernel A/B runs)
-    if (force == -2) { const char* e = getenv("PSG_CONV_TILE"); force = e ? atoi(e) : -1; }
+    const int force = tile_setting();
     const int cand[5][2] = {{128, 128}, {128, 64}, {64, 64}, {128, 160}, {64, 160}};
     double eff[5] = {1.0, 0.78, 0.55, 1.0, 0.70};      // measured relative MFMA efficiency of the tile shapes
     // (a K <= 640 boost for 128x64 - three resident workgroups hiding the short loop ends - paid before the epilogue was
@@ -140,8 +145,18 @@ static bool tapcls_pays(const ConvP& p, int BM, int BN) {
     return pays;
 }
 
-static int choose_and_launch(const ConvP& p0, int dtype, hipStream_t s) {
-    ConvP p = p0;
+// One launch of psg_conv_fwd as the host planned it: the tile, the K split, the border-class order, persistent pointwise or
+// per-tile kernel, and the grid.  conv_plan_launch decides, launch_planned only reads - so psg_conv_route reports what
+// psg_conv_fwd runs, from the same code.
+struct ConvLaunch {
+    ConvP p;                       // the launch's parameters: splits, kt_per_split, tapcls (and the parity-class fields) set
+    int BM, BN, mode, pw, epi_lds; // epi_lds: the launch stores through the LDS staging (bf16, unsplit, 16-byte row chunks)
+    int mtiles, ntiles, grid;
+};
+
+static int conv_plan_launch(const ConvP& p0, int dtype, ConvLaunch& L) {
+    ConvP& p = L.p;
+    p = p0;
     ConvPlan pl = conv_plan(p, dtype, p.ws != nullptr);
     p.splits = 1; p.kt_per_split = p.KT;
     if (pl.splits > 1) {
@@ -149,8 +164,61 @@ static int choose_and_launch(const ConvP& p0, int dtype, hipStream_t s) {
         else pl = conv_plan(p, dtype, false);          // workspace too small: the best UNSPLIT tile, not the split plan's tile
     }
     const int BM = pl.BM, BN = pl.BN;
+    L.BM = BM; L.BN = BN; L.mode = conv_mode(p);
+    // (only a pinned tile gets here with a 160-wide tile the dtype / mode has no kernel for: the plan scores them 0)
+    if (BN == 160 && dtype != PSG_BF16) return set_error(PSG_ERR_ARG, "conv_gemm: no %s %dx%d tile", "fp32", BM, BN);
+    if (BN == 160 && L.mode == 3) return set_error(PSG_ERR_ARG, "conv_gemm: no 160-wide parity-class kernel");
     p.tapcls = 0;
     if (tapcls_setting() && tapcls_applicable(p, dtype) && (tapcls_setting() == 2 || tapcls_pays(p, BM, BN))) p.tapcls = 1;
+    L.pw = (BM == 128 && BN == 128 && p.splits == 1 && conv_pw_applicable(p, dtype)) ? 1 : 0;
+    if (L.pw) conv_pw_grid(p, L.mtiles, L.ntiles, L.grid);
+    else {
+        L.mtiles = conv_mtiles(p, BM); L.ntiles = (p.N + BN - 1) / BN;
+        L.grid = L.mtiles * L.ntiles * (p.splits > 1 ? p.splits : 1);
+    }
+    L.epi_lds = (p.epi_lds && p.splits == 1) ? 1 : 0;
+    return PSG_OK;
+}
+
+// The launches of a descriptor that conv_setup accepted: one, or up to four for the data gradient of a stride-2 3x3 conv
+static int conv_plan_all(const ConvP& p, int dtype, ConvLaunch (&L)[4], int& n) {
+    n = 0;
+    if (p.transposed && p.stride == 2 && p.fast && p.ks == 3) {
+        // Data gradient of a stride-2 conv: a result pixel (ho, wo) is reached only by the taps with
+        // kh = (ho + pad) mod 2 (mod 2), same for kw - 1, 2, 2 or 4 of the 9.  One launch per parity class, each a
+        // dense stride-1-like gather on the class's own grid: 2.25 taps per pixel on average instead of 9.
+        for (int ah = 0; ah < 2; ++ah)
+            for (int aw = 0; aw < 2; ++aw) {
+                ConvP q = p;
+                q.sub_h0 = (ah - p.pad) & 1; q.sub_w0 = (aw - p.pad) & 1;
+                q.sub_nH = (p.Ho - q.sub_h0 + 1) >> 1; q.sub_nW = (p.Wo - q.sub_w0 + 1) >> 1;
+                if (q.sub_nH <= 0 || q.sub_nW <= 0) continue;
+                q.ntap = 0;
+                for (int kh = ah; kh < 3; kh += 2)
+                    for (int kw = aw; kw < 3; kw += 2) {
+                        q.tap_dh[q.ntap] = (q.sub_h0 + p.pad - kh) / 2;
+                        q.tap_dw[q.ntap] = (q.sub_w0 + p.pad - kw) / 2;
+                        q.tap_wi[q.ntap] = kh * 3 + kw;
+                        ++q.ntap;
+                    }
+                q.M = p.B * q.sub_nH * q.sub_nW;
+                q.taps = q.ntap;                           // (profiling: useful FLOPs of this class)
+                q.KT = q.ntap * p.tpt;
+                const int rc = conv_plan_launch(q, dtype, L[n]);
+                if (rc) return rc;
+                ++n;
+            }
+        return PSG_OK;
+    }
+    const int rc = conv_plan_launch(p, dtype, L[0]);
+    if (rc) return rc;
+    n = 1;
+    return PSG_OK;
+}
+
+static int launch_planned(const ConvLaunch& L, int dtype, hipStream_t s) {
+    ConvP p = L.p;
+    const int BM = L.BM, BN = L.BN;
 #ifdef PSG_ABL
     if (PSG_ABL & 8) { const char* e = getenv("PSG_DBG_PTR"); p.ws = (e && p.splits <= 1) ? reinterpret_cast<float*>(strtoull(e, nullptr, 0)) : (p.splits <= 1 ? nullptr : p.ws); }
 #endif
@@ -160,7 +228,7 @@ static int choose_and_launch(const ConvP& p0, int dtype, hipStream_t s) {
         if (dbg) fprintf(stderr, "psg conv: M=%d N=%d Cin=%d ks=%d tr=%d fast=%d epi_lds=%d -> tile %dx%d splits=%d tapcls=%d\n", p.M, p.N, p.Cin, p.ks, p.transposed,
                          p.fast, p.epi_lds, BM, BN, p.splits, p.tapcls);
     }
-    if (BM == 128 && BN == 128 && p.splits == 1 && conv_pw_applicable(p, dtype)) return launch_conv_pw(p, s);
+    if (L.pw) return launch_conv_pw(p, s);
     if (p.tapcls) ++g_tapcls_launches;
 #define X(T, TBM, TBN) \
     if ((dtype == PSG_BF16) == std::is_same<T, bf16_t>::value && BM == TBM && BN == TBN) return launch_conv<T, TBM, TBN>(p, s);
@@ -272,38 +340,36 @@ int64_t psg_conv_fwd_workspace_bytes(const psg_conv_desc* d) {
 
 int psg_conv_fwd(const psg_conv_desc* d, psg_stream_t stream) {
     ConvP p;
-    const int rc0 = conv_setup(d, p);
-    if (rc0) return rc0;
-    hipStream_t s = (hipStream_t)stream;
-    if (p.transposed && p.stride == 2 && p.fast && p.ks == 3) {
-        // Data gradient of a stride-2 conv: a result pixel (ho, wo) is reached only by the taps with
-        // kh = (ho + pad) mod 2 (mod 2), same for kw - 1, 2, 2 or 4 of the 9.  One launch per parity class, each a
-        // dense stride-1-like gather on the class's own grid: 2.25 taps per pixel on average instead of 9.
-        for (int ah = 0; ah < 2; ++ah)
-            for (int aw = 0; aw < 2; ++aw) {
-                ConvP q = p;
-                q.sub_h0 = (ah - p.pad) & 1; q.sub_w0 = (aw - p.pad) & 1;
-                q.sub_nH = (p.Ho - q.sub_h0 + 1) >> 1; q.sub_nW = (p.Wo - q.sub_w0 + 1) >> 1;
-                if (q.sub_nH <= 0 || q.sub_nW <= 0) continue;
-                q.ntap = 0;
-                for (int kh = ah; kh < 3; kh += 2)
-                    for (int kw = aw; kw < 3; kw += 2) {
-                        q.tap_dh[q.ntap] = (q.sub_h0 + p.pad - kh) / 2;
-                        q.tap_dw[q.ntap] = (q.sub_w0 + p.pad - kw) / 2;
-                        q.tap_wi[q.ntap] = kh * 3 + kw;
-                        ++q.ntap;
-                    }
-                q.M = p.B * q.sub_nH * q.sub_nW;
-                q.taps = q.ntap;                           // (profiling: useful FLOPs of this class)
-                q.KT = q.ntap * p.tpt;
-                const int rc = choose_and_launch(q, d->dtype, s);
-                if (rc) return rc;
-            }
-        return PSG_OK;
-    }
-    return choose_and_launch(p, d->dtype, s);
+    int rc = conv_setup(d, p);
+    if (rc) return rc;
+    ConvLaunch L[4];
+    int n = 0;
+    if ((rc = conv_plan_all(p, d->dtype, L, n))) return rc;
+    for (int i = 0; i < n; ++i)
+        if ((rc = launch_planned(L[i], d->dtype, (hipStream_t)stream))) return rc;
+    return PSG_OK;
 }
 
+int psg_conv_route(const psg_conv_desc* d, int32_t* out) {
+    PSG_REQUIRE(out, PSG_ERR_ARG, "conv_route: null pointer");
+    ConvP p;
+    int rc = conv_setup(d, p);
+    if (rc) return rc;
+    ConvLaunch L[4];
+    int n = 0;
+    if ((rc = conv_plan_all(p, d->dtype, L, n))) return rc;
+    for (int i = 0; i < 1 + 4 * PSG_CONV_ROUTE_FIELDS; ++i) out[i] = 0;
+    out[0] = n;
+    for (int i = 0; i < n; ++i) {
+        const ConvP& q = L[i].p;
+        const int32_t v[PSG_CONV_ROUTE_FIELDS] = {L[i].BM, L[i].BN, L[i].mode, q.splits, q.kt_per_split, q.tapcls, L[i].pw, L[i].epi_lds,
+                                                  L[i].mtiles, L[i].ntiles, L[i].grid, q.M, q.KT, q.sub_h0, q.sub_w0, q.sub_nH, q.sub_nW, q.ntap};
+        for (int f = 0; f < PSG_CONV_ROUTE_FIELDS; ++f) out[1 + i * PSG_CONV_ROUTE_FIELDS + f] = v[f];
+    }
+    return PSG_OK;
+}
+
+int psg_conv_set_tile(int c) { psg::g_tile = (c >= 0 && c <= 4) ? c : -1; return PSG_OK; }
 int psg_conv_set_tapclass(int on) { psg::g_tapcls = on < 0 ? 0 : (on > 2 ? 2 : on); return PSG_OK; }
 int64_t psg_conv_tapclass_launches(void) { return psg::g_tapcls_launches; }
 

@@ -1001,11 +1001,15 @@ __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(const ConvP p) 
 // dynamic LDS of a BM x BN conv_gemm_kernel: two [W tile | X tile] buffers of 128-byte rows (+ the border-class row table)
 constexpr int conv_lds(int BM, int BN, bool cls) { return 2 * (BM + BN) * 128 + (cls ? BM * 4 : 0); }
 
+// gather mode of a launch (MODE of conv_gemm_kernel) and its M-tile count: launch_conv and the host's plan (conv_gemm.hip)
+static inline int conv_mode(const ConvP& p) { return p.ntap > 0 ? 3 : (!p.fast ? 2 : (!p.transposed ? 0 : (p.stride == 1 ? 1 : 2))); }
+static inline int conv_mtiles(const ConvP& p, int BM) { return p.tapcls ? tapcls_mtiles(p, BM) : (p.M + BM - 1) / BM; }
+
 template <typename T, int BM, int BN>
 int launch_conv(const ConvP& p, hipStream_t stream) {
     const size_t lds = conv_lds(BM, BN, p.tapcls);
     ConvP q = p;
-    q.mtiles = p.tapcls ? tapcls_mtiles(p, BM) : (p.M + BM - 1) / BM;
+    q.mtiles = conv_mtiles(p, BM);
     q.ntiles = (p.N + BN - 1) / BN;
     const int grid = q.mtiles * q.ntiles * (q.splits > 1 ? q.splits : 1);
     // algorithmic bytes: every input pixel, weight and output element once (+ the epilogue's residual / saved tensors)
@@ -1014,7 +1018,7 @@ int launch_conv(const ConvP& p, hipStream_t stream) {
     ProfScope prof(p.transposed ? PROF_CONV_DGRAD : PROF_CONV_FWD, 2.0 * (double)p.M * (double)p.N * (double)p.taps * (double)p.Cin, stream, abytes);
     const ConvP fin = q;                               // (the finishing kernel runs the epilogue: it keeps the operands)
     if (q.splits > 1) { q.bias = nullptr; q.rowadd = nullptr; q.residual = nullptr; q.preact = nullptr; q.dact_u = nullptr; }
-    const int mode = p.ntap > 0 ? 3 : (!p.fast ? 2 : (!p.transposed ? 0 : (p.stride == 1 ? 1 : 2)));
+    const int mode = conv_mode(p);
     if (p.tapcls) {
         if (q.splits > 1 || (mode != 0 && mode != 1) || p.ks != 3 || p.stride != 1 || p.pad != 1 || p.Ho < 3 || p.Wo < 3)
             return set_error(PSG_ERR_ARG, "conv_gemm: border-class form needs an unsplit stride-1 3x3 pad-1 launch");

@@ -314,13 +314,20 @@ int conv_pw_set_attrs() {
     return PSG_OK;
 }
 
-int launch_conv_pw(const ConvP& p0, hipStream_t stream) {
-    ConvP p = p0;
-    p.mtiles = p.M / 128; p.ntiles = p.N / 128;
-    const int total = p.mtiles * p.ntiles;
-    int grid = 2 * avail_cus_for((double)total / 512.0);
+// tile counts and the persistent grid (resident slots, at most one per tile) of a launch conv_pw_applicable accepted
+void conv_pw_grid(const ConvP& p, int& mtiles, int& ntiles, int& grid) {
+    mtiles = p.M / 128; ntiles = p.N / 128;
+    const int total = mtiles * ntiles;
+    grid = 2 * avail_cus_for((double)total / 512.0);
     if (grid > total) grid = total;
     grid &= ~7;                                          // (a virtual block keeps its XCD: v and v + G agree mod 8)
+}
+
+int launch_conv_pw(const ConvP& p0, hipStream_t stream) {
+    ConvP p = p0;
+    int grid;
+    conv_pw_grid(p, p.mtiles, p.ntiles, grid);
+    const int total = p.mtiles * p.ntiles;
     const int ek = pw_kind(p);
     const bool aux = (p.dact_u || p.residual), pre = p.preact != nullptr;
     const int64_t ldaux = p.dact_u ? p.lddact : p.ldres;

@@ -54,6 +54,7 @@ import types
 import numpy as np
 import torch
 
+from tests.drop_ref import drop_hash_pair, drop_thresh, mix32  # noqa: F401  (re-exported)
 from tests.gemm_ref import A_FLOOR, BF16_ROUND, F32_ROUND, c_acc
 
 TWO24 = 2.0 ** -24
@@ -74,33 +75,7 @@ def _sq(n):
 
 
 # ------------------------------------------------------------------------------------------------- dropout mask restatement
-_M32 = np.uint64(0xFFFFFFFF)
-
-
-def mix32(h):
-    """psg_common.h mix32 (murmur3's 32-bit finaliser) on an array of values < 2^32, in integers only."""
-    h = np.asarray(h, dtype=np.uint64) & _M32
-    h ^= h >> np.uint64(16)
-    h = (h * np.uint64(0x85EBCA6B)) & _M32
-    h ^= h >> np.uint64(13)
-    h = (h * np.uint64(0xC2B2AE35)) & _M32
-    h ^= h >> np.uint64(16)
-    return h
-
-
-def drop_hash_pair(seed, pair):
-    """psg_common.h drop_hash_pair: one 32-bit hash for the elements 2 pair, 2 pair + 1.  seed: int < 2^64; pair: uint64 array."""
-    pair = np.asarray(pair, dtype=np.uint64)
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    lo, hi = pair & _M32, pair >> np.uint64(32)
-    t = ((hi * np.uint64(0x85EBCA77)) & _M32) ^ np.uint64(seed >> 32)
-    return mix32((((lo * np.uint64(0x9E3779B1)) & _M32) + np.uint64(seed & 0xFFFFFFFF) + t) & _M32)
-
-
-def drop_thresh(p):
-    """psg_common.h drop_thresh: floor(p 2^32) of the fp32 rate, saturated."""
-    t = float(np.float32(p)) * 4294967296.0
-    return int(min(max(t, 0.0), 4294967295.0))
+# (mix32, drop_hash_pair, drop_thresh: tests/drop_ref.py, shared with the conv epilogue's masks in tests/gemm_ref.py)
 
 
 def keep_mask(seed, BH, L, S, p):

@@ -21,11 +21,22 @@ BF16_ROUND = 2.0 ** -8        # |round(v) - v| <= 2^-8 |v| for bf16 round-to-nea
 F32_ROUND = 4 * 2.0 ** -24    # fp32 outputs: the final rounding plus the epilogue's own fp32 operations
 A_FLOOR = 2.0 ** -126         # smallest normal fp32 / bf16: values below it carry no relative precision
 # largest |d act / du| over the reals: what an accumulator error can become after the activation
-ACT_SLOPE = {"none": 1.0, "silu": 1.0998, "gelu": 1.1289}
+ACT_SLOPE = {"none": 1.0, "silu": 1.0998, "gelu": 1.1289, "relu": 1.0, "tanh": 1.0}
 # The kernels' activations are not the exact functions: bf16 launches use __expf / rcp SiLU and an erf by Abramowitz-Stegun
 # 7.1.26 (|erf error| <= 1.5e-7).  Relative to the activation's value both stay below 2^-20, except GELU near its zero at
 # u = 0 where the erf error enters as 0.5 |u| 1.5e-7; the bound adds ACT_APPROX * |u| for that.
-ACT_APPROX = {"none": 0.0, "silu": 2.0 ** -20, "gelu": 2.0 ** -20}
+# ReLU is fmaxf(x, 0): exact.  tanh is the math library's tanhf on both paths, specified to 5 ulp (OpenCL C 7.4; the HIP
+# table lists 2): 5 * 2^-24 < 2^-21 relative to |tanh u| <= |u|; its derivative is 1 - t * t of that value (act_grad /
+# act_both in psg_common.h), an absolute 2 |t| |dt| + 2^-24 <= 11 * 2^-24 < 2^-20.  tests/test_conv_ref_cpu.py evaluates
+# the psg_common.h formulas in fp32 against fp64 and checks both against these entries.
+ACT_APPROX = {"none": 0.0, "silu": 2.0 ** -20, "gelu": 2.0 ** -20, "relu": 0.0, "tanh": 2.0 ** -21}
+# largest |d^2 act / du^2| over the reals: what an accumulator error can become in a saved derivative act'(u).  (ReLU's
+# derivative is a step: see saved_dact.)
+ACT_CURV = {"none": 0.0, "silu": 0.5, "gelu": 0.7979, "relu": 0.0, "tanh": 0.7699}
+# fp32 launches were not part of the measurement behind c_acc(): tests/test_conv_ref_cpu.py holds torch's own fp32 conv2d /
+# conv_transpose2d / linear of every fp32 case of tests/conv_cases.py against check()'s bound, requires it to lie inside
+# (else the bound would be widened for fp32 alone, by four times the factor torch needs) and writes the worst ratio it
+# measured into tests/golden/REPORT_conv_routes.txt.  It lies inside, so fp32 cases use check() unwidened.
 
 
 def c_acc(K):
@@ -45,8 +56,8 @@ def c_acc(K):
 
 
 # ---------------------------------------------------------------------------------------------------------------- GEMMs
-def _geom(H, W, ks, stride):
-    pad = ks // 2
+def _geom(H, W, ks, stride, pad=None):
+    pad = ks // 2 if pad is None else pad
     return pad, (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
 
 
@@ -61,12 +72,13 @@ def _cols(xb, ks, stride, pad):
     return F.unfold(xb, ks, padding=pad, stride=stride)
 
 
-def conv_fwd(x, w, stride=1):
-    """y[b, ho, wo, o] = sum_{c, kh, kw} x[b, ho*s + kh - p, wo*s + kw - p, c] w[o, c, kh, kw] (3x3 pad 1 or 1x1 pad 0).
-    x [B, H, W, C] channels-last, w [O, C, ks, ks].  Returns (y, S) in fp64, [B, Ho, Wo, O]."""
+def conv_fwd(x, w, stride=1, pad=None):
+    """y[b, ho, wo, o] = sum_{c, kh, kw} x[b, ho*s + kh - p, wo*s + kw - p, c] w[o, c, kh, kw]; pad None: ks // 2 (3x3 pad 1,
+    1x1 pad 0), explicit for the 4x4 stride-2 convs (pad 1 or 2).  x [B, H, W, C] channels-last, any H x W, w [O, C, ks, ks].
+    Returns (y, S) in fp64, [B, Ho, Wo, O]."""
     B, H, W_, C = x.shape
     O, ks = w.shape[0], w.shape[2]
-    pad, Ho, Wo = _geom(H, W_, ks, stride)
+    pad, Ho, Wo = _geom(H, W_, ks, stride, pad)
     wm = w.detach().double().reshape(O, -1)
     wa = wm.abs()
     y = torch.empty((B, Ho, Wo, O), dtype=torch.float64, device=x.device)
@@ -81,13 +93,15 @@ def conv_fwd(x, w, stride=1):
     return y, S
 
 
-def conv_dgrad(g, w, in_hw, stride=1):
+def conv_dgrad(g, w, in_hw, stride=1, pad=None):
     """Data gradient dx = d(sum y * g)/dx of conv_fwd: the transposed conv of g [B, Ho, Wo, O] (any row stride) with
-    w [O, C, ks, ks], onto the input grid in_hw = (H, W).  Returns (dx, S) in fp64, [B, H, W, C]."""
+    w [O, C, ks, ks], onto the input grid in_hw = (H, W), square or not; 1x1 stride 2 leaves the odd positions zero.
+    Returns (dx, S) in fp64, [B, H, W, C]."""
     B, Ho, Wo, O = g.shape
     C, ks = w.shape[1], w.shape[2]
     H, W_ = in_hw
-    pad = ks // 2
+    pad = ks // 2 if pad is None else pad
+    assert (Ho, Wo) == _geom(H, W_, ks, stride, pad)[1:], "gradient grid inconsistent with the input grid"
     wt = w.detach().double().reshape(O, -1).t()
     wa = wt.abs()
     dx = torch.empty((B, H, W_, C), dtype=torch.float64, device=g.device)
@@ -181,9 +195,13 @@ def _f64(t):
 
 
 def act(u, kind):
-    """The activation in fp64: none, SiLU, or GELU in its erf form (nn.GELU())."""
+    """The activation in fp64: none, SiLU, GELU in its erf form (nn.GELU()), ReLU or tanh."""
     if kind == "none":
         return u
+    if kind == "relu":
+        return torch.clamp(u, min=0.0)
+    if kind == "tanh":
+        return torch.tanh(u)
     if kind == "silu":
         return u * torch.sigmoid(u)
     if kind == "gelu":
@@ -192,9 +210,13 @@ def act(u, kind):
 
 
 def act_grad(u, kind):
-    """d act / du in fp64."""
+    """d act / du in fp64 (ReLU: 1 for u > 0, else 0, as the kernels define it at 0)."""
     if kind == "none":
         return torch.ones_like(u)
+    if kind == "relu":
+        return (u > 0).to(u.dtype)
+    if kind == "tanh":
+        return 1.0 - torch.tanh(u) ** 2
     if kind == "silu":
         s = torch.sigmoid(u)
         return s * (1.0 + u * (1.0 - s))
@@ -256,6 +278,39 @@ def dact_mul(acc, S, dact):
     (gelu'(u) * keep / (1 - p), one value per element).  Returns (ref, S): an accumulator error is scaled by |dact| too."""
     d = _f64(dact)
     return acc * d, S * d.abs()
+
+
+def dact_u(acc, S, u, kind):
+    """The backward form without DACT_MUL: the accumulator times act'(saved u), u as the kernel read it (bf16 or fp32, used
+    exactly).  Returns (ref, S, r_extra): the kernel evaluates act' in fp32 by the psg_common.h formulas, a relative
+    4 ACT_APPROX of a derivative that is not near zero - and an absolute ACT_APPROX |acc| where it is (tanh' and GELU'
+    cancel there), which the caller adds as `extra` = ACT_APPROX[kind] * |acc|."""
+    d = act_grad(_f64(u), kind)
+    return acc * d, S * d.abs(), 4.0 * ACT_APPROX[kind]
+
+
+def saved_dact(u, Su, kind, keep=None, p=0.0):
+    """What PSG_CONV_SAVE_DACT stores in `preact`: act'(u) * keep / (1 - p) in fp64, u = acc + bias + rowadd.  Returns
+    (ref, S, extra) for check(): an accumulator error moves act'(u) by at most ACT_CURV times itself, the approximation of
+    act' is absolute ((|u| + 1) ACT_APPROX, as for GELU in the batch-256 table).  ReLU's derivative is a step at 0: an
+    element whose |u| lies within its own accumulator bound may take either side, so it gets extra = 1 there
+    (tests/test_conv_ref_cpu.py::test_relu_and_tanh_cases_exercise_the_activation bounds their number per case)."""
+    sc = 1.0 if keep is None else 1.0 / (1.0 - p)
+    m = sc if keep is None else keep.to(torch.float64) * sc
+    ref = act_grad(u, kind) * m
+    extra = (u.abs() + 1.0) * ACT_APPROX[kind] * m
+    if kind == "relu":
+        extra = extra + (u.abs() <= Su * 2.0 ** -19).to(torch.float64) * m
+    return ref, Su * ACT_CURV[kind] * m, extra
+
+
+def conv_keep_mask(seed, M, N, p):
+    """Keep mask [M, N] (bool tensor) of a psg_conv_fwd epilogue: element (m, n) has index m * N + n with m the ROW OF y
+    (not of the tile, the class or the parity grid) and N = Cout; tests/drop_ref.py restates the hash in integers."""
+    import numpy as np
+    from tests.drop_ref import keep_flat
+    idx = np.arange(M, dtype=np.uint64).reshape(M, 1) * np.uint64(N) + np.arange(N, dtype=np.uint64).reshape(1, N)
+    return torch.from_numpy(keep_flat(seed, idx, p))
 
 
 # ----------------------------------------------------------------------------------------------------------- comparator
