@@ -451,6 +451,28 @@ int64_t psg_layernorm_bwd_workspace_bytes(int64_t rows, int N);
 int psg_bert_embed_ln(const int64_t* ids, const int64_t* type_ids, const float* word_emb, const float* pos_emb,
                       const float* type_emb, const float* gamma, const float* beta, void* y, int64_t ldy, int B, int S,
                       int N, int vocab, int max_pos, int type_vocab, float eps, int dtype, psg_stream_t stream);
+/* Backward of psg_bert_embed_ln up to the tables.  z = (word_emb[id] + type_emb[type]) + pos_emb[s] is rebuilt from the fp32
+ * tables in the forward's association and its statistics in the forward's reduction order (nothing is saved).  dy has
+ * dy_dtype (row stride lddy); dz is fp32 [B*S][N] contiguous whatever dy_dtype - it is what psg_embed_scatter sums, never
+ * rounded.  dgamma / dbeta / accumulate / ws: as psg_layernorm_bwd (psg_bert_embed_ln_bwd_workspace_bytes(B*S, N) bytes).  A
+ * row whose id or type id is outside its table reads no table, gets a zero dz row and adds nothing to dgamma / dbeta. */
+int psg_bert_embed_ln_bwd(const int64_t* ids, const int64_t* type_ids, const float* word_emb, const float* pos_emb,
+                          const float* type_emb, const float* gamma, const void* dy, int64_t lddy, float* dz, float* dgamma,
+                          float* dbeta, int accumulate, int B, int S, int N, int vocab, int max_pos, int type_vocab, float eps,
+                          int dy_dtype, void* ws, int64_t ws_bytes, psg_stream_t stream);
+int64_t psg_bert_embed_ln_bwd_workspace_bytes(int64_t rows, int N);
+/* Embedding-table gradient: table_grad[k] (+)= sum of dz[perm[j]] over the run of sorted positions j with key[j] == k.
+ * key: int64 [rows], ascending; perm: int64 [rows], the dz row of each sorted position (values below rows, trusted); dz fp32
+ * rows of stride lddz; table_grad fp32 [V][N].  Keys outside [0, V) and key == skip_key (the padding index; -1: none)
+ * contribute nothing.  No float atomics: a run's rows are added in ascending j, runs are cut at every multiple of
+ * psg_embed_scatter_chunk_rows() sorted positions (at most 512), the chunks' sums go through ws and are added in chunk order,
+ * so the bits depend on (key, perm, dz) alone.  accumulate == 0 writes every row of table_grad (rows no key names and row
+ * skip_key: exact zeros); accumulate != 0 leaves those rows alone and stores old + (run sum), the add last.  ws: 16-byte
+ * aligned, at least psg_embed_scatter_workspace_bytes(rows, N) bytes (PSG_ERR_WORKSPACE otherwise). */
+int psg_embed_scatter(const float* dz, int64_t lddz, const int64_t* key, const int64_t* perm, float* table_grad, int64_t rows,
+                      int N, int64_t V, int64_t skip_key, int accumulate, void* ws, int64_t ws_bytes, psg_stream_t stream);
+int64_t psg_embed_scatter_workspace_bytes(int64_t rows, int N);
+int psg_embed_scatter_chunk_rows(void);
 
 /* ---------------------------------------------------------------------------
  * Optimizer side — improved_diffusion_trainer.py:399-413

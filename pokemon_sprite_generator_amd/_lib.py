@@ -118,6 +118,13 @@ SIGNATURES = {
                                   c_int, c_int64, c_int, c_float, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "psg_layernorm_bwd_workspace_bytes": (c_int64, [c_int64, c_int]),
     "psg_bert_embed_ln": (c_int, [c_void_p] * 8 + [c_int64] + [c_int] * 6 + [c_float, c_int, c_void_p]),
+    "psg_bert_embed_ln_bwd": (c_int, [c_void_p] * 7 + [c_int64, c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_float, c_int, c_void_p, c_int64,
+                                                                                                              c_void_p]),
+    "psg_bert_embed_ln_bwd_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "psg_embed_scatter": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_int, c_void_p, c_int64,
+                                  c_void_p]),
+    "psg_embed_scatter_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "psg_embed_scatter_chunk_rows": (c_int, []),
     "psg_sumsq_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "psg_adamw_f32": (c_int, [c_void_p] * 4 + [c_int64] + [c_float] * 5 + [c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     "psg_adamw_dev_f32": (c_int, [c_void_p] * 4 + [c_int64, c_void_p, c_void_p, c_int] + [c_float] * 4 + [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),

@@ -2,7 +2,9 @@
 //   psg_layernorm      y = LN(x [+ r]) * gamma + beta over rows of width N (BERT's two post-LNs per layer, the final
 //                      nn.LayerNorm of the TextEncoder);
 //   psg_layernorm_bwd  its backward (fine-tuning): dz, dgamma, dbeta from the forward's operands and dy;
-//   psg_bert_embed_ln  BertEmbeddings: LN(word_emb[id] + type_emb[type] + pos_emb[s]).
+//   psg_bert_embed_ln  BertEmbeddings: LN(word_emb[id] + type_emb[type] + pos_emb[s]);
+//   psg_bert_embed_ln_bwd, psg_embed_scatter  its backward (finetune_strategy 'full'): dz in fp32 + dgamma / dbeta, and the
+//                      atomic-free sum of dz rows into the word / position / token-type table gradients.
 // One wave per row (N = 768: 64 lanes x 12 values), four rows per workgroup and many workgroups per CU in flight.  A lane
 // holds its chunks of 8 consecutive values in registers from the load to the store: one pass over HBM each way.
 // Statistics are fp32 and reduced in a fixed order (per-lane chunk order, then the xor butterfly, which leaves every lane
@@ -272,6 +274,199 @@ __global__ __launch_bounds__(256) void ln_param_sum_kernel(const float* __restri
     }
 }
 
+// ------------------------------------------------------------------------------------------- BertEmbeddings backward
+// layernorm_bwd_kernel with z = (word[id] + type[tt]) + pos[s] rebuilt from the fp32 tables in embed_ln_kernel's association
+// (x_hat has the forward's bits; the forward saves nothing).  dz is fp32 whatever dy's dtype: it is what the table scatters
+// sum.  A row whose id or type id is outside its table (a NaN row of the forward) reads no table, gets a zero dz row and
+// adds nothing to dgamma / dbeta.
+template <typename TDY, int CPL, bool PG>
+__global__ __launch_bounds__(64 * LN_ROWS) void embed_ln_bwd_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ type_ids,
+                                                                     const float* __restrict__ wemb, const float* __restrict__ pemb,
+                                                                     const float* __restrict__ temb, const float* __restrict__ gamma,
+                                                                     const TDY* __restrict__ dy, int64_t lddy, float* __restrict__ dz,
+                                                                     float* __restrict__ part, int64_t rows, int S, int N, int vocab,
+                                                                     int type_vocab, float eps) {
+    __shared__ float red[LN_ROWS - 1][2][8][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nch = N >> 3;
+    const float invN = 1.0f / (float)N;
+    float ag[PG ? CPL : 1][8], ab[PG ? CPL : 1][8];
+    if (PG) {
+#pragma unroll
+        for (int i = 0; i < CPL; ++i)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { ag[i][j] = 0.f; ab[i][j] = 0.f; }
+    }
+    const int64_t row0 = ((int64_t)blockIdx.x * LN_ROWS + wave) * LNB_RPW;
+    for (int it = 0; it < LNB_RPW; ++it) {
+        const int64_t row = row0 + it;
+        if (row >= rows) break;                                   // (wave-uniform)
+        const int64_t id = ids[row];
+        const int64_t tt = type_ids ? type_ids[row] : 0;
+        float* dzrow = dz + row * N;
+        if (id < 0 || id >= vocab || tt < 0 || tt >= type_vocab) {      // (wave-uniform)
+            const float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            for (int c = lane; c < nch; c += 64) st8<float>(dzrow + 8 * c, o);
+            continue;
+        }
+        const float* wr = wemb + id * N;
+        const float* tr = temb + tt * N;
+        const float* pr = pemb + (row % S) * N;
+        float v[CPL][8], g[CPL][8];
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const int c = lane + 64 * i;
+            if (c < nch) {
+                float a[8], t[8], p[8];
+                ld8<float>(wr + 8 * c, a);
+                ld8<float>(tr + 8 * c, t);
+                ld8<float>(pr + 8 * c, p);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[i][j] = (a[j] + t[j]) + p[j];
+                ld8<TDY>(dy + row * lddy + 8 * c, g[i]);
+            }
+        }
+        float mean, rstd;
+        ln_stats<CPL>(v, lane, nch, N, eps, mean, rstd);
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const int c = lane + 64 * i;
+            if (c < nch) {
+                float gm[8];
+                ld8<float>(gamma + 8 * c, gm);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float xh = (v[i][j] - mean) * rstd;
+                    if (PG) { ag[i][j] += g[i][j] * xh; ab[i][j] += g[i][j]; }
+                    v[i][j] = xh;
+                    g[i][j] *= gm[j];
+                    s1 += g[i][j];
+                    s2 += g[i][j] * xh;
+                }
+            }
+        }
+        s1 = wave_sum(s1) * invN;
+        s2 = wave_sum(s2) * invN;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const int c = lane + 64 * i;
+            if (c < nch) {
+                float o[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) o[j] = rstd * ((g[i][j] - s1) - v[i][j] * s2);
+                st8<float>(dzrow + 8 * c, o);
+            }
+        }
+    }
+    if (PG) {                                                     // the workgroup's partial rows, as layernorm_bwd_kernel
+        float* pg = part + (int64_t)blockIdx.x * N;
+        float* pb = part + ((int64_t)gridDim.x + blockIdx.x) * N;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const int c = lane + 64 * i;
+            __syncthreads();
+            if (wave > 0) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { red[wave - 1][0][j][lane] = ag[i][j]; red[wave - 1][1][j][lane] = ab[i][j]; }
+            }
+            __syncthreads();
+            if (wave == 0 && c < nch) {
+#pragma unroll
+                for (int w = 0; w < LN_ROWS - 1; ++w)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) { ag[i][j] += red[w][0][j][lane]; ab[i][j] += red[w][1][j][lane]; }
+                st8<float>(pg + 8 * c, ag[i]);
+                st8<float>(pb + 8 * c, ab[i]);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------- embedding-table scatter-add
+// table_grad[k] (+)= sum of dz[perm[j]] over the run of sorted positions j with key[j] == k: the inverted-index form, no float
+// atomics.  The sorted positions are cut at every multiple of ES_CHUNK, so no run is summed by one wave however long it is:
+//   embed_scatter_chunk_kernel  one wave per (chunk, slab of 256 columns) walks its positions in ascending j with the column
+//                               sums in registers and, wherever the key changes (and at the chunk's end), stores the sum of
+//                               the segment to part[first position of the segment];
+//   embed_scatter_sum_kernel    the wave of a run's first position adds the run's segments in chunk order - part[j], then
+//                               part[c] for every chunk start c the run reaches - and writes old + sum (the add last) or sum.
+// Every sum's order is fixed by (key, perm) alone.  Keys outside [0, V) and key == skip_key contribute nothing and write nothing.
+constexpr int ES_CHUNK = 32;        // sorted positions per chunk (psg_embed_scatter_chunk_rows)
+constexpr int ES_COLS = 256;        // columns per wave: one f32x4 per lane
+
+__global__ __launch_bounds__(64) void embed_scatter_chunk_kernel(const float* __restrict__ dz, int64_t lddz, const int64_t* __restrict__ key,
+                                                                  const int64_t* __restrict__ perm, float* __restrict__ part,
+                                                                  int64_t rows, int N, int64_t V, int64_t skip_key) {
+    const int col = 4 * ((int)blockIdx.y * 64 + (int)threadIdx.x);
+    if (col >= N) return;
+    const int64_t j0 = (int64_t)blockIdx.x * ES_CHUNK;
+    const int64_t j1 = j0 + ES_CHUNK < rows ? j0 + ES_CHUNK : rows;
+    int64_t kcur = key[j0], seg = j0;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t jb = j0; jb < j1; jb += 4) {
+        int64_t k[4];
+        f32x4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {                             // the four rows' loads in flight together
+            const int64_t j = jb + u;
+            k[u] = j < j1 ? key[j] : -1;
+            v[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (j < j1 && k[u] >= 0 && k[u] < V && k[u] != skip_key) v[u] = *reinterpret_cast<const f32x4*>(dz + perm[j] * lddz + col);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t j = jb + u;
+            if (j < j1) {
+                if (k[u] != kcur) {                               // (wave-uniform)
+                    *reinterpret_cast<f32x4*>(part + seg * N + col) = acc;
+                    acc = f32x4{0.f, 0.f, 0.f, 0.f};
+                    kcur = k[u];
+                    seg = j;
+                }
+                acc += v[u];
+            }
+        }
+    }
+    *reinterpret_cast<f32x4*>(part + seg * N + col) = acc;
+}
+
+__global__ __launch_bounds__(256) void embed_scatter_sum_kernel(const float* __restrict__ part, const int64_t* __restrict__ key,
+                                                                 float* __restrict__ out, int64_t rows, int N, int64_t V, int64_t skip_key,
+                                                                 int accumulate) {
+    const int col = 4 * ((int)blockIdx.y * 64 + (int)(threadIdx.x & 63));
+    const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= rows || col >= N) return;
+    const int64_t k = key[j];
+    if (k < 0 || k >= V || k == skip_key) return;                 // (wave-uniform, as every branch below)
+    if (j > 0 && key[j - 1] == k) return;                         // not the first position of its run
+    f32x4 acc = *reinterpret_cast<const f32x4*>(part + j * N + col);
+    int64_t c = (j / ES_CHUNK + 1) * ES_CHUNK;
+    while (c < rows && key[c] == k) {
+        f32x4 v[4] = {};
+        int n = 0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {                             // up to four segments' loads in flight; added in chunk order
+            if (c < rows && key[c] == k) {
+                v[u] = *reinterpret_cast<const f32x4*>(part + c * N + col);
+                c += ES_CHUNK;
+                n = u + 1;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (u < n) acc += v[u];
+    }
+    float* o = out + k * N + col;
+    if (accumulate) acc = *reinterpret_cast<const f32x4*>(o) + acc;
+    *reinterpret_cast<f32x4*>(o) = acc;
+}
+
+__global__ __launch_bounds__(256) void zero_f32x4_kernel(float* __restrict__ p, int64_t n4) {
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) reinterpret_cast<f32x4*>(p)[i] = z;
+}
+
 using LnCpls = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8>;      // 16-byte chunks per lane: every N row_width_check admits
 
 static int row_width_check(const char* who, int N) {
@@ -368,6 +563,78 @@ int psg_bert_embed_ln(const int64_t* ids, const int64_t* type_ids, const float* 
                            type_ids, word_emb, pos_emb, type_emb, gamma, beta, (TO*)y, ldy, rows, S, N, vocab, type_vocab, eps);
     }); });
     PSG_LAUNCH_CHECK("bert_embed_ln");
+    return PSG_OK;
+}
+
+int64_t psg_bert_embed_ln_bwd_workspace_bytes(int64_t rows, int N) { return psg_layernorm_bwd_workspace_bytes(rows, N); }
+
+int psg_bert_embed_ln_bwd(const int64_t* ids, const int64_t* type_ids, const float* word_emb, const float* pos_emb,
+                          const float* type_emb, const float* gamma, const void* dy, int64_t lddy, float* dz, float* dgamma,
+                          float* dbeta, int accumulate, int B, int S, int N, int vocab, int max_pos, int type_vocab, float eps,
+                          int dy_dtype, void* ws, int64_t ws_bytes, psg_stream_t stream) {
+    PSG_REQUIRE(ids && word_emb && pos_emb && type_emb && gamma && dy && dz, PSG_ERR_ARG, "bert_embed_ln_bwd: null pointer");
+    PSG_REQUIRE(dy_dtype == PSG_F32 || dy_dtype == PSG_BF16, PSG_ERR_DTYPE, "bert_embed_ln_bwd: dtype %d", dy_dtype);
+    { const int rc = row_width_check("bert_embed_ln_bwd", N); if (rc) return rc; }
+    PSG_REQUIRE(B > 0 && S > 0 && vocab > 0 && type_vocab > 0 && max_pos > 0, PSG_ERR_SHAPE, "bert_embed_ln_bwd: non-positive dimension");
+    PSG_REQUIRE(S <= max_pos, PSG_ERR_SHAPE, "bert_embed_ln_bwd: S=%d exceeds the %d position embeddings", S, max_pos);
+    PSG_REQUIRE(eps >= 0.f, PSG_ERR_ARG, "bert_embed_ln_bwd: eps %g", (double)eps);
+    PSG_REQUIRE(lddy >= N, PSG_ERR_SHAPE, "bert_embed_ln_bwd: row stride < N");
+    PSG_REQUIRE((lddy & 7) == 0 && aligned16(dy) && aligned16(dz) && aligned16(word_emb) && aligned16(pos_emb) && aligned16(type_emb) &&
+                aligned16(gamma), PSG_ERR_ALIGN, "bert_embed_ln_bwd: tables and rows must start on 16-byte boundaries");
+    const int64_t rows = (int64_t)B * S;
+    const bool pg = dgamma || dbeta;
+    PSG_REQUIRE(!pg || ws, PSG_ERR_ARG, "bert_embed_ln_bwd: dgamma / dbeta need a workspace");
+    PSG_REQUIRE(!pg || aligned16(ws), PSG_ERR_ALIGN, "bert_embed_ln_bwd: workspace must start on a 16-byte boundary");
+    PSG_REQUIRE(!pg || ws_bytes >= psg_bert_embed_ln_bwd_workspace_bytes(rows, N), PSG_ERR_WORKSPACE,
+                "bert_embed_ln_bwd: workspace of %ld bytes, need %ld", (long)ws_bytes, (long)psg_bert_embed_ln_bwd_workspace_bytes(rows, N));
+    const int cpl = (N / 8 + 63) / 64;
+    const int nwg = (int)((rows + LNB_WG_ROWS - 1) / LNB_WG_ROWS);
+    hipStream_t s = (hipStream_t)stream;
+    with_dtype(dy_dtype, [&](auto tdy) { with_const(LnCpls{}, cpl, [&](auto c) { with_const(Bools{}, pg, [&](auto p) {
+        using TDY = decltype(tdy);
+        hipLaunchKernelGGL((embed_ln_bwd_kernel<TDY, decltype(c)::value, decltype(p)::value>), dim3((unsigned)nwg), dim3(64 * LN_ROWS), 0, s, ids,
+                           type_ids, word_emb, pos_emb, type_emb, gamma, (const TDY*)dy, lddy, dz, (float*)ws, rows, S, N, vocab, type_vocab, eps);
+    }); }); });
+    PSG_LAUNCH_CHECK("bert_embed_ln_bwd");
+    if (pg) {
+        hipLaunchKernelGGL(ln_param_sum_kernel, dim3((unsigned)((N + 63) / 64), 2), dim3(256), 0, s, (const float*)ws, nwg, N, dgamma, dbeta, accumulate);
+        PSG_LAUNCH_CHECK("bert_embed_ln_bwd_param_sum");
+    }
+    return PSG_OK;
+}
+
+int psg_embed_scatter_chunk_rows(void) { return ES_CHUNK; }
+
+int64_t psg_embed_scatter_workspace_bytes(int64_t rows, int N) {
+    if (rows <= 0 || N <= 0) return 0;
+    return rows * (int64_t)N * (int64_t)sizeof(float);
+}
+
+int psg_embed_scatter(const float* dz, int64_t lddz, const int64_t* key, const int64_t* perm, float* table_grad, int64_t rows,
+                      int N, int64_t V, int64_t skip_key, int accumulate, void* ws, int64_t ws_bytes, psg_stream_t stream) {
+    PSG_REQUIRE(dz && key && perm && table_grad && ws, PSG_ERR_ARG, "embed_scatter: null pointer");
+    { const int rc = row_width_check("embed_scatter", N); if (rc) return rc; }
+    PSG_REQUIRE(rows > 0 && rows <= (int64_t)0x7FFFFFFF && V > 0 && V <= (int64_t)0x7FFFFFFF, PSG_ERR_SHAPE,
+                "embed_scatter: rows=%ld, V=%ld", (long)rows, (long)V);
+    PSG_REQUIRE(lddz >= N, PSG_ERR_SHAPE, "embed_scatter: row stride < N");
+    PSG_REQUIRE((lddz & 3) == 0 && aligned16(dz) && aligned16(table_grad) && aligned16(ws), PSG_ERR_ALIGN,
+                "embed_scatter: rows, table and workspace must start on 16-byte boundaries");
+    PSG_REQUIRE(ws_bytes >= psg_embed_scatter_workspace_bytes(rows, N), PSG_ERR_WORKSPACE, "embed_scatter: workspace of %ld bytes, need %ld",
+                (long)ws_bytes, (long)psg_embed_scatter_workspace_bytes(rows, N));
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned slabs = (unsigned)((N + ES_COLS - 1) / ES_COLS);
+    if (!accumulate) {
+        const int64_t n4 = V * (int64_t)N / 4;
+        const int64_t wgs = (n4 + 255) / 256;
+        hipLaunchKernelGGL(zero_f32x4_kernel, dim3((unsigned)(wgs < 4096 ? wgs : 4096)), dim3(256), 0, s, table_grad, n4);
+        PSG_LAUNCH_CHECK("embed_scatter_zero");
+    }
+    hipLaunchKernelGGL(embed_scatter_chunk_kernel, dim3((unsigned)((rows + ES_CHUNK - 1) / ES_CHUNK), slabs), dim3(64), 0, s, dz, lddz, key, perm,
+                       (float*)ws, rows, N, V, skip_key);
+    PSG_LAUNCH_CHECK("embed_scatter_chunk");
+    hipLaunchKernelGGL(embed_scatter_sum_kernel, dim3((unsigned)((rows + 3) / 4), slabs), dim3(256), 0, s, (const float*)ws, key, table_grad, rows, N,
+                       V, skip_key, accumulate);
+    PSG_LAUNCH_CHECK("embed_scatter_sum");
     return PSG_OK;
 }
 

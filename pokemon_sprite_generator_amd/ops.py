@@ -1140,6 +1140,103 @@ def layer_norm(x, weight, bias, eps, residual=None, out_dtype=None):
 
 
 # ---------------------------------------------------------------------------
+# BertEmbeddings
+# ---------------------------------------------------------------------------
+_pos_index = {}
+
+
+def _position_runs(B, S, device):
+    """(key, perm) of the position table's scatter: key = t % S of the rows t = b*S + s in ascending order, ties in ascending b."""
+    k = (B, S, device)
+    if k not in _pos_index:
+        j = torch.arange(B * S, dtype=torch.int64, device=device)
+        _pos_index[k] = (j // B, (j % B) * S + j // B)
+    return _pos_index[k]
+
+
+class _BertEmbedFn(torch.autograd.Function):
+    """y = dropout(LayerNorm(word[ids] + type[type_ids] + pos[s])): psg_bert_embed_ln (+ psg_dropout_apply in place), and its
+    backward psg_bert_embed_ln_bwd + one psg_embed_scatter per table whose gradient is wanted.  Only the ids are kept; the keys
+    are sorted on the device (integer plumbing), nothing synchronises with the host."""
+
+    @staticmethod
+    def forward(ctx, ids, type_ids, word, pos, typ, gamma, beta, eps, pad_id, dtype, drop_p, seed):
+        lib = _lib_for(word)
+        B, S = ids.shape
+        V, N = word.shape
+        y = torch.empty((B * S, N), dtype=dtype, device=word.device)
+        check(lib.psg_bert_embed_ln(ptr(ids), ptr(type_ids), ptr(word), ptr(pos), ptr(typ), ptr(gamma), ptr(beta), ptr(y), N, B, S, N, V,
+                                    pos.shape[0], typ.shape[0], float(eps), dtype_code(dtype), stream_ptr()), "psg_bert_embed_ln")
+        if drop_p > 0:
+            check(lib.psg_dropout_apply(ptr(y), N, ptr(y), N, B * S, N, drop_p, seed, 1.0 / (1.0 - drop_p), dtype_code(dtype), stream_ptr()),
+                  "psg_dropout_apply")
+        ctx.save_for_backward(ids, type_ids, word, pos, typ, gamma)
+        ctx.params = (word, pos, typ, gamma, beta)
+        ctx.meta = (B, S, float(eps), int(pad_id), float(drop_p), seed)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ids, type_ids, word, pos, typ, gamma = ctx.saved_tensors
+        B, S, eps, pad_id, drop_p, seed = ctx.meta
+        p_word, p_pos, p_typ, p_gamma, p_beta = ctx.params
+        V, N = word.shape
+        rows = B * S
+        lib = _lib_for(dy)
+        dev = dy.device
+        dyr, lddy = _rows(dy)
+        if drop_p > 0:
+            g = torch.empty((rows, N), dtype=dy.dtype, device=dev)
+            check(lib.psg_dropout_apply(ptr(dyr), lddy, ptr(g), N, rows, N, drop_p, seed, 1.0 / (1.0 - drop_p), dtype_code(dy.dtype), stream_ptr()),
+                  "psg_dropout_apply")
+            dyr, lddy = g, N
+        want_w, want_p, want_t, want_g, want_b = ctx.needs_input_grad[2:7]
+        need = max(lib.psg_bert_embed_ln_bwd_workspace_bytes(rows, N) if (want_g or want_b) else 0,
+                   lib.psg_embed_scatter_workspace_bytes(rows, N) if (want_w or want_p or want_t) else 0)
+        ws = _lib.workspace(need, dev) if need else None
+        nws = ws.numel() if ws is not None else 0
+        go, gacc, ge = _param_out(p_gamma) if want_g else (None, False, None)
+        bo, bacc, be = _param_out(p_beta) if want_b else (None, False, None)
+        bo2 = torch.zeros_like(bo) if (want_g and want_b and gacc != bacc) else bo      # one accumulate flag per launch
+        dz = torch.empty((rows, N), dtype=torch.float32, device=dev)
+        check(lib.psg_bert_embed_ln_bwd(ptr(ids), ptr(type_ids), ptr(word), ptr(pos), ptr(typ), ptr(gamma), ptr(dyr), lddy, ptr(dz), ptr(go),
+                                        ptr(bo2), int(gacc if want_g else bacc), B, S, N, V, pos.shape[0], typ.shape[0], eps,
+                                        dtype_code(dy.dtype), ptr(ws), nws, stream_ptr()), "psg_bert_embed_ln_bwd")
+        if bo2 is not bo:
+            bo.add_(bo2) if bacc else bo.copy_(bo2)
+
+        def scatter(param, key, perm, skip):
+            out, acc, e = _param_out(param)
+            if not out.is_contiguous():
+                raise _lib.PsgError("bert_embed: the gradient of an embedding table must be a contiguous [V, N] tensor")
+            check(lib.psg_embed_scatter(ptr(dz), N, ptr(key), ptr(perm), ptr(out), rows, N, param.shape[0], skip, int(acc), ptr(ws), nws,
+                                        stream_ptr()), "psg_embed_scatter")
+            return _param_ret(out, e)
+
+        dw = dp = dt = None
+        if want_w:
+            dw = scatter(p_word, *torch.sort(ids.view(-1), stable=True), pad_id)
+        if want_p:
+            dp = scatter(p_pos, *_position_runs(B, S, dev), -1)
+        if want_t:
+            if type_ids is None:                     # every row is type 0: one run in row order
+                order = _position_runs(1, rows, dev)[1]
+                dt = scatter(p_typ, torch.zeros_like(order), order, -1)
+            else:
+                dt = scatter(p_typ, *torch.sort(type_ids.view(-1), stable=True), -1)
+        dg = _param_ret(go, ge) if want_g else None
+        db = _param_ret(bo, be) if want_b else None
+        return None, None, dw, dp, dt, dg, db, None, None, None, None, None
+
+
+def bert_embed(ids, type_ids, word, pos, typ, gamma, beta, eps, pad_id=0, dtype=torch.float32, drop_p=0.0, seed=0):
+    """transformers' BertEmbeddings over token ids [B, S] (int64, contiguous; type_ids the same or None) -> [B*S, N] rows in
+    `dtype`, with the embedding dropout drawn from `seed` when drop_p > 0; fp32 tables and LayerNorm parameters, whose gradients
+    the backward produces (row `pad_id` of the word table gets none, as nn.Embedding's padding_idx)."""
+    return _BertEmbedFn.apply(ids, type_ids, word, pos, typ, gamma, beta, eps, pad_id, dtype, drop_p, seed)
+
+
+# ---------------------------------------------------------------------------
 # attention core
 # ---------------------------------------------------------------------------
 class _AttnFn(torch.autograd.Function):

@@ -22,7 +22,10 @@ pooler is kept for checkpoint interchange only: the reference returns `last_hidd
 By default (`trainable=False`) the class is inference only: every parameter frozen, `torch.no_grad()`, `.train()` ignored;
 `finetune_strategy` is validated and otherwise unused.  With `trainable=True` the strategy is applied as the reference
 applies it ('none': BERT frozen; 'minimal': last 2 encoder layers + pooler; 'partial': last 4 + pooler; `projection` and
-`layer_norm` always trainable; 'full' raises - the embedding gradients are not built).  When grad mode is on, the frozen
+`layer_norm` always trainable; 'full' raises unless `train_embeddings=True` is passed as well: then every `bert.*` parameter
+trains, the word / position / token-type tables and their LayerNorm through `ops.bert_embed`, whose backward is
+psg_bert_embed_ln_bwd + one atomic-free psg_embed_scatter per table; row `pad_token_id` of the word table - an optional
+`bert_config` key, default 0 - gets no gradient, as nn.Embedding's padding_idx).  When grad mode is on, the frozen
 prefix runs under no_grad on the inference launches and the trainable suffix through the autograd nodes of `ops`
 (`qkv_linear`, `attention_self(kv_len=)`, `linear`, `layer_norm`): autograd stops at the first trainable layer's input, and
 nothing of the prefix is kept.  Parameters and gradients are fp32 (`p.grad`), the activations `compute_dtype`.  `.train()`
@@ -47,6 +50,7 @@ CONFIG_KEYS = ("hidden_size", "num_hidden_layers", "num_attention_heads", "inter
                "max_position_embeddings", "type_vocab_size", "layer_norm_eps")
 FINETUNE_STRATEGIES = ("none", "minimal", "partial", "full")
 DROPOUT_KEYS = ("hidden_dropout_prob", "attention_probs_dropout_prob")      # optional `bert_config` keys (BertConfig defaults: 0.1)
+PAD_KEY = "pad_token_id"            # optional `bert_config` key (BertConfig default: 0): word_embeddings.padding_idx
 MAX_LENGTH = 256                    # the reference tokenizer call's max_length (text_encoder.py forward)
 
 
@@ -58,6 +62,9 @@ def config_dict(cfg):
         v = cfg.get(k) if isinstance(cfg, dict) else getattr(cfg, k, None)
         if v is not None:
             out[k] = float(v)
+    v = cfg.get(PAD_KEY) if isinstance(cfg, dict) else getattr(cfg, PAD_KEY, None)
+    if v is not None:
+        out[PAD_KEY] = int(v)
     out["layer_norm_eps"] = float(out["layer_norm_eps"])
     for k in CONFIG_KEYS[:-1]:
         out[k] = int(out[k])
@@ -128,7 +135,7 @@ class _Embeddings(nn.Module):
     def __init__(self, c):
         super().__init__()
         H = c["hidden_size"]
-        self.word_embeddings = nn.Embedding(c["vocab_size"], H, padding_idx=0)
+        self.word_embeddings = nn.Embedding(c["vocab_size"], H, padding_idx=c.get(PAD_KEY, 0))
         self.position_embeddings = nn.Embedding(c["max_position_embeddings"], H)
         self.token_type_embeddings = nn.Embedding(c["type_vocab_size"], H)
         self.LayerNorm = nn.LayerNorm(H, eps=c["layer_norm_eps"])
@@ -190,13 +197,14 @@ class TextEncoder(nn.Module):
     with `trainable=True` fine-tuned under `finetune_strategy`."""
 
     def __init__(self, model_name='google-bert/bert-base-uncased', hidden_dim=768, finetune_strategy='minimal', *,
-                 compute_dtype=torch.float32, tokenizer=None, bert_config=None, trainable=False):
+                 compute_dtype=torch.float32, tokenizer=None, bert_config=None, trainable=False, train_embeddings=False):
         super().__init__()
         if finetune_strategy not in FINETUNE_STRATEGIES:
             raise ValueError(f"Unknown finetune_strategy: {finetune_strategy}")
-        if trainable and finetune_strategy == "full":
+        if trainable and finetune_strategy == "full" and not train_embeddings:
             raise _lib.PsgError("TextEncoder(trainable=True, finetune_strategy='full'): the embedding gradients (word / position / "
-                                "token-type tables and their LayerNorm) are not built; use 'none', 'minimal' or 'partial'")
+                                "token-type tables and their LayerNorm) are not built; use 'none', 'minimal' or 'partial', or pass "
+                                "train_embeddings=True to train the embedding tables too")
         state = None
         if bert_config is None:                          # pretrained weights and tokenizer from the local HF cache
             tok, cfg, state = _from_pretrained(model_name)
@@ -206,6 +214,8 @@ class TextEncoder(nn.Module):
         self.model_name, self.finetune_strategy = model_name, finetune_strategy
         self.compute_dtype = compute_dtype
         self.trainable = bool(trainable)
+        self.train_embeddings = bool(train_embeddings)
+        self.pad_token_id = int(cfg.get(PAD_KEY, 0))
         self.hidden_dropout_prob = float(cfg.get("hidden_dropout_prob", 0.1))
         self.attention_probs_dropout_prob = float(cfg.get("attention_probs_dropout_prob", 0.1))
         self.tokenizer = tokenizer
@@ -226,6 +236,10 @@ class TextEncoder(nn.Module):
         for p in self.parameters():
             p.requires_grad = False
         if not self.trainable:
+            return
+        if self.finetune_strategy == "full":         # (reached with train_embeddings=True only) the reference unfreezes all of bert
+            for p in self.parameters():
+                p.requires_grad = True
             return
         n = len(self.bert.encoder.layer)
         last = {"none": 0, "minimal": 2, "partial": 4}[self.finetune_strategy]
@@ -250,10 +264,11 @@ class TextEncoder(nn.Module):
         return super().train(mode and self.trainable)
 
     @classmethod
-    def from_reference(cls, enc, compute_dtype=torch.float32, trainable=False):
+    def from_reference(cls, enc, compute_dtype=torch.float32, trainable=False, train_embeddings=False):
         """A reference TextEncoder instance -> this class with its tokenizer, configuration and weights (copied)."""
         obj = cls(hidden_dim=enc.layer_norm.normalized_shape[0], finetune_strategy=getattr(enc, "finetune_strategy", "minimal"),
-                  compute_dtype=compute_dtype, tokenizer=enc.tokenizer, bert_config=config_dict(enc.bert.config), trainable=trainable)
+                  compute_dtype=compute_dtype, tokenizer=enc.tokenizer, bert_config=config_dict(enc.bert.config), trainable=trainable,
+                  train_embeddings=train_embeddings)
         own = obj.state_dict()
         obj.load_state_dict({k: v.detach().clone() for k, v in enc.state_dict().items() if k in own}, strict=True)
         return obj.to(next(enc.parameters()).device)
@@ -359,13 +374,22 @@ class TextEncoder(nn.Module):
         B, S = ids.shape
         ph, pa = (self.hidden_dropout_prob, self.attention_probs_dropout_prob) if drop else (0.0, 0.0)
         first = self.first_trainable_layer()
+        emb = self.bert.embeddings
+        emb_params = [emb.word_embeddings.weight, emb.position_embeddings.weight, emb.token_type_embeddings.weight, emb.LayerNorm.weight,
+                      emb.LayerNorm.bias]
+        train_emb = torch.is_grad_enabled() and any(p.requires_grad for p in emb_params)
+        if train_emb:                               # 'full': the embedding is a node too (same launches, same seed draw, same bits)
+            first = 0                               # (every layer carries its gradient, trainable or not)
+            x = ops.bert_embed(ids, tt, *emb_params, self.bert.config["layer_norm_eps"], self.pad_token_id, dt, ph,
+                               _SeedStream.next() if ph > 0 else 0)
         with torch.no_grad():                       # the frozen prefix: no graph, no saved activation
-            x = self._embed(ids, tt, B, S, dt, dev)
-            if ph > 0:                              # BertEmbeddings' dropout, in place
-                lib = ops._lib_for(x)
-                H = x.shape[1]
-                check(lib.psg_dropout_apply(ptr(x), H, ptr(x), H, B * S, H, ph, _SeedStream.next(), 1.0 / (1.0 - ph), dtype_code(dt),
-                                            stream_ptr()), "psg_dropout_apply")
+            if not train_emb:
+                x = self._embed(ids, tt, B, S, dt, dev)
+                if ph > 0:                          # BertEmbeddings' dropout, in place
+                    lib = ops._lib_for(x)
+                    H = x.shape[1]
+                    check(lib.psg_dropout_apply(ptr(x), H, ptr(x), H, B * S, H, ph, _SeedStream.next(), 1.0 / (1.0 - ph), dtype_code(dt),
+                                                stream_ptr()), "psg_dropout_apply")
             for i in range(first):
                 x = self._layer_autograd(i, x, kv_len, B, S, ph, pa) if drop else self._layer_infer(i, x, kv_len, B, S)
         for i in range(first, len(self.bert.encoder.layer)):

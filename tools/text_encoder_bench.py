@@ -13,7 +13,13 @@ with the additive finfo.min padding mask / F.layer_norm in the same dtype.  Ever
 --train: instead of the frozen forward, forward + backward of `TextEncoder(trainable=True)` under 'minimal' and 'partial'
          (eval mode, a fixed cotangent, gradients into p.grad) next to torch autograd over the same restatement and weights;
          FLOP = the forward's + 2x the trainable layers' (data and weight gradients; the first trainable layer's QKV data
-         gradient is not computed and not counted).
+         gradient is not computed and not counted).  `--strategies full` builds the encoder with train_embeddings=True: the
+         embedding tables train too (there the first layer's QKV data gradient is computed, and counted).
+--embed: the embedding backward alone at bert-base tables, (B, S) of --pairs: dropout mask, psg_bert_embed_ln_bwd, the device
+         sort and the three psg_embed_scatter launches (94 MB zero-fill of the word-table gradient included) through
+         `ops.bert_embed`'s backward, alternating call by call with torch autograd over F.embedding x 3 + F.layer_norm +
+         F.dropout on the same tables; and, through the C ABI, the share of the kernel sequence that is the zero-fill
+         (accumulate = 0 against accumulate = 1 on the word table).
 """
 import argparse
 import ctypes as C
@@ -95,6 +101,88 @@ def timed(fn, iters, warmup):
     return a.elapsed_time(b) / iters
 
 
+def timed_alternating(f1, f2, iters, warmup):
+    """ms per call of f1 and of f2, run in turns (f1, f2, f1, ...) so that both see the same machine state."""
+    for _ in range(warmup):
+        f1()
+        f2()
+    torch.cuda.synchronize()
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(iters)]
+    for a, b, c in ev:
+        a.record()
+        f1()
+        b.record()
+        f2()
+        c.record()
+    torch.cuda.synchronize()
+    return sum(a.elapsed_time(b) for a, b, _ in ev) / iters, sum(b.elapsed_time(c) for _, b, c in ev) / iters
+
+
+def embed_legs(args, lib, dev, dts, rows):
+    from pokemon_sprite_generator_amd import _lib, ops
+    from pokemon_sprite_generator_amd._lib import check, dtype_code, ptr, stream_ptr
+    c, p, seed = BERT_BASE, 0.1, 4321
+    V, P, N, eps = c["vocab_size"], c["max_position_embeddings"], c["hidden_size"], c["layer_norm_eps"]
+    g = torch.Generator(device=dev).manual_seed(0)
+    tabs = [0.02 * torch.randn(s, device=dev, generator=g) for s in ((V, N), (P, N), (2, N))]
+    tabs += [1.0 + 0.1 * torch.randn(N, device=dev, generator=g), 0.02 * torch.randn(N, device=dev, generator=g)]
+    params = [t.requires_grad_(True) for t in tabs]
+    word, pos, typ, gamma, beta = params
+    print(f"{'dtype':5} {'B':>4} {'S':>4} {'embed bwd ms':>12} {'torch ms':>9} {'speedup':>7} | {'kernels ms':>10} {'acc=1 ms':>9} {'zero-fill':>9}")
+    for dn in args.dtypes.split(","):
+        dt = dts[dn]
+        for B, S in (tuple(int(v) for v in pr.split("x")) for pr in args.pairs.split(",")):
+            rows_ = B * S
+            ids = torch.randint(1000, 30000, (B, S), device=dev)
+            ids[:, S - S // 4:] = 0                                               # a quarter of right padding
+            tt = (torch.arange(S, device=dev)[None] >= S // 3).long().expand(B, S).contiguous()
+            G = torch.randn(rows_, N, device=dev).to(dt)
+            y = ops.bert_embed(ids, tt, word, pos, typ, gamma, beta, eps, 0, dt, p, seed)
+            torch.manual_seed(0)
+            z = (F.embedding(ids, word, padding_idx=0) + F.embedding(tt, typ)) + F.embedding(torch.arange(S, device=dev)[None].expand(B, S), pos)
+            yt = F.dropout(F.layer_norm(z, (N,), gamma, beta, eps).to(dt), p, training=True).view(rows_, N)
+
+            def clear():
+                for q in params:
+                    q.grad = None
+
+            def ours():
+                clear()
+                y.backward(G, retain_graph=True)
+
+            def theirs():
+                clear()
+                yt.backward(G, retain_graph=True)
+
+            ms, tms = timed_alternating(ours, theirs, args.iters, args.warmup)
+            clear()
+            # the kernel sequence through the C ABI, word table written (zero-fill) or accumulated into
+            need = max(lib.psg_bert_embed_ln_bwd_workspace_bytes(rows_, N), lib.psg_embed_scatter_workspace_bytes(rows_, N))
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            g2, dz = torch.empty_like(G), torch.empty(rows_, N, device=dev)
+            outs = [torch.zeros_like(t) for t in tabs]
+            j = torch.arange(rows_, device=dev)
+            pk, pp = j // B, (j % B) * S + j // B
+
+            def seq(acc):
+                check(lib.psg_dropout_apply(ptr(G), N, ptr(g2), N, rows_, N, p, seed, 1.0 / (1.0 - p), dtype_code(dt), stream_ptr()), "dropout")
+                check(lib.psg_bert_embed_ln_bwd(ptr(ids), ptr(tt), ptr(word), ptr(pos), ptr(typ), ptr(gamma), ptr(g2), N, ptr(dz), ptr(outs[3]),
+                                                ptr(outs[4]), 0, B, S, N, V, P, 2, eps, dtype_code(dt), ptr(ws), need, stream_ptr()), "embed_ln_bwd")
+                wk, wp = torch.sort(ids.view(-1), stable=True)
+                tk, tp = torch.sort(tt.view(-1), stable=True)
+                for out, key, perm, skip, a in ((outs[0], wk, wp, 0, acc), (outs[1], pk, pp, -1, 0), (outs[2], tk, tp, -1, 0)):
+                    check(lib.psg_embed_scatter(ptr(dz), N, ptr(key), ptr(perm), ptr(out), rows_, N, out.shape[0], skip, a, ptr(ws), need,
+                                                stream_ptr()), "embed_scatter")
+
+            with torch.no_grad():
+                k0, k1 = timed_alternating(lambda: seq(0), lambda: seq(1), args.iters, args.warmup)
+            r = {"leg": "embed_bwd", "dtype": dn, "B": B, "S": S, "ms": ms, "torch_ms": tms, "speedup": tms / ms, "kernels_ms": k0,
+                 "kernels_accumulate_ms": k1, "zero_fill_share": (k0 - k1) / k0}
+            rows.append(r)
+            print(f"{dn:5} {B:4d} {S:4d} {ms:12.3f} {tms:9.3f} {r['speedup']:7.2f} | {k0:10.3f} {k1:9.3f} {100 * r['zero_fill_share']:8.1f}%", flush=True)
+            del y, yt, z
+
+
 def train_legs(args, lib, dev, dts, rows):
     def counts():
         m, v, f = C.c_int64(), C.c_int64(), C.c_int64()
@@ -103,7 +191,7 @@ def train_legs(args, lib, dev, dts, rows):
 
     print(f"{'strategy':8} {'dtype':5} {'B':>4} {'S':>4} {'fwd+bwd ms':>10} {'TFLOP/s':>8} {'attn family':>12} | {'torch ms':>9} {'TFLOP/s':>8} {'speedup':>7}")
     for strat in args.strategies.split(","):
-        enc = build(dev, finetune_strategy=strat, trainable=True)
+        enc = build(dev, finetune_strategy=strat, trainable=True, train_embeddings=True)      # (the keyword matters to 'full' only)
         trained = len(enc.bert.encoder.layer) - enc.first_trainable_layer()
         for dn in args.dtypes.split(","):
             enc.compute_dtype = dts[dn]
@@ -129,7 +217,7 @@ def train_legs(args, lib, dev, dts, rows):
                     fam = ["bf16-mfma", "valu", "fp32-mfma"][max(range(3), key=lambda i: c1[i] - c0[i])]
                     ms = timed(ours, args.iters, args.warmup)
                     tms = timed(theirs, args.iters, args.warmup)
-                    fl = train_flop_per_call(B, S, trained)
+                    fl = train_flop_per_call(B, S, trained) + (B * S * 2.0 * 768 * 3 * 768 if strat == "full" else 0.0)
                     r = {"strategy": strat, "trained_layers": trained, "dtype": dn, "B": B, "S": S, "ms": ms, "tflops": fl / ms / 1e9,
                          "attn_family": fam, "attn_launches": [c1[i] - c0[i] for i in range(3)], "torch_ms": tms, "torch_tflops": fl / tms / 1e9,
                          "speedup": tms / ms}
@@ -151,18 +239,20 @@ def main():
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--train", action="store_true")
     ap.add_argument("--strategies", default="minimal,partial")
+    ap.add_argument("--embed", action="store_true")
+    ap.add_argument("--pairs", default="16x64,64x256", help="--embed: BxS pairs")
     args = ap.parse_args()
     from pokemon_sprite_generator_amd import _lib
     dev = torch.device("cuda", 0)
     lib = _lib.init(0)
     dts = {"bf16": torch.bfloat16, "fp32": torch.float32}
     rows = []
-    if args.train:
-        train_legs(args, lib, dev, dts, rows)
+    if args.train or args.embed:
+        (embed_legs if args.embed else train_legs)(args, lib, dev, dts, rows)
         if args.json:
             os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
             with open(args.json, "w") as f:
-                json.dump({"tool": "tools/text_encoder_bench.py --train", "iters": args.iters, "warmup": args.warmup, "rows": rows}, f, indent=1)
+                json.dump({"tool": "tools/text_encoder_bench.py " + ("--embed" if args.embed else "--train"), "iters": args.iters, "warmup": args.warmup, "rows": rows}, f, indent=1)
         return
     enc = build(dev)
     print(f"{'dtype':5} {'B':>4} {'S':>4} {'ms':>9} {'TFLOP/s':>8} {'launch':>6} {'attn family':>12} | {'torch ms':>9} {'TFLOP/s':>8} {'speedup':>7}")
