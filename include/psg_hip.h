@@ -126,6 +126,55 @@ int psg_recon_loss_f32(const float* pred, const float* target, float* grad, floa
 int64_t psg_recon_loss_workspace_bytes(void);
 
 /* ---------------------------------------------------------------------------
+ * Stage 1's loss around the VGG16 convolutions (perceptual.hip) - src/models/losses.py: CombinedLoss = L1 + 0.1 * VGG16
+ * perceptual + beta * KL, used on every batch by vae_trainer.py:214,249-286.  The convolutions are psg_conv_fwd with the ReLU
+ * epilogue; these are the passes between them.  Channels-last operands are rows of C channels with a row stride ld (elements):
+ * C and ld are whole 16-byte chunks (multiples of 4 for fp32, 8 for bf16) and the base is 16-byte aligned (PSG_ERR_SHAPE /
+ * PSG_ERR_ALIGN otherwise).  No atomics; the same inputs give the same bits.
+ * ------------------------------------------------------------------------- */
+/* nn.MaxPool2d(kernel_size=2, stride=2) of torchvision's vgg16().features (indices 4, 9, 16 under losses.py:56-57): x
+ * [B,Hi,Wi,C] -> y [B,Hi/2,Wi/2,C], floor (the last row / column of an odd Hi / Wi is dropped); Hi, Wi >= 2.  tap (may be
+ * NULL; uint8, contiguous [B,Hi/2,Wi/2,C], 8-byte aligned) receives the winning tap 0..3, row-major inside the window.  On
+ * ties the FIRST tap wins (torch.max_pool2d on the CPU replaces the maximum only by a strictly greater value).  y holds the
+ * bits of the winning input.  Inputs are assumed finite. */
+int psg_maxpool2x2_fwd(const void* x, int64_t ldx, void* y, int64_t ldy, uint8_t* tap, int B, int Hi, int Wi, int C,
+                       int dtype, psg_stream_t stream);
+/* Its backward as a gather: every element of dx [B,Hi,Wi,C] is written exactly once - the dy of its cell if it is the
+ * recorded tap, else 0; the row / column an odd Hi / Wi drops gets 0.  dx needs no zero-fill. */
+int psg_maxpool2x2_bwd(const void* dy, int64_t lddy, const uint8_t* tap, void* dx, int64_t lddx, int B, int Hi, int Wi,
+                       int C, int dtype, psg_stream_t stream);
+/* losses.py:75-81 + :51-53 (+ :137 through a, b) in one pass: img fp32 NCHW [B,3,Hi,Wi] -> y [B,Ho,Wo,8] in `dtype`,
+ *   v = clamp(a * img + b, 0, 1);  v = F.interpolate(v, (Ho,Wo), 'bilinear', align_corners=False) when (Ho,Wo) != (Hi,Wi)
+ *   (no resampling arithmetic at all otherwise);  y[..c] = (v - mean[c]) * inv_std[c]
+ * with the ImageNet mean (0.485, 0.456, 0.406) and inv_std = fp32(1 / std), std = (0.229, 0.224, 0.225).  The resize is PyTorch's:
+ * source index (in / out) * (dst + 0.5) - 0.5 clamped at 0, two taps per axis, combined in fp32 as h0 (w0 v00 + w1 v01) +
+ * h1 (w0 v10 + w1 v11).  Only the formula is PyTorch's: the source index is evaluated in fp64 (torch: fp32 for an fp32 image) and each
+ * weight rounded once, so fp32 results of the resize are closer to the exact one than torch's and not bit-comparable with them.
+ * Any (Ho,Wo), larger or smaller.
+ * Channels 3..7 are zero (the first convolution's weight is padded alike). */
+int psg_image_prep_fwd(const float* img, void* y, int64_t ldy, int B, int Hi, int Wi, int Ho, int Wo, float a, float b,
+                       int dtype, psg_stream_t stream);
+/* Its backward as a gather: dimg (fp32 NCHW [B,3,Hi,Wi], every element written once) = (the forward's resize weights applied to
+ * dy [B,Ho,Wo,8], summed in a fixed order in fp64 and rounded once; the one dy[..c] without a resize) * inv_std[c] * a where 0 <= a * img + b <= 1
+ * (inclusive, as torch.clamp's gradient; the mask is recomputed from img), else 0. */
+int psg_image_prep_bwd(const float* img, const void* dy, int64_t lddy, float* dimg, int B, int Hi, int Wi, int Ho, int Wo,
+                       float a, float b, int dtype, psg_stream_t stream);
+/* F.l1_loss of two feature maps (losses.py:89-90) and its gradient in one pass: a, b [rows, cols] in `dtype`,
+ *   out2 (2 fp32 device scalars) = { mean |a - b|, scale * mean |a - b| }   (fp32 accumulation, n = rows * cols)
+ *   grad (may be NULL; `dtype`) = sign(a - b) * fp32(scale / n) rounded to `dtype`, with sign(0) = 0 (as torch: after ReLU both
+ *   maps are zero in many places).
+ * Deterministic two-stage reduction.  ws: >= psg_feat_l1_workspace_bytes() bytes (PSG_ERR_WORKSPACE otherwise). */
+int psg_feat_l1(const void* a, int64_t lda, const void* b, int64_t ldb, void* grad, int64_t ldg, float* out2, int64_t rows,
+                int cols, float scale, int dtype, void* ws, int64_t ws_bytes, psg_stream_t stream);
+int64_t psg_feat_l1_workspace_bytes(void);
+/* losses.py:147-148: out[0] = -0.5 * sum(1 + logvar - mu^2 - exp(logvar)) / n over n fp32 elements, and (either may be NULL)
+ * dmu = mu / n, dlogvar = 0.5 * (exp(logvar) - 1) / n in fp32.  The sum is taken as 0.5 * sum(mu^2 + (expm1(logvar) - logvar)),
+ * every term >= 0, in fp64 in a fixed two-stage order.  ws: 8-byte aligned, >= psg_kl_workspace_bytes() bytes. */
+int psg_kl_f32(const float* mu, const float* logvar, float* dmu, float* dlogvar, float* out, int64_t n, void* ws,
+               int64_t ws_bytes, psg_stream_t stream);
+int64_t psg_kl_workspace_bytes(void);
+
+/* ---------------------------------------------------------------------------
  * Layout / small ops at the boundary (NCHW fp32 <-> channels-last dtype)
  * ------------------------------------------------------------------------- */
 /* [B,C,HW] fp32 -> [B,HW,C] dtype (UNet.forward input, unet.py:448) and back (:507-509). */

@@ -112,6 +112,15 @@ SIGNATURES = {
     "psg_attn_bwd_longq_workspace_bytes": (c_int64, [c_int] * 5),
     "psg_recon_loss_f32": (c_int, [c_void_p] * 4 + [c_int64, c_float, c_float, c_void_p, c_void_p]),
     "psg_recon_loss_workspace_bytes": (c_int64, []),
+    "psg_maxpool2x2_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p] + [c_int] * 5 + [c_void_p]),
+    "psg_maxpool2x2_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64] + [c_int] * 5 + [c_void_p]),
+    "psg_image_prep_fwd": (c_int, [c_void_p, c_void_p, c_int64] + [c_int] * 5 + [c_float, c_float, c_int, c_void_p]),
+    "psg_image_prep_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p] + [c_int] * 5 + [c_float, c_float, c_int, c_void_p]),
+    "psg_feat_l1": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_int, c_void_p,
+                            c_int64, c_void_p]),
+    "psg_feat_l1_workspace_bytes": (c_int64, []),
+    "psg_kl_f32": (c_int, [c_void_p] * 5 + [c_int64, c_void_p, c_int64, c_void_p]),
+    "psg_kl_workspace_bytes": (c_int64, []),
     "psg_layernorm": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_float,
                               c_int, c_int, c_void_p]),
     "psg_layernorm_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,

@@ -13,10 +13,10 @@ import threading
 import torch
 
 from . import _lib
-from ._lib import ACT_GELU, ACT_NONE, ACT_SILU, ConvDesc, WgradDesc, check, dtype_code, ptr, stream_ptr
+from ._lib import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SILU, ConvDesc, WgradDesc, check, dtype_code, ptr, stream_ptr
 
 __all__ = ["conv2d", "linear", "group_norm", "group_norm_split", "attention_self", "attention_cross", "attention_cross_longq",
-           "cross_in_proj", "upsample_bilinear", "nchw_to_nhwc", "nchw_to_nhwc_grad", "nhwc_to_nchw", "image_out", "recon_loss", "text_pool", "timestep_sinusoid", "WeightCache", "ACT_NONE", "ACT_SILU", "ACT_GELU"]
+           "cross_in_proj", "upsample_bilinear", "nchw_to_nhwc", "nchw_to_nhwc_grad", "nhwc_to_nchw", "image_out", "recon_loss", "max_pool2x2", "image_prep", "feature_l1", "kl_loss", "text_pool", "timestep_sinusoid", "WeightCache", "ACT_NONE", "ACT_SILU", "ACT_GELU", "ACT_RELU"]
 
 
 def _lib_for(t):
@@ -1396,6 +1396,181 @@ def recon_loss(pred, target, w_l1=1.0, w_mse=0.1):
     """final_trainer.py:425-440: (l1 + 0.1 * mse, l1, mse) as fp32 device scalars; one pass produces loss and gradient."""
     out3 = _ReconLossFn.apply(pred, target, w_l1, w_mse)
     return out3[0], out3[1].detach(), out3[2].detach()
+
+
+# ---------------------------------------------------------------------------
+# inference launches of frozen modules (the VAE, the text encoder, the perceptual loss's target side)
+# ---------------------------------------------------------------------------
+def prepared(cache, key, param_list, build):
+    """Prepared (kernel-layout) weights of a frozen module, rebuilt when a parameter changes (version counters)."""
+    stamp = tuple((p.data_ptr(), p._version) for p in param_list)
+    ent = cache.get(key)
+    if ent is None or ent[0] != stamp:
+        ent = (stamp, build())
+        cache[key] = ent
+    return ent[1]
+
+
+def conv_infer(x, wf, bias, Cin, Cout, ks, stride, pad, act=ACT_NONE, residual=None, out_dtype=None):
+    """x [B,H,W,Cin] channels-last (rows 16-byte aligned) -> [B,Ho,Wo,Cout]; wf = prepared weight [Cout][Kpad]."""
+    lib = _lib_for(x)
+    xr, ldx = _rows(x)
+    B, Hi, Wi = x.shape[0], x.shape[1], x.shape[2]
+    Ho, Wo = (Hi + 2 * pad - ks) // stride + 1, (Wi + 2 * pad - ks) // stride + 1
+    y = torch.empty((B, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
+    res_r, ld_res = (None, 0) if residual is None else _rows(residual)
+    _conv_launch(lib, x.dtype, xr, ldx, wf, 0, y, Cout, (B, Hi, Wi, Ho, Wo, ks, stride, pad), Cin, Cout, bias=bias,
+                 residual=res_r, ld_res=ld_res, act=act)
+    return y
+
+
+def prep_weight(w, dtype, pad_in=0, pad_out=0):
+    """fp32 OIHW parameter -> prepared forward weight [O'][Kpad] in `dtype`; optional zero padding of Cin / Cout."""
+    lib = _lib_for(w)
+    O, I, kh, kw = w.shape
+    src = w.detach().float()
+    if pad_in or pad_out:
+        src = torch.nn.functional.pad(src, (0, 0, 0, 0, 0, pad_in, 0, pad_out))
+        O, I = O + pad_out, I + pad_in
+    src = src.contiguous(memory_format=torch.channels_last)           # OHWI memory: the layout every kernel-side path takes
+    code = dtype_code(dtype)
+    kp = lib.psg_kpad(kh * kw * I, code)
+    wf = torch.empty((O, kp), dtype=dtype, device=w.device)
+    check(lib.psg_prep_weight(ptr(src), dtype_code(torch.float32), W_OHWI, ptr(wf), None, O, I, kh, code, stream_ptr()),
+          "psg_prep_weight")
+    return wf
+
+
+
+# ---------------------------------------------------------------------------
+# stage 1's loss around the VGG16 convolutions (src/models/losses.py)
+# ---------------------------------------------------------------------------
+class _MaxPoolFn(torch.autograd.Function):
+    """nn.MaxPool2d(2, 2) on channels-last [B,H,W,C]: psg_maxpool2x2_fwd / _bwd.  Saved for backward: the winning taps
+    (one byte per output element), written only when a gradient is wanted."""
+
+    @staticmethod
+    def forward(ctx, x):
+        lib = _lib_for(x)
+        xr, ldx = _rows(x)
+        B, Hi, Wi, Cc = x.shape
+        y = torch.empty((B, Hi // 2, Wi // 2, Cc), dtype=x.dtype, device=x.device)
+        tap = torch.empty(y.shape, dtype=torch.uint8, device=x.device) if ctx.needs_input_grad[0] else None
+        check(lib.psg_maxpool2x2_fwd(ptr(xr), ldx, ptr(y), Cc, ptr(tap), B, Hi, Wi, Cc, dtype_code(x.dtype), stream_ptr()), "psg_maxpool2x2_fwd")
+        ctx.tap, ctx.meta = tap, (B, Hi, Wi, Cc)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, Hi, Wi, Cc = ctx.meta
+        lib = _lib_for(dy)
+        dyr, lddy = _rows(dy)
+        dx = torch.empty((B, Hi, Wi, Cc), dtype=dy.dtype, device=dy.device)
+        check(lib.psg_maxpool2x2_bwd(ptr(dyr), lddy, ptr(ctx.tap), ptr(dx), Cc, B, Hi, Wi, Cc, dtype_code(dy.dtype), stream_ptr()),
+              "psg_maxpool2x2_bwd")
+        return dx
+
+
+def max_pool2x2(x):
+    """nn.MaxPool2d(kernel_size=2, stride=2) (floor; ties: the first tap) on channels-last [B,H,W,C]."""
+    return _MaxPoolFn.apply(x)
+
+
+class _ImagePrepFn(torch.autograd.Function):
+    """fp32 NCHW image [B,3,H,W] -> normalised channels-last [B,Ho,Wo,8] in `dtype` (psg_image_prep_fwd): clamp(a img + b, 0, 1),
+    bilinear resize to `size` if it differs, ImageNet normalisation; channels 3..7 zero.  Saved for backward: the image (the
+    clamp mask is recomputed from it).  Backward: psg_image_prep_bwd, a gather with the forward's resize weights."""
+
+    @staticmethod
+    def forward(ctx, img, a, b, size, dtype):
+        lib = _lib_for(img)
+        if img.dim() != 4 or img.shape[1] != 3:
+            raise _lib.PsgError(f"image_prep: expected a [B,3,H,W] image, got {tuple(img.shape)}")
+        x = img.detach().contiguous().float()
+        B, _, Hi, Wi = x.shape
+        Ho, Wo = (Hi, Wi) if size is None else (int(size[0]), int(size[1]))
+        y = torch.empty((B, Ho, Wo, 8), dtype=dtype, device=x.device)
+        check(lib.psg_image_prep_fwd(ptr(x), ptr(y), 8, B, Hi, Wi, Ho, Wo, float(a), float(b), dtype_code(dtype), stream_ptr()),
+              "psg_image_prep_fwd")
+        ctx.img = x if ctx.needs_input_grad[0] else None
+        ctx.meta = (B, Hi, Wi, Ho, Wo, float(a), float(b), tuple(img.shape))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, Hi, Wi, Ho, Wo, a, b, shape = ctx.meta
+        lib = _lib_for(dy)
+        dyr, lddy = _rows(dy)
+        dimg = torch.empty((B, 3, Hi, Wi), dtype=torch.float32, device=dy.device)
+        check(lib.psg_image_prep_bwd(ptr(ctx.img), ptr(dyr), lddy, ptr(dimg), B, Hi, Wi, Ho, Wo, a, b, dtype_code(dy.dtype), stream_ptr()),
+              "psg_image_prep_bwd")
+        return dimg.view(shape), None, None, None, None
+
+
+def image_prep(img, a=1.0, b=0.0, size=None, dtype=torch.float32):
+    """losses.py:75-81 and :51-53 in one pass (see _ImagePrepFn); `size` None keeps the image's own size."""
+    return _ImagePrepFn.apply(img, a, b, size, dtype)
+
+
+class _FeatL1Fn(torch.autograd.Function):
+    """(mean |a - b|, weight * mean |a - b|) of two feature maps as fp32 device scalars: psg_feat_l1.  The gradient with respect
+    to `a` (weight * sign(a - b) / n, sign(0) = 0) is produced by the forward's own pass and belongs to the second result;
+    `b` is a constant."""
+
+    @staticmethod
+    def forward(ctx, a, b, weight):
+        lib = _lib_for(a)
+        if a.shape != b.shape or a.dtype != b.dtype:
+            raise _lib.PsgError(f"feature_l1: {tuple(a.shape)} {a.dtype} and {tuple(b.shape)} {b.dtype} differ")
+        ar, lda = _rows(a)
+        br, ldb = _rows(b.detach())
+        cols = ar.shape[-1]
+        rows = ar.numel() // cols
+        grad = torch.empty(a.shape, dtype=a.dtype, device=a.device) if ctx.needs_input_grad[0] else None
+        out2 = torch.empty(2, dtype=torch.float32, device=a.device)
+        ws = _lib.workspace(lib.psg_feat_l1_workspace_bytes(), a.device)
+        check(lib.psg_feat_l1(ptr(ar), lda, ptr(br), ldb, ptr(grad), cols, ptr(out2), rows, cols, float(weight), dtype_code(a.dtype),
+                              ptr(ws), ws.numel(), stream_ptr()), "psg_feat_l1")
+        ctx.grad = grad
+        return out2
+
+    @staticmethod
+    def backward(ctx, g):
+        return (ctx.grad.float() * g[1]).to(ctx.grad.dtype), None, None      # fp32 product, one rounding (0.1 is not a bf16 number)
+
+
+def feature_l1(a, b, weight=1.0):
+    """weight * F.l1_loss(a, b) for feature maps [..., C] in the compute dtype (losses.py:89-90); the gradient reaches `a` only."""
+    return _FeatL1Fn.apply(a, b, weight)[1]
+
+
+class _KLFn(torch.autograd.Function):
+    """losses.py:147-148: -0.5 * sum(1 + logvar - mu^2 - exp(logvar)) / numel as an fp32 device scalar (psg_kl_f32); both
+    gradients come out of the forward's pass."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar):
+        lib = _lib_for(mu)
+        if mu.shape != logvar.shape:
+            raise _lib.PsgError(f"kl_loss: shapes {tuple(mu.shape)} and {tuple(logvar.shape)} differ")
+        m, lv = mu.detach().contiguous().float(), logvar.detach().contiguous().float()
+        dmu = torch.empty_like(m) if ctx.needs_input_grad[0] else None
+        dlv = torch.empty_like(lv) if ctx.needs_input_grad[1] else None
+        out = torch.empty(1, dtype=torch.float32, device=m.device)
+        ws = _lib.workspace(lib.psg_kl_workspace_bytes(), m.device)
+        check(lib.psg_kl_f32(ptr(m), ptr(lv), ptr(dmu), ptr(dlv), ptr(out), m.numel(), ptr(ws), ws.numel(), stream_ptr()), "psg_kl_f32")
+        ctx.grads, ctx.shape = (dmu, dlv), tuple(mu.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        dmu, dlv = ctx.grads
+        return (dmu.view(ctx.shape) * g[0] if dmu is not None else None), (dlv.view(ctx.shape) * g[0] if dlv is not None else None)
+
+
+def kl_loss(mu, logvar):
+    """The KL term of CombinedLoss (mean over all latent elements) as an fp32 device scalar."""
+    return _KLFn.apply(mu, logvar)[0]
 
 
 # ---------------------------------------------------------------------------

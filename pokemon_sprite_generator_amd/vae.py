@@ -23,16 +23,7 @@ import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import ACT_NONE, ACT_RELU, ACT_SILU, ACT_TANH, check, ptr, stream_ptr
-
-
-def _prepared(cache, key, param_list, build):
-    """Prepared (kernel-layout) weights of a frozen module, rebuilt when a parameter changes (version counters)."""
-    stamp = tuple((p.data_ptr(), p._version) for p in param_list)
-    ent = cache.get(key)
-    if ent is None or ent[0] != stamp:
-        ent = (stamp, build())
-        cache[key] = ent
-    return ent[1]
+from .ops import conv_infer as _conv, prep_weight as _prep, prepared as _prepared
 
 
 def _wants_grad(*tensors):
@@ -45,36 +36,6 @@ def _require_frozen(module):
         if p.requires_grad:
             raise _lib.PsgError(f"{type(module).__name__}: parameter {n} has requires_grad=True, but VAE weight gradients (stage 1, "
                                 "and the joint phase of stage 3) are not built; freeze the VAE")
-
-
-def _conv(x, wf, bias, Cin, Cout, ks, stride, pad, act=ACT_NONE, residual=None, out_dtype=None):
-    """x [B,H,W,Cin] channels-last (rows 16-byte aligned) -> [B,Ho,Wo,Cout]; wf = prepared weight [Cout][Kpad]."""
-    lib = ops._lib_for(x)
-    xr, ldx = ops._rows(x)
-    B, Hi, Wi = x.shape[0], x.shape[1], x.shape[2]
-    Ho, Wo = (Hi + 2 * pad - ks) // stride + 1, (Wi + 2 * pad - ks) // stride + 1
-    y = torch.empty((B, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
-    res_r, ld_res = (None, 0) if residual is None else ops._rows(residual)
-    ops._conv_launch(lib, x.dtype, xr, ldx, wf, 0, y, Cout, (B, Hi, Wi, Ho, Wo, ks, stride, pad), Cin, Cout, bias=bias,
-                     residual=res_r, ld_res=ld_res, act=act)
-    return y
-
-
-def _prep(w, dtype, pad_in=0, pad_out=0):
-    """fp32 OIHW parameter -> prepared forward weight [O'][Kpad] in `dtype`; optional zero padding of Cin / Cout."""
-    lib = ops._lib_for(w)
-    O, I, kh, kw = w.shape
-    src = w.detach().float()
-    if pad_in or pad_out:
-        src = torch.nn.functional.pad(src, (0, 0, 0, 0, 0, pad_in, 0, pad_out))
-        O, I = O + pad_out, I + pad_in
-    src = src.contiguous(memory_format=torch.channels_last)           # OHWI memory: the layout every kernel-side path takes
-    code = _lib.dtype_code(dtype)
-    kp = lib.psg_kpad(kh * kw * I, code)
-    wf = torch.empty((O, kp), dtype=dtype, device=w.device)
-    check(lib.psg_prep_weight(ptr(src), _lib.dtype_code(torch.float32), ops.W_OHWI, ptr(wf), None, O, I, kh, code, stream_ptr()),
-          "psg_prep_weight")
-    return wf
 
 
 class ResNetBlock(nn.Module):
