@@ -397,17 +397,82 @@ def _param_ret(out, e):
     return out
 
 
-def _param_grad(param, compute):
-    """Run `compute(out, accumulate)` for a parameter gradient: into the registered sink (returns None for
-    autograd) or into a fresh tensor (returned)."""
-    e = GradSink.get(param)
-    if e is not None:
-        compute(e.view, e.written)
-        GradSink.done(e)
-        return None
-    out = torch.empty_like(param)
-    compute(out, False)
-    return out
+def _linear_geom(M):
+    """The conv geometry (B, Hi, Wi, Ho, Wo, ks, stride, pad) of a Linear over M rows."""
+    return (M, 1, 1, 1, 1, 1, 1, 0)
+
+
+def _conv_geom(x, ks, stride, pad):
+    """The conv geometry of x [B,Hi,Wi,Cin] under a ks x ks kernel: Ho / Wo are nn.Conv2d's (floor)."""
+    B, Hi, Wi = x.shape[0], x.shape[1], x.shape[2]
+    return (B, Hi, Wi, (Hi + 2 * pad - ks) // stride + 1, (Wi + 2 * pad - ks) // stride + 1, ks, stride, pad)
+
+
+def _deliver_gemm_grads(lib, dtype, parts, weight, bias, want_w, want_b, scale=1.0, side_stream=False, keep=()):
+    """The weight gradient and the (fused) bias gradient of a GEMM node, delivered: returns what autograd gets for
+    (weight, bias) - None for a gradient that went to the parameter's GradSink view, else the tensor.
+
+    `parts`: one (x, ldx, g, ldg, geom, Cin, Cout) per launch; several parts write consecutive row ranges of ONE packed
+    parameter (the in-projection), which is marked done once, after the last launch.  `want_b` without `want_w` (frozen
+    weight) takes the column sums of g instead (`scale` applied afterwards: rare).
+
+    `side_stream`: the launches may hop to SideStream when it is enabled and the weight has a sink; `keep` are tensors to
+    hold besides each part's g and x until the stream is joined (see SideStream._pending: _ConvFn returns dy itself as
+    d_res).  Only _ConvFn and _FFNFn pass it.  What is known of why: when the second stream was added, _ConvFn got the hop
+    and _CrossInProjFn, which already existed, did not; _FFNFn, added afterwards, copied conv's; _QKVFn, added last, did
+    not.  No measurement of the hop exists for the two packed-projection nodes.  The stream is off by default and measured
+    slower, so the split is kept as it is, not extended."""
+    if not (want_w or want_b):
+        return None, None
+    bo, bacc, be = _param_out(bias) if want_b else (None, False, None)
+    whole = len(parts) == 1
+    dw = None
+    if want_w:
+        wo, wacc, we = _param_out(weight)
+        side = SideStream.get(wo.device) if (side_stream and SideStream.enabled and we is not None) else None
+        row = 0
+        for x, ldx, g, ldg, geom, Cin, Cout in parts:
+            dwp, dbp = (wo, bo) if whole else (wo[row:row + Cout], None if bo is None else bo[row:row + Cout])
+            if side is not None:
+                side.wait_stream(torch.cuda.current_stream(wo.device))
+                with torch.cuda.stream(side):
+                    _wgrad_launch(lib, dtype, x, ldx, g, ldg, dwp, geom, Cin, Cout, accumulate=wacc, dbias=dbp, accumulate_bias=bacc, scale=scale)
+                g.record_stream(side); x.record_stream(side)
+                SideStream.hold(g, x, *keep)
+            else:
+                _wgrad_launch(lib, dtype, x, ldx, g, ldg, dwp, geom, Cin, Cout, accumulate=wacc, dbias=dbp, accumulate_bias=bacc, scale=scale)
+            row += Cout
+        dw = _param_ret(wo, we)
+    else:
+        row = 0
+        for x, ldx, g, ldg, geom, Cin, Cout in parts:
+            out = bo if whole else bo[row:row + Cout]
+            M = geom[0] * geom[3] * geom[4]
+            if scale == 1.0:
+                _colsum(lib, g, ldg, M, 1, Cout, dtype, torch.float32, out=out, accumulate=bacc)
+            else:                      # (rare: frozen weight, trainable bias, gated output)
+                t = _colsum(lib, g, ldg, M, 1, Cout, dtype, torch.float32).mul_(scale)
+                out.add_(t) if bacc else out.copy_(t)
+            row += Cout
+    return dw, (_param_ret(bo, be) if want_b else None)
+
+
+class _AffineGrads:
+    """The (gamma, beta) gradients of a normalisation backward, delivered.  The constructor hands out where the kernel writes:
+    `dgamma`, `dbeta` (None for an unwanted one) and the ONE `accumulate` flag the kernels take; after the launch `finish()`
+    returns what autograd gets for (gamma, beta), as `_deliver_gemm_grads`, and reports the sink entries ready.  When the two
+    entries disagree on `written`, `dbeta` is a zeroed temporary that `finish()` joins into beta's view."""
+
+    def __init__(self, gamma, beta, want_g, want_b):
+        self.go, gacc, self.ge = _param_out(gamma) if want_g else (None, False, None)
+        self.bo, self.bacc, self.be = _param_out(beta) if want_b else (None, False, None)
+        self.dgamma, self.accumulate = self.go, (gacc if want_g else self.bacc)
+        self.dbeta = torch.zeros_like(self.bo) if (want_g and want_b and gacc != self.bacc) else self.bo
+
+    def finish(self):
+        if self.dbeta is not self.bo:
+            self.bo.add_(self.dbeta) if self.bacc else self.bo.copy_(self.dbeta)
+        return (_param_ret(self.go, self.ge) if self.go is not None else None), (_param_ret(self.bo, self.be) if self.bo is not None else None)
 
 
 # ---------------------------------------------------------------------------
@@ -581,16 +646,13 @@ class _ConvFn(torch.autograd.Function):
         is_conv = weight.dim() == 4
         Cout, Cin = weight.shape[0], weight.shape[1]
         ks = weight.shape[2] if is_conv else 1
-        pad = 1 if ks == 3 else 0
         xr, ldx = _rows(x)
         if is_conv:
-            B, Hi, Wi = x.shape[0], x.shape[1], x.shape[2]
-            Ho, Wo = (Hi + 2 * pad - ks) // stride + 1, (Wi + 2 * pad - ks) // stride + 1
-            out_shape = (B, Ho, Wo, Cout)
+            geom = _conv_geom(x, ks, stride, 1 if ks == 3 else 0)
+            out_shape = (geom[0], geom[3], geom[4], Cout)
         else:
-            B, Hi, Wi, Ho, Wo = xr.numel() // xr.shape[-1], 1, 1, 1, 1
+            geom = _linear_geom(xr.numel() // xr.shape[-1])
             out_shape = tuple(x.shape[:-1]) + (Cout,)
-        geom = (B, Hi, Wi, Ho, Wo, ks, stride, pad)
         need_dx = ctx.needs_input_grad[0]
         wf, wd = WeightCache.get(weight, dtype, need_dx)
         y, ldy = _out_rows(out, out_shape, dtype, x.device)
@@ -640,31 +702,9 @@ class _ConvFn(torch.autograd.Function):
             dx = torch.empty(x_shape, dtype=dtype, device=dy.device)
             tgeom = (B, Ho, Wo, Hi, Wi, ks, stride, pad)     # gather source = dY grid, result = input grid
             _conv_launch(lib, dtype, g, ldg, wd, 0, dx, Cin, tgeom, Cout, Cin, transposed=True, alpha=gate)
-        want_b = has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1]:
-            # one launch: weight gradient + (fused) bias gradient, straight into the gradient arena when registered
-            wo, wacc, we = _param_out(ctx.weight_param)
-            bo, bacc, be = _param_out(ctx.bias_param) if want_b else (None, False, None)
-            if SideStream.enabled and we is not None:
-                side, cur = SideStream.get(dy.device), torch.cuda.current_stream(dy.device)
-                side.wait_stream(cur)
-                with torch.cuda.stream(side):
-                    _wgrad_launch(lib, dtype, xr, ldx, g, ldg, wo, geom, Cin, Cout, accumulate=wacc, dbias=bo, accumulate_bias=bacc, scale=gate)
-                g.record_stream(side); xr.record_stream(side)
-                SideStream.hold(g, xr, dy)
-            else:
-                _wgrad_launch(lib, dtype, xr, ldx, g, ldg, wo, geom, Cin, Cout, accumulate=wacc, dbias=bo, accumulate_bias=bacc, scale=gate)
-            dw = _param_ret(wo, we)
-            if want_b:
-                db = _param_ret(bo, be)
-        elif want_b:
-            def bias_only(out, acc):
-                if gate == 1.0:
-                    _colsum(lib, g, ldg, M, 1, Cout, dtype, torch.float32, out=out, accumulate=acc)
-                else:                      # (rare: frozen weight, trainable bias, gated output)
-                    t = _colsum(lib, g, ldg, M, 1, Cout, dtype, torch.float32).mul_(gate)
-                    out.add_(t) if acc else out.copy_(t)
-            db = _param_grad(ctx.bias_param, bias_only)
+        # one launch: weight gradient + (fused) bias gradient, straight into the gradient arena when registered
+        dw, db = _deliver_gemm_grads(lib, dtype, [(xr, ldx, g, ldg, geom, Cin, Cout)], ctx.weight_param, ctx.bias_param,
+                                   ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2], scale=gate, side_stream=True, keep=(dy,))
         if has_ra and ctx.needs_input_grad[3]:
             dra = _colsum(lib, g, ldg, Ho * Wo, B, Cout, dtype, dtype, keep2d=True)
         return dx, dw, db, dra, d_res, None, None, None, None, None, None
@@ -695,7 +735,7 @@ class _QKVFn(torch.autograd.Function):
         Cin, H = wq.shape[1], wq.shape[0]
         M = xr.numel() // xr.shape[-1]
         y = torch.empty(tuple(x.shape[:-1]) + (3 * H,), dtype=x.dtype, device=x.device)
-        geom = (M, 1, 1, 1, 1, 1, 1, 0)
+        geom = _linear_geom(M)
         _conv_launch(lib, x.dtype, xr, ldx, wf, 0, y, 3 * H, geom, Cin, 3 * H, bias=bcat)
         ctx.save_for_backward(xr, wd)
         ctx.params = (wq, bq, wk, bk, wv, bv)
@@ -716,20 +756,9 @@ class _QKVFn(torch.autograd.Function):
             _conv_launch(lib, dtype, g, ldg, wd, 0, dx, Cin, geom, 3 * H, Cin, transposed=True)
         grads = []
         for i in range(3):
-            w, b = ctx.params[2 * i], ctx.params[2 * i + 1]
-            need_w, need_b = ctx.needs_input_grad[1 + 2 * i], ctx.needs_input_grad[2 + 2 * i]
             gi = g2[..., i * H:(i + 1) * H]                  # a column slice of dqkv: same row stride, start moved
-            dw = db = None
-            if need_w:
-                wo, wacc, we = _param_out(w)
-                bo, bacc, be = _param_out(b) if need_b else (None, False, None)
-                _wgrad_launch(lib, dtype, xr, ldx, gi, ldg, wo, geom, Cin, H, accumulate=wacc, dbias=bo, accumulate_bias=bacc)
-                dw = _param_ret(wo, we)
-                if need_b:
-                    db = _param_ret(bo, be)
-            elif need_b:
-                db = _param_grad(b, lambda out, acc, gi=gi: _colsum(lib, gi, ldg, geom[0], 1, H, dtype, torch.float32, out=out, accumulate=acc))
-            grads += [dw, db]
+            grads += _deliver_gemm_grads(lib, dtype, [(xr, ldx, gi, ldg, geom, Cin, H)], ctx.params[2 * i], ctx.params[2 * i + 1],
+                                       ctx.needs_input_grad[1 + 2 * i], ctx.needs_input_grad[2 + 2 * i])
         return (dx, *grads, None)
 
 
@@ -776,7 +805,7 @@ class _FFNFn(torch.autograd.Function):
         u = torch.empty((M, Hd), dtype=dtype, device=x.device) if need else None
         hmid = torch.empty((M, Hd), dtype=dtype, device=x.device)
         y, ldy = _out_rows(out, tuple(x.shape), dtype, x.device)
-        g1 = (M, 1, 1, 1, 1, 1, 1, 0)
+        g1 = _linear_geom(M)
         # `u` receives gelu'(W1 x + b1) * mask1 / (1 - p), not the pre-activation: backward multiplies by it
         _conv_launch(lib, dtype, xr, ldx, wf1, 0, hmid, Hd, g1, C, Hd, bias=b1, preact=u, act=ACT_GELU, drop_p=drop_p, seed=seed1,
                      flags=_lib.CONV_SAVE_DACT if (u is not None and _FFN_SAVE_DACT) else 0)
@@ -794,7 +823,7 @@ class _FFNFn(torch.autograd.Function):
         lib = _lib_for(dy)
         dtype = dy.dtype
         dyr, lddy = _rows(dy)
-        geo = (M, 1, 1, 1, 1, 1, 1, 0)
+        geo = _linear_geom(M)
         if wd1 is None:
             _, wd1 = WeightCache.get(w1, dtype, True)
         if wd2 is None:
@@ -810,29 +839,15 @@ class _FFNFn(torch.autograd.Function):
         else:
             _conv_launch(lib, dtype, g2, C, wd2, 0, gu, Hd, geo, C, Hd, transposed=True, dact_u=u, ld_dact=Hd, act=ACT_GELU, drop_p=drop_p, seed=seed1)
 
-        def wgrad(xin, ldxin, g, ldg, wp, bp, cin, cout):
-            wo, wacc, we = _param_out(wp)
-            bo, bacc, be = _param_out(bp)
-            if SideStream.enabled and we is not None:
-                side, cur = SideStream.get(dy.device), torch.cuda.current_stream(dy.device)
-                side.wait_stream(cur)
-                with torch.cuda.stream(side):
-                    _wgrad_launch(lib, dtype, xin, ldxin, g, ldg, wo, geo, cin, cout, accumulate=wacc, dbias=bo, accumulate_bias=bacc)
-                g.record_stream(side); xin.record_stream(side)
-                SideStream.hold(g, xin)
-            else:
-                _wgrad_launch(lib, dtype, xin, ldxin, g, ldg, wo, geo, cin, cout, accumulate=wacc, dbias=bo, accumulate_bias=bacc)
-            return _param_ret(wo, we), _param_ret(bo, be)
-
-        dw2 = db2 = dw1 = db1 = dx = None
-        if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
-            dw2, db2 = wgrad(hmid, Hd, g2, C, w2p, b2p, Hd, C)
+        # (a Linear whose weight OR bias trains gets both gradients from the one fused launch)
+        dx = None
+        need2, need1 = ctx.needs_input_grad[3] or ctx.needs_input_grad[4], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        dw2, db2 = _deliver_gemm_grads(lib, dtype, [(hmid, Hd, g2, C, geo, Hd, C)], w2p, b2p, need2, need2, side_stream=True)
         if ctx.needs_input_grad[0]:
             dx = torch.empty(x_shape, dtype=dtype, device=dy.device)
             # dx = W1^T gu + dy (the residual branch's gradient rides in the epilogue)
             _conv_launch(lib, dtype, gu, Hd, wd1, 0, dx, C, geo, Hd, C, transposed=True, residual=dyr, ld_res=lddy)
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dw1, db1 = wgrad(xr, ldx, gu, Hd, w1p, b1p, C, Hd)
+        dw1, db1 = _deliver_gemm_grads(lib, dtype, [(xr, ldx, gu, Hd, geo, C, Hd)], w1p, b1p, need1, need1, side_stream=True)
         return dx, dw1, db1, dw2, db2, None, None, None, None, None
 
 
@@ -853,22 +868,22 @@ class _CrossInProjFn(torch.autograd.Function):
         wf, wd = WeightCache.get(weight, dtype, ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         xr, ldx = _rows(xn)
         tr, ldt = _rows(tp)
-        Mq, Mk = xn.numel() // E, tp.numel() // E
+        gq, gk = _linear_geom(xn.numel() // E), _linear_geom(tp.numel() // E)
         q = torch.empty(tuple(xn.shape[:-1]) + (E,), dtype=dtype, device=xn.device)
         kv = torch.empty(tuple(tp.shape[:-1]) + (2 * E,), dtype=dtype, device=xn.device)
         kp = wf.shape[1]
         esz = wf.element_size()
-        _conv_launch(lib, dtype, xr, ldx, wf.data_ptr(), 0, q, E, (Mq, 1, 1, 1, 1, 1, 1, 0), E, E, bias=bias[:E])
-        _conv_launch(lib, dtype, tr, ldt, wf.data_ptr() + E * kp * esz, 0, kv, 2 * E, (Mk, 1, 1, 1, 1, 1, 1, 0), E, 2 * E, bias=bias[E:])
+        _conv_launch(lib, dtype, xr, ldx, wf.data_ptr(), 0, q, E, gq, E, E, bias=bias[:E])
+        _conv_launch(lib, dtype, tr, ldt, wf.data_ptr() + E * kp * esz, 0, kv, 2 * E, gk, E, 2 * E, bias=bias[E:])
         ctx.save_for_backward(xr, tr, weight)
         ctx.bias_param, ctx.weight_param = bias, weight
-        ctx.meta = (E, ldx, ldt, Mq, Mk, tuple(xn.shape), tuple(tp.shape), wd, wf)
+        ctx.meta = (E, ldx, ldt, gq, gk, tuple(xn.shape), tuple(tp.shape), wd, wf)
         return q, kv
 
     @staticmethod
     def backward(ctx, dq, dkv):
         xr, tr, weight = ctx.saved_tensors
-        E, ldx, ldt, Mq, Mk, xs, ts, wd, wf = ctx.meta
+        E, ldx, ldt, gq, gk, xs, ts, wd, wf = ctx.meta
         lib = _lib_for(dq)
         dtype = dq.dtype
         dqr, lddq = _rows(dq)
@@ -877,28 +892,16 @@ class _CrossInProjFn(torch.autograd.Function):
             _, wd = WeightCache.get(weight, dtype, True)
         kpd = wd.shape[1]
         esz = wd.element_size()
-        dxn = dtp = dw = db = None
+        dxn = dtp = None
         if ctx.needs_input_grad[0]:
             dxn = torch.empty(xs, dtype=dtype, device=dq.device)
-            _conv_launch(lib, dtype, dqr, lddq, wd.data_ptr(), kpd, dxn, E, (Mq, 1, 1, 1, 1, 1, 1, 0), E, E, transposed=True)
+            _conv_launch(lib, dtype, dqr, lddq, wd.data_ptr(), kpd, dxn, E, gq, E, E, transposed=True)
         if ctx.needs_input_grad[1]:
             dtp = torch.empty(ts, dtype=dtype, device=dq.device)
-            _conv_launch(lib, dtype, dkr, lddk, wd.data_ptr() + E * esz, kpd, dtp, E, (Mk, 1, 1, 1, 1, 1, 1, 0), 2 * E, E, transposed=True)
-        if ctx.needs_input_grad[2]:
-            wo, wacc, we = _param_out(ctx.weight_param)
-            bo, bacc, be = _param_out(ctx.bias_param) if ctx.needs_input_grad[3] else (None, False, None)
-            _wgrad_launch(lib, dtype, xr, ldx, dqr, lddq, wo[:E], (Mq, 1, 1, 1, 1, 1, 1, 0), E, E, accumulate=wacc,
-                          dbias=None if bo is None else bo[:E], accumulate_bias=bacc)
-            _wgrad_launch(lib, dtype, tr, ldt, dkr, lddk, wo[E:], (Mk, 1, 1, 1, 1, 1, 1, 0), E, 2 * E, accumulate=wacc,
-                          dbias=None if bo is None else bo[E:], accumulate_bias=bacc)
-            dw = _param_ret(wo, we)
-            if bo is not None:
-                db = _param_ret(bo, be)
-        elif ctx.needs_input_grad[3]:
-            def bg(out, acc):
-                _colsum(lib, dqr, lddq, Mq, 1, E, dtype, torch.float32, out=out[:E], accumulate=acc)
-                _colsum(lib, dkr, lddk, Mk, 1, 2 * E, dtype, torch.float32, out=out[E:], accumulate=acc)
-            db = _param_grad(ctx.bias_param, bg)
+            _conv_launch(lib, dtype, dkr, lddk, wd.data_ptr() + E * esz, kpd, dtp, E, gk, 2 * E, E, transposed=True)
+        # rows [:E] of the packed parameter from the queries, rows [E:] from the text tokens
+        dw, db = _deliver_gemm_grads(lib, dtype, [(xr, ldx, dqr, lddq, gq, E, E), (tr, ldt, dkr, lddk, gk, E, 2 * E)],
+                                   ctx.weight_param, ctx.bias_param, ctx.needs_input_grad[2], ctx.needs_input_grad[3])
         return dxn, dtp, dw, db
 
 
@@ -1050,22 +1053,14 @@ class _GroupNormFn(torch.autograd.Function):
         if dpass is not None:
             dres, lddres = _rows(dpass if dpass.dtype == dtype else dpass.to(dtype))
         dx = torch.empty(shape, dtype=dtype, device=dy.device)
-        eg, eb = GradSink.get(ctx.gamma_param), GradSink.get(ctx.beta_param)
-        sink = eg is not None and eb is not None and eg.written == eb.written
-        if sink:
-            dg, db, acc = eg.view, eb.view, eg.written
-        else:
-            dg = torch.empty(Cc, dtype=torch.float32, device=dy.device)
-            db = torch.empty(Cc, dtype=torch.float32, device=dy.device)
-            acc = False
+        # The kernel always produces both parameter gradients, so this node does not gate on needs_input_grad as LayerNorm and
+        # BertEmbed do: a frozen gamma / beta that has a sink entry is written and reported ready too (as it always was).
+        ag = _AffineGrads(ctx.gamma_param, ctx.beta_param, True, True)
         ws = _lib.workspace(lib.psg_groupnorm_bwd_workspace_bytes(B, Cc), dy.device)
         check(lib.psg_groupnorm_bwd_res(ptr(dyr), lddy, ptr(xr), ldx, ptr(gamma), ptr(beta), ptr(stats[0]), ptr(stats[1]), ptr(dres), lddres,
-                                        ptr(dx), Cc, ptr(dg), ptr(db), B, HW, Cc, groups, int(silu), int(acc), dtype_code(dtype), ptr(ws),
-                                        stream_ptr()), "psg_groupnorm_bwd_res")
-        if sink:
-            GradSink.done(eg)
-            GradSink.done(eb)
-            return dx, None, None, None, None, None, None
+                                        ptr(dx), Cc, ptr(ag.dgamma), ptr(ag.dbeta), B, HW, Cc, groups, int(silu), int(ag.accumulate),
+                                        dtype_code(dtype), ptr(ws), stream_ptr()), "psg_groupnorm_bwd_res")
+        dg, db = ag.finish()
         return dx, dg, db, None, None, None, None
 
 
@@ -1085,24 +1080,30 @@ def group_norm_split(x, gamma, beta, groups, eps=1e-5, silu=False):
 # ---------------------------------------------------------------------------
 # LayerNorm
 # ---------------------------------------------------------------------------
+def layer_norm_fwd(x, gamma, beta, eps, residual=None, out_dtype=None):
+    """The psg_layernorm launch of `layer_norm` and of the frozen text encoder: (y, xr, ldx, rr, ldr) - the result in
+    `out_dtype` (x's by default) and the row-addressed operands, which are all a backward needs."""
+    lib = _lib_for(x)
+    N = x.shape[-1]
+    xr, ldx = _rows(x)
+    rr, ldr = _rows(residual) if residual is not None else (None, 0)
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    check(lib.psg_layernorm(ptr(xr), ldx, ptr(rr), ldr, ptr(y), N, ptr(gamma), ptr(beta), x.numel() // N, N, float(eps), dtype_code(x.dtype),
+                            dtype_code(out_dtype), stream_ptr()), "psg_layernorm")
+    return y, xr, ldx, rr, ldr
+
+
 class _LayerNormFn(torch.autograd.Function):
     """y = LayerNorm(x [+ residual]) * gamma + beta over the last dimension: psg_layernorm / psg_layernorm_bwd.  Only the
     inputs are saved (the backward recomputes the statistics); the one dz serves x and the residual."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, residual, out_dtype):
-        lib = _lib_for(x)
-        N = x.shape[-1]
-        rows = x.numel() // N
-        xr, ldx = _rows(x)
-        rr, ldr = _rows(residual) if residual is not None else (None, 0)
-        out_dtype = x.dtype if out_dtype is None else out_dtype
-        y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-        check(lib.psg_layernorm(ptr(xr), ldx, ptr(rr), ldr, ptr(y), N, ptr(gamma), ptr(beta), rows, N, float(eps), dtype_code(x.dtype),
-                                dtype_code(out_dtype), stream_ptr()), "psg_layernorm")
+        y, xr, ldx, rr, ldr = layer_norm_fwd(x, gamma, beta, eps, residual, out_dtype)
         ctx.save_for_backward(xr, rr, gamma)
         ctx.gamma_param, ctx.beta_param = gamma, beta
-        ctx.meta = (rows, N, float(eps), ldx, ldr, tuple(x.shape))
+        ctx.meta = (x.numel() // x.shape[-1], x.shape[-1], float(eps), ldx, ldr, tuple(x.shape))
         return y
 
     @staticmethod
@@ -1113,21 +1114,13 @@ class _LayerNormFn(torch.autograd.Function):
         dyr, lddy = _rows(dy)
         dz = torch.empty(shape, dtype=xr.dtype, device=dy.device)
         want_g, want_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        go, gacc, ge = _param_out(ctx.gamma_param) if want_g else (None, False, None)
-        bo, bacc, be = _param_out(ctx.beta_param) if want_b else (None, False, None)
-        if want_g and want_b and gacc != bacc:         # one accumulate flag per launch: beta goes through a zeroed tensor, joined after
-            bo2 = torch.zeros_like(bo)
-        else:
-            bo2 = bo
+        ag = _AffineGrads(ctx.gamma_param, ctx.beta_param, want_g, want_b)
         need = lib.psg_layernorm_bwd_workspace_bytes(rows, N) if (want_g or want_b) else 0
         ws = _lib.workspace(need, dy.device) if need else None
-        check(lib.psg_layernorm_bwd(ptr(xr), ldx, ptr(rr), ldr, ptr(dyr), lddy, ptr(gamma), ptr(dz), N, ptr(go), ptr(bo2),
-                                    int(gacc if want_g else bacc), rows, N, eps, dtype_code(xr.dtype), dtype_code(dy.dtype), ptr(ws),
+        check(lib.psg_layernorm_bwd(ptr(xr), ldx, ptr(rr), ldr, ptr(dyr), lddy, ptr(gamma), ptr(dz), N, ptr(ag.dgamma), ptr(ag.dbeta),
+                                    int(ag.accumulate), rows, N, eps, dtype_code(xr.dtype), dtype_code(dy.dtype), ptr(ws),
                                     ws.numel() if ws is not None else 0, stream_ptr()), "psg_layernorm_bwd")
-        if bo2 is not bo:
-            bo.add_(bo2) if bacc else bo.copy_(bo2)
-        dg = _param_ret(go, ge) if want_g else None
-        db = _param_ret(bo, be) if want_b else None
+        dg, db = ag.finish()
         need_x = ctx.needs_input_grad[0]
         need_r = rr is not None and ctx.needs_input_grad[4]
         return (dz if need_x else None), dg, db, None, (dz if need_r else None), None
@@ -1135,7 +1128,7 @@ class _LayerNormFn(torch.autograd.Function):
 
 def layer_norm(x, weight, bias, eps, residual=None, out_dtype=None):
     """nn.LayerNorm over the last dimension of x [..., N] (+ a residual added first: BERT's post-LN), fp32 parameters;
-    `out_dtype`: the result's dtype (x's by default).  The forward values are text_encoder.layer_norm's."""
+    `out_dtype`: the result's dtype (x's by default).  The forward launch is `layer_norm_fwd`, the frozen text encoder's."""
     return _LayerNormFn.apply(x, weight, bias, eps, residual, out_dtype)
 
 
@@ -1154,25 +1147,32 @@ def _position_runs(B, S, device):
     return _pos_index[k]
 
 
+def bert_embed_fwd(ids, type_ids, word, pos, typ, gamma, beta, eps, dtype, drop_p=0.0, seed=0):
+    """The launches of `bert_embed` and of the frozen text encoder: psg_bert_embed_ln over token ids [B, S] -> [B*S, N] rows
+    in `dtype`, then (drop_p > 0) psg_dropout_apply in place with the mask drawn from `seed`."""
+    lib = _lib_for(word)
+    B, S = ids.shape
+    V, N = word.shape
+    y = torch.empty((B * S, N), dtype=dtype, device=word.device)
+    check(lib.psg_bert_embed_ln(ptr(ids), ptr(type_ids), ptr(word), ptr(pos), ptr(typ), ptr(gamma), ptr(beta), ptr(y), N, B, S, N, V,
+                                pos.shape[0], typ.shape[0], float(eps), dtype_code(dtype), stream_ptr()), "psg_bert_embed_ln")
+    if drop_p > 0:
+        check(lib.psg_dropout_apply(ptr(y), N, ptr(y), N, B * S, N, drop_p, seed, 1.0 / (1.0 - drop_p), dtype_code(dtype), stream_ptr()),
+              "psg_dropout_apply")
+    return y
+
+
 class _BertEmbedFn(torch.autograd.Function):
-    """y = dropout(LayerNorm(word[ids] + type[type_ids] + pos[s])): psg_bert_embed_ln (+ psg_dropout_apply in place), and its
-    backward psg_bert_embed_ln_bwd + one psg_embed_scatter per table whose gradient is wanted.  Only the ids are kept; the keys
-    are sorted on the device (integer plumbing), nothing synchronises with the host."""
+    """y = dropout(LayerNorm(word[ids] + type[type_ids] + pos[s])): `bert_embed_fwd`, and its backward psg_bert_embed_ln_bwd +
+    one psg_embed_scatter per table whose gradient is wanted.  Only the ids are kept; the keys are sorted on the device
+    (integer plumbing), nothing synchronises with the host."""
 
     @staticmethod
     def forward(ctx, ids, type_ids, word, pos, typ, gamma, beta, eps, pad_id, dtype, drop_p, seed):
-        lib = _lib_for(word)
-        B, S = ids.shape
-        V, N = word.shape
-        y = torch.empty((B * S, N), dtype=dtype, device=word.device)
-        check(lib.psg_bert_embed_ln(ptr(ids), ptr(type_ids), ptr(word), ptr(pos), ptr(typ), ptr(gamma), ptr(beta), ptr(y), N, B, S, N, V,
-                                    pos.shape[0], typ.shape[0], float(eps), dtype_code(dtype), stream_ptr()), "psg_bert_embed_ln")
-        if drop_p > 0:
-            check(lib.psg_dropout_apply(ptr(y), N, ptr(y), N, B * S, N, drop_p, seed, 1.0 / (1.0 - drop_p), dtype_code(dtype), stream_ptr()),
-                  "psg_dropout_apply")
+        y = bert_embed_fwd(ids, type_ids, word, pos, typ, gamma, beta, eps, dtype, drop_p, seed)
         ctx.save_for_backward(ids, type_ids, word, pos, typ, gamma)
         ctx.params = (word, pos, typ, gamma, beta)
-        ctx.meta = (B, S, float(eps), int(pad_id), float(drop_p), seed)
+        ctx.meta = (*ids.shape, float(eps), int(pad_id), float(drop_p), seed)
         return y
 
     @staticmethod
@@ -1195,15 +1195,11 @@ class _BertEmbedFn(torch.autograd.Function):
                    lib.psg_embed_scatter_workspace_bytes(rows, N) if (want_w or want_p or want_t) else 0)
         ws = _lib.workspace(need, dev) if need else None
         nws = ws.numel() if ws is not None else 0
-        go, gacc, ge = _param_out(p_gamma) if want_g else (None, False, None)
-        bo, bacc, be = _param_out(p_beta) if want_b else (None, False, None)
-        bo2 = torch.zeros_like(bo) if (want_g and want_b and gacc != bacc) else bo      # one accumulate flag per launch
+        ag = _AffineGrads(p_gamma, p_beta, want_g, want_b)
         dz = torch.empty((rows, N), dtype=torch.float32, device=dev)
-        check(lib.psg_bert_embed_ln_bwd(ptr(ids), ptr(type_ids), ptr(word), ptr(pos), ptr(typ), ptr(gamma), ptr(dyr), lddy, ptr(dz), ptr(go),
-                                        ptr(bo2), int(gacc if want_g else bacc), B, S, N, V, pos.shape[0], typ.shape[0], eps,
+        check(lib.psg_bert_embed_ln_bwd(ptr(ids), ptr(type_ids), ptr(word), ptr(pos), ptr(typ), ptr(gamma), ptr(dyr), lddy, ptr(dz),
+                                        ptr(ag.dgamma), ptr(ag.dbeta), int(ag.accumulate), B, S, N, V, pos.shape[0], typ.shape[0], eps,
                                         dtype_code(dy.dtype), ptr(ws), nws, stream_ptr()), "psg_bert_embed_ln_bwd")
-        if bo2 is not bo:
-            bo.add_(bo2) if bacc else bo.copy_(bo2)
 
         def scatter(param, key, perm, skip):
             out, acc, e = _param_out(param)
@@ -1224,8 +1220,7 @@ class _BertEmbedFn(torch.autograd.Function):
                 dt = scatter(p_typ, torch.zeros_like(order), order, -1)
             else:
                 dt = scatter(p_typ, *torch.sort(type_ids.view(-1), stable=True), -1)
-        dg = _param_ret(go, ge) if want_g else None
-        db = _param_ret(bo, be) if want_b else None
+        dg, db = ag.finish()                         # (after the scatters: the tables are reported ready before gamma and beta)
         return None, None, dw, dp, dt, dg, db, None, None, None, None, None
 
 
@@ -1239,72 +1234,76 @@ def bert_embed(ids, type_ids, word, pos, typ, gamma, beta, eps, pad_id=0, dtype=
 # ---------------------------------------------------------------------------
 # attention core
 # ---------------------------------------------------------------------------
+def _attn_operands(q_src, kv_src, heads, rowed=False):
+    """The operands of the attention entries for packed projections - self (kv_src None): q_src [B,L,3E] holds the q | k | v
+    columns; cross: q_src [B,L,E] and kv_src [B,S,2E] with the k | v columns.  Returns (qr, kvr, io, dims, E): the
+    row-addressed tensors behind the pointers, io = (q, ldq, k, ldk, v, ldk) and dims = (B, heads, L, S, d), both in the
+    entries' argument order.  `rowed`: the tensors are results of `_rows` already (a backward's saved inputs) or freshly
+    allocated (its gradient outputs, packed the same way) and are taken as they are - no second check, and no copy, which
+    for an output would swallow the result."""
+    qr, ldq = (q_src, q_src.stride(-2)) if rowed else _rows(q_src)
+    B, L = q_src.shape[0], q_src.shape[1]
+    esz = qr.element_size()
+    if kv_src is None:
+        E, S, kvr, ldk = q_src.shape[-1] // 3, L, None, ldq
+        kp = qr.data_ptr() + E * esz
+    else:
+        E, S = q_src.shape[-1], kv_src.shape[1]
+        kvr, ldk = (kv_src, kv_src.stride(-2)) if rowed else _rows(kv_src)
+        kp = kvr.data_ptr()
+    return qr, kvr, (qr.data_ptr(), ldq, kp, ldk, kp + E * esz, ldk), (B, heads, L, S, E // heads), E
+
+
+def attention_fwd(q_src, kv_src, heads, drop_p=0.0, seed=0, kv_len=None, want_lse=True):
+    """The forward launch of every attention path: (o [B,L,E], lse, qr, kvr) - the result, the log-sum-exp and the row-addressed
+    inputs, which are what a backward saves.  psg_attn_fwd; with `kv_len` (int32 [B] on the device: the keys of sample b end at kv_len[b])
+    psg_attn_fwd_varlen_train, or - `want_lse` False, nothing kept for a backward, no dropout - psg_attn_fwd_varlen."""
+    lib = _lib_for(q_src)
+    dtype = q_src.dtype
+    qr, kvr, io, dims, E = _attn_operands(q_src, kv_src, heads)
+    B, _, L, _, d = dims
+    o = torch.empty((B, L, E), dtype=dtype, device=q_src.device)
+    lse = torch.empty((B, heads, L), dtype=torch.float32, device=q_src.device) if want_lse else None
+    args = (*io, ptr(o), E, ptr(lse), *dims, float(d) ** -0.5, float(drop_p), int(seed), dtype_code(dtype))
+    if kv_len is None:
+        check(lib.psg_attn_fwd(*args, stream_ptr()), "psg_attn_fwd")
+    elif want_lse:
+        check(lib.psg_attn_fwd_varlen_train(*args, ptr(kv_len), stream_ptr()), "psg_attn_fwd_varlen_train")
+    else:
+        check(lib.psg_attn_fwd_varlen(*args, ptr(kv_len), stream_ptr()), "psg_attn_fwd_varlen")
+    return o, lse, qr, kvr
+
+
 class _AttnFn(torch.autograd.Function):
     """softmax((q/sqrt(d)) k^T) v for packed projections.  self: qkv [B,L,3E]; cross: q [B,L,E], kv [B,S,2E].
     With `kv_len` (int32 [B] on the device) the keys of sample b end at kv_len[b]: psg_attn_fwd_varlen_train / psg_attn_bwd_varlen."""
 
     @staticmethod
     def forward(ctx, q_src, kv_src, heads, drop_p, seed, kv_len=None):
-        lib = _lib_for(q_src)
-        dtype = q_src.dtype
-        self_mode = kv_src is None
-        qr, ldq = _rows(q_src)
-        B, L = q_src.shape[0], q_src.shape[1]
-        esz = qr.element_size()
-        if self_mode:
-            E = q_src.shape[-1] // 3
-            S = L
-            kp, vp, ldk = qr.data_ptr() + E * esz, qr.data_ptr() + 2 * E * esz, ldq
-            kvr = None
-        else:
-            E = q_src.shape[-1]
-            kvr, ldk = _rows(kv_src)
-            S = kv_src.shape[1]
-            kp, vp = kvr.data_ptr(), kvr.data_ptr() + E * esz
-        d = E // heads
-        scale = float(d) ** -0.5
-        o = torch.empty((B, L, E), dtype=dtype, device=q_src.device)
-        lse = torch.empty((B, heads, L), dtype=torch.float32, device=q_src.device)
-        if kv_len is None:
-            check(lib.psg_attn_fwd(qr.data_ptr(), ldq, kp, ldk, vp, ldk, ptr(o), E, ptr(lse), B, heads, L, S, d, scale, float(drop_p),
-                                   int(seed), dtype_code(dtype), stream_ptr()), "psg_attn_fwd")
-        else:
-            check(lib.psg_attn_fwd_varlen_train(qr.data_ptr(), ldq, kp, ldk, vp, ldk, ptr(o), E, ptr(lse), B, heads, L, S, d, scale,
-                                                float(drop_p), int(seed), dtype_code(dtype), ptr(kv_len), stream_ptr()),
-                  "psg_attn_fwd_varlen_train")
+        o, lse, qr, kvr = attention_fwd(q_src, kv_src, heads, drop_p, seed, kv_len)
         ctx.kv_len = kv_len
         ctx.save_for_backward(qr, kvr, o, lse)
-        ctx.meta = (self_mode, B, L, S, E, heads, d, scale, drop_p, seed, ldq, ldk, tuple(q_src.shape), None if self_mode else tuple(kv_src.shape))
+        ctx.meta = (heads, drop_p, seed)
         return o
 
     @staticmethod
     def backward(ctx, do):
         qr, kvr, o, lse = ctx.saved_tensors
-        self_mode, B, L, S, E, heads, d, scale, drop_p, seed, ldq, ldk, qshape, kvshape = ctx.meta
+        heads, drop_p, seed = ctx.meta
+        _, _, io, dims, _ = _attn_operands(qr, kvr, heads, True)
+        B, _, L, _, d = dims
         lib = _lib_for(do)
         dtype = do.dtype
         dor, lddo = _rows(do)
-        esz = qr.element_size()
         delta = torch.empty((B, heads, L), dtype=torch.float32, device=do.device)
-        if self_mode:
-            dqkv = torch.empty(qshape, dtype=dtype, device=do.device)
-            W3 = 3 * E
-            kp, vp = qr.data_ptr() + E * esz, qr.data_ptr() + 2 * E * esz
-            dqp, dkp, dvp, lddq, lddk = dqkv.data_ptr(), dqkv.data_ptr() + E * esz, dqkv.data_ptr() + 2 * E * esz, W3, W3
-            dkv = None
-        else:
-            dqkv = torch.empty(qshape, dtype=dtype, device=do.device)
-            dkv = torch.empty(kvshape, dtype=dtype, device=do.device)
-            kp, vp = kvr.data_ptr(), kvr.data_ptr() + E * esz
-            dqp, dkp, dvp, lddq, lddk = dqkv.data_ptr(), dkv.data_ptr(), dkv.data_ptr() + E * esz, E, 2 * E
+        dqkv = torch.empty(qr.shape, dtype=dtype, device=do.device)
+        dkv = None if kvr is None else torch.empty(kvr.shape, dtype=dtype, device=do.device)
+        args = (*io, ptr(o), o.shape[-1], ptr(dor), lddo, ptr(lse), ptr(delta), *_attn_operands(dqkv, dkv, heads, True)[2], *dims,
+                float(d) ** -0.5, float(drop_p), int(seed), dtype_code(dtype))
         if ctx.kv_len is None:
-            check(lib.psg_attn_bwd(qr.data_ptr(), ldq, kp, ldk, vp, ldk, ptr(o), E, ptr(dor), lddo, ptr(lse), ptr(delta), dqp, lddq, dkp,
-                                   lddk, dvp, lddk, B, heads, L, S, d, scale, float(drop_p), int(seed), dtype_code(dtype), stream_ptr()),
-                  "psg_attn_bwd")
+            check(lib.psg_attn_bwd(*args, stream_ptr()), "psg_attn_bwd")
         else:
-            check(lib.psg_attn_bwd_varlen(qr.data_ptr(), ldq, kp, ldk, vp, ldk, ptr(o), E, ptr(dor), lddo, ptr(lse), ptr(delta), dqp, lddq,
-                                          dkp, lddk, dvp, lddk, B, heads, L, S, d, scale, float(drop_p), int(seed), dtype_code(dtype),
-                                          ptr(ctx.kv_len), stream_ptr()), "psg_attn_bwd_varlen")
+            check(lib.psg_attn_bwd_varlen(*args, ptr(ctx.kv_len), stream_ptr()), "psg_attn_bwd_varlen")
         return dqkv, dkv, None, None, None, None
 
 
@@ -1325,41 +1324,29 @@ class _AttnLongQFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q_src, kv_src, heads):
-        lib = _lib_for(q_src)
-        dtype = q_src.dtype
-        qr, ldq = _rows(q_src)
-        kvr, ldk = _rows(kv_src)
-        B, L, E = q_src.shape
-        S = kv_src.shape[1]
-        d = E // heads
-        scale = float(d) ** -0.5
-        esz = qr.element_size()
-        o = torch.empty((B, L, E), dtype=dtype, device=q_src.device)
-        lse = torch.empty((B, heads, L), dtype=torch.float32, device=q_src.device)
-        check(lib.psg_attn_fwd(qr.data_ptr(), ldq, kvr.data_ptr(), ldk, kvr.data_ptr() + E * esz, ldk, ptr(o), E, ptr(lse), B, heads, L, S, d,
-                               scale, 0.0, 0, dtype_code(dtype), stream_ptr()), "psg_attn_fwd")
+        o, lse, qr, kvr = attention_fwd(q_src, kv_src, heads)
         ctx.save_for_backward(qr, kvr, o, lse)
-        ctx.meta = (B, L, S, E, heads, d, scale, ldq, ldk)
+        ctx.heads = heads
         return o
 
     @staticmethod
     def backward(ctx, do):
         qr, kvr, o, lse = ctx.saved_tensors
-        B, L, S, E, heads, d, scale, ldq, ldk = ctx.meta
+        heads = ctx.heads
+        _, _, io, dims, E = _attn_operands(qr, kvr, heads, True)
+        B, _, L, S, d = dims
         lib = _lib_for(do)
         dtype = do.dtype
         dor, lddo = _rows(do)
-        esz = qr.element_size()
         delta = torch.empty((B, heads, L), dtype=torch.float32, device=do.device)
         dq = torch.empty((B, L, E), dtype=dtype, device=do.device)
         dkv = torch.empty((B, S, 2 * E), dtype=dtype, device=do.device)
-        need = lib.psg_attn_bwd_longq_workspace_bytes(B, heads, L, S, d)
+        need = lib.psg_attn_bwd_longq_workspace_bytes(*dims)
         if need < 0:
             check(-1, "psg_attn_bwd_longq_workspace_bytes")
         ws = _lib.workspace(need, do.device)
-        check(lib.psg_attn_bwd_longq(qr.data_ptr(), ldq, kvr.data_ptr(), ldk, kvr.data_ptr() + E * esz, ldk, ptr(o), E, ptr(dor), lddo, ptr(lse),
-                                     ptr(delta), dq.data_ptr(), E, dkv.data_ptr(), 2 * E, dkv.data_ptr() + E * esz, 2 * E, B, heads, L, S, d,
-                                     scale, 0.0, 0, dtype_code(dtype), ptr(ws), ws.numel(), stream_ptr()), "psg_attn_bwd_longq")
+        check(lib.psg_attn_bwd_longq(*io, ptr(o), E, ptr(dor), lddo, ptr(lse), ptr(delta), *_attn_operands(dq, dkv, heads, True)[2], *dims,
+                                     float(d) ** -0.5, 0.0, 0, dtype_code(dtype), ptr(ws), ws.numel(), stream_ptr()), "psg_attn_bwd_longq")
         return dq, dkv, None
 
 
@@ -1411,16 +1398,19 @@ def prepared(cache, key, param_list, build):
     return ent[1]
 
 
-def conv_infer(x, wf, bias, Cin, Cout, ks, stride, pad, act=ACT_NONE, residual=None, out_dtype=None):
-    """x [B,H,W,Cin] channels-last (rows 16-byte aligned) -> [B,Ho,Wo,Cout]; wf = prepared weight [Cout][Kpad]."""
+def conv_infer(x, wf, bias, Cin, Cout, ks=1, stride=1, pad=0, act=ACT_NONE, residual=None, out_dtype=None):
+    """psg_conv_fwd on a prepared weight wf [Cout][Kpad], nothing kept for a backward.  x [B,H,W,Cin] channels-last (rows
+    16-byte aligned) -> [B,Ho,Wo,Cout]; a 2-D x [M,Cin] is a Linear (ks = 1) -> [M,Cout]."""
     lib = _lib_for(x)
     xr, ldx = _rows(x)
-    B, Hi, Wi = x.shape[0], x.shape[1], x.shape[2]
-    Ho, Wo = (Hi + 2 * pad - ks) // stride + 1, (Wi + 2 * pad - ks) // stride + 1
-    y = torch.empty((B, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
+    if x.dim() == 4:
+        geom = _conv_geom(x, ks, stride, pad)
+        out_shape = (geom[0], geom[3], geom[4], Cout)
+    else:
+        geom, out_shape = _linear_geom(x.shape[0]), (x.shape[0], Cout)
+    y = torch.empty(out_shape, dtype=x.dtype, device=x.device)
     res_r, ld_res = (None, 0) if residual is None else _rows(residual)
-    _conv_launch(lib, x.dtype, xr, ldx, wf, 0, y, Cout, (B, Hi, Wi, Ho, Wo, ks, stride, pad), Cin, Cout, bias=bias,
-                 residual=res_r, ld_res=ld_res, act=act)
+    _conv_launch(lib, x.dtype, xr, ldx, wf, 0, y, Cout, geom, Cin, Cout, bias=bias, residual=res_r, ld_res=ld_res, act=act)
     return y
 
 
@@ -1604,40 +1594,41 @@ def upsample_bilinear(x, size):
     return _UpsampleFn.apply(x, int(size[0]), int(size[1]))
 
 
+def nhwc_rows_to_nchw(xr, ldx, C):
+    """The first C columns of the rows of xr [B,H,W,>=C] (row stride ldx, compute dtype) -> fp32 [B,C,H,W]: psg_nhwc_to_nchw."""
+    lib = _lib_for(xr)
+    B, H, W = xr.shape[0], xr.shape[1], xr.shape[2]
+    y = torch.empty((B, C, H, W), dtype=torch.float32, device=xr.device)
+    check(lib.psg_nhwc_to_nchw(ptr(xr), ldx, ptr(y), B, C, H * W, dtype_code(xr.dtype), stream_ptr()), "psg_nhwc_to_nchw")
+    return y
+
+
+def nchw_to_nhwc(x, dtype, width=None):
+    """[B,C,H,W] fp32 -> [B,H,W,C] compute dtype (network input; no gradient): psg_nchw_to_nhwc.  `width` > C: rows of that
+    many columns, the padding columns zero."""
+    lib = _lib_for(x)
+    xc = x.detach().contiguous().float()
+    B, Cc, H, W = xc.shape
+    width = Cc if width is None else width
+    y = (torch.empty if width == Cc else torch.zeros)((B, H, W, width), dtype=dtype, device=x.device)
+    check(lib.psg_nchw_to_nhwc(ptr(xc), ptr(y), width, B, Cc, H * W, dtype_code(dtype), stream_ptr()), "psg_nchw_to_nhwc")
+    return y
+
+
 class _ToNCHWFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        lib = _lib_for(x)
-        xr, ldx = _rows(x)
-        B, H, W, Cc = x.shape
-        y = torch.empty((B, Cc, H, W), dtype=torch.float32, device=x.device)
-        check(lib.psg_nhwc_to_nchw(ptr(xr), ldx, ptr(y), B, Cc, H * W, dtype_code(x.dtype), stream_ptr()), "psg_nhwc_to_nchw")
-        ctx.meta = (B, H, W, Cc, x.dtype)
-        return y
+        ctx.dtype = x.dtype
+        return nhwc_rows_to_nchw(*_rows(x), x.shape[-1])
 
     @staticmethod
     def backward(ctx, dy):
-        B, H, W, Cc, dtype = ctx.meta
-        lib = _lib_for(dy)
-        dyc = dy.contiguous().float()
-        dx = torch.empty((B, H, W, Cc), dtype=dtype, device=dy.device)
-        check(lib.psg_nchw_to_nhwc(ptr(dyc), ptr(dx), Cc, B, Cc, H * W, dtype_code(dtype), stream_ptr()), "psg_nchw_to_nhwc")
-        return dx
+        return nchw_to_nhwc(dy, ctx.dtype)
 
 
 def nhwc_to_nchw(x):
     """channels-last compute dtype -> the reference's NCHW fp32 boundary layout (differentiable)."""
     return _ToNCHWFn.apply(x)
-
-
-def nchw_to_nhwc(x, dtype):
-    """[B,C,H,W] fp32 -> [B,H,W,C] compute dtype (network input; no gradient)."""
-    lib = _lib_for(x)
-    xc = x.detach().contiguous().float()
-    B, Cc, H, W = xc.shape
-    y = torch.empty((B, H, W, Cc), dtype=dtype, device=x.device)
-    check(lib.psg_nchw_to_nhwc(ptr(xc), ptr(y), Cc, B, Cc, H * W, dtype_code(dtype), stream_ptr()), "psg_nchw_to_nhwc")
-    return y
 
 
 class _ToNHWCFn(torch.autograd.Function):
@@ -1662,21 +1653,13 @@ class _ImageOutFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, cout):
-        lib = _lib_for(y)
-        B, H, W, Cc = y.shape
-        img = torch.empty((B, cout, H, W), dtype=torch.float32, device=y.device)
-        check(lib.psg_nhwc_to_nchw(ptr(y), Cc, ptr(img), B, cout, H * W, dtype_code(y.dtype), stream_ptr()), "psg_nhwc_to_nchw")
-        ctx.meta = (B, H, W, Cc, cout, y.dtype)
-        return img
+        ctx.meta = (y.shape[-1], y.dtype)
+        return nhwc_rows_to_nchw(y, y.shape[-1], cout)
 
     @staticmethod
     def backward(ctx, dimg):
-        B, H, W, Cc, cout, dtype = ctx.meta
-        lib = _lib_for(dimg)
-        dc = dimg.contiguous().float()
-        dy = torch.zeros((B, H, W, Cc), dtype=dtype, device=dimg.device)
-        check(lib.psg_nchw_to_nhwc(ptr(dc), ptr(dy), Cc, B, cout, H * W, dtype_code(dtype), stream_ptr()), "psg_nchw_to_nhwc")
-        return dy, None
+        Cc, dtype = ctx.meta
+        return nchw_to_nhwc(dimg, dtype, width=Cc), None
 
 
 def image_out(y, cout):

@@ -41,7 +41,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from ._lib import ACT_GELU, ACT_NONE, check, dtype_code, ptr, stream_ptr
+from ._lib import ACT_GELU
 from .unet import _SeedStream
 from .vae import _prep, _prepared
 
@@ -156,40 +156,14 @@ class _Bert(nn.Module):
         self.pooler = _Pooler(c["hidden_size"])
 
 
-def _linear(x, wf, bias, cout, act=ACT_NONE, residual=None, out=None):
-    """[M, Cin] rows (16-byte aligned, contiguous) -> [M, cout] in x's dtype: psg_conv_fwd as a Linear with fused epilogue."""
-    lib = ops._lib_for(x)
-    M, cin = x.shape
-    y = torch.empty((M, cout), dtype=x.dtype, device=x.device) if out is None else out
-    ops._conv_launch(lib, x.dtype, x, cin, wf, 0, y, cout, (M, 1, 1, 1, 1, 1, 1, 0), cin, cout, bias=bias,
-                     residual=residual, ld_res=cout if residual is not None else 0, act=act)
-    return y
-
-
 def layer_norm(x, weight, bias, eps, residual=None, out_dtype=None):
     """y = LayerNorm(x [+ residual]) * weight + bias over the last dimension (psg_layernorm); x [..., N] contiguous."""
-    lib = ops._lib_for(x)
-    N = x.shape[-1]
-    rows = x.numel() // N
-    out_dtype = x.dtype if out_dtype is None else out_dtype
-    y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-    check(lib.psg_layernorm(ptr(x), N, ptr(residual), N if residual is not None else 0, ptr(y), N, ptr(weight), ptr(bias), rows, N,
-                            float(eps), dtype_code(x.dtype), dtype_code(out_dtype), stream_ptr()), "psg_layernorm")
-    return y
+    return ops.layer_norm_fwd(x, weight, bias, eps, residual, out_dtype)[0]
 
 
 def attention_varlen(qkv, kv_len, heads):
     """Self-attention of packed projections qkv [B, S, 3E] with the keys of sample b limited to kv_len[b] (int32, device)."""
-    lib = ops._lib_for(qkv)
-    B, S, E3 = qkv.shape
-    E = E3 // 3
-    d = E // heads
-    esz = qkv.element_size()
-    o = torch.empty((B, S, E), dtype=qkv.dtype, device=qkv.device)
-    base = qkv.data_ptr()
-    check(lib.psg_attn_fwd_varlen(base, E3, base + E * esz, E3, base + 2 * E * esz, E3, ptr(o), E, None, B, heads, S, S, d,
-                                  float(d) ** -0.5, 0.0, 0, dtype_code(qkv.dtype), ptr(kv_len), stream_ptr()), "psg_attn_fwd_varlen")
-    return o
+    return ops.attention_fwd(qkv, None, heads, kv_len=kv_len, want_lse=False)[0]
 
 
 class TextEncoder(nn.Module):
@@ -297,17 +271,11 @@ class TextEncoder(nn.Module):
         ps = [sa.query.weight, sa.key.weight, sa.value.weight, sa.query.bias, sa.key.bias, sa.value.bias]
         return _prepared(self._cache, ("qkv_train", i, dt), ps, lambda: ops.prep_qkv(*ps, dt, True))
 
-    def _embed(self, ids, tt, B, S, dt, dev):
-        c = self.bert.config
-        H = c["hidden_size"]
-        lib = ops._lib_for(self.layer_norm.weight)
+    def _embed(self, ids, tt, dt, drop_p=0.0, seed=0):
+        """BertEmbeddings on the inference launches (the embedding dropout in place when drop_p > 0)."""
         emb = self.bert.embeddings
-        x = torch.empty((B * S, H), dtype=dt, device=dev)
-        check(lib.psg_bert_embed_ln(ptr(ids), ptr(tt), ptr(emb.word_embeddings.weight), ptr(emb.position_embeddings.weight),
-                                    ptr(emb.token_type_embeddings.weight), ptr(emb.LayerNorm.weight), ptr(emb.LayerNorm.bias), ptr(x), H,
-                                    B, S, H, c["vocab_size"], c["max_position_embeddings"], c["type_vocab_size"], c["layer_norm_eps"],
-                                    dtype_code(dt), stream_ptr()), "psg_bert_embed_ln")
-        return x
+        return ops.bert_embed_fwd(ids, tt, emb.word_embeddings.weight, emb.position_embeddings.weight, emb.token_type_embeddings.weight,
+                                  emb.LayerNorm.weight, emb.LayerNorm.bias, self.bert.config["layer_norm_eps"], dt, drop_p, seed)
 
     def _layer_infer(self, i, x, kv_len, B, S):
         """Encoder layer i on the inference launches (nothing kept for a backward)."""
@@ -317,11 +285,11 @@ class TextEncoder(nn.Module):
         lay = self.bert.encoder.layer[i]
         (wqkv, bqkv), wo, w1, w2 = self._layer_weights(i, dt)
         ao, it, ou = lay.attention.output, lay.intermediate.dense, lay.output
-        qkv = _linear(x, wqkv, bqkv, 3 * H)
+        qkv = ops.conv_infer(x, wqkv, bqkv, H, 3 * H)
         ctx = attention_varlen(qkv.view(B, S, 3 * H), kv_len, heads).view(B * S, H)
-        h = layer_norm(_linear(ctx, wo, ao.dense.bias, H, residual=x), ao.LayerNorm.weight, ao.LayerNorm.bias, eps)
-        u = _linear(h, w1, it.bias, I, act=ACT_GELU)
-        return layer_norm(_linear(u, w2, ou.dense.bias, H, residual=h), ou.LayerNorm.weight, ou.LayerNorm.bias, eps)
+        h = layer_norm(ops.conv_infer(ctx, wo, ao.dense.bias, H, H, residual=x), ao.LayerNorm.weight, ao.LayerNorm.bias, eps)
+        u = ops.conv_infer(h, w1, it.bias, H, I, act=ACT_GELU)
+        return layer_norm(ops.conv_infer(u, w2, ou.dense.bias, I, H, residual=h), ou.LayerNorm.weight, ou.LayerNorm.bias, eps)
 
     def _layer_autograd(self, i, x, kv_len, B, S, ph, pa):
         """Encoder layer i through the autograd nodes of `ops` (dropouts ph / pa drawn when > 0)."""
@@ -358,19 +326,19 @@ class TextEncoder(nn.Module):
         return self._encode_train(ids, kv_len, tt, drop)
 
     def _encode_frozen(self, ids, kv_len, tt):
-        dev, dt = ids.device, self.compute_dtype
+        dt = self.compute_dtype
         B, S = ids.shape
-        x = self._embed(ids, tt, B, S, dt, dev)
+        x = self._embed(ids, tt, dt)
         for i in range(len(self.bert.encoder.layer)):
             x = self._layer_infer(i, x, kv_len, B, S)
         if isinstance(self.projection, nn.Linear):
             wp = _prepared(self._cache, ("proj", dt), [self.projection.weight], lambda: _prep(self.projection.weight[:, :, None, None], dt))
-            x = _linear(x, wp, self.projection.bias, self.hidden_dim)
+            x = ops.conv_infer(x, wp, self.projection.bias, self.bert_hidden_size, self.hidden_dim)
         y = layer_norm(x, self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps, out_dtype=torch.float32)
         return y.view(B, S, self.hidden_dim)
 
     def _encode_train(self, ids, kv_len, tt, drop):
-        dev, dt = ids.device, self.compute_dtype
+        dt = self.compute_dtype
         B, S = ids.shape
         ph, pa = (self.hidden_dropout_prob, self.attention_probs_dropout_prob) if drop else (0.0, 0.0)
         first = self.first_trainable_layer()
@@ -384,12 +352,7 @@ class TextEncoder(nn.Module):
                                _SeedStream.next() if ph > 0 else 0)
         with torch.no_grad():                       # the frozen prefix: no graph, no saved activation
             if not train_emb:
-                x = self._embed(ids, tt, B, S, dt, dev)
-                if ph > 0:                          # BertEmbeddings' dropout, in place
-                    lib = ops._lib_for(x)
-                    H = x.shape[1]
-                    check(lib.psg_dropout_apply(ptr(x), H, ptr(x), H, B * S, H, ph, _SeedStream.next(), 1.0 / (1.0 - ph), dtype_code(dt),
-                                                stream_ptr()), "psg_dropout_apply")
+                x = self._embed(ids, tt, dt, ph, _SeedStream.next() if ph > 0 else 0)
             for i in range(first):
                 x = self._layer_autograd(i, x, kv_len, B, S, ph, pa) if drop else self._layer_infer(i, x, kv_len, B, S)
         for i in range(first, len(self.bert.encoder.layer)):

@@ -167,14 +167,10 @@ class VAEEncoder(nn.Module):
         if not x.is_cuda:
             raise _lib.PsgError("VAEEncoder (MI355X build) needs GPU tensors; there is no CPU fallback")
         dt = self.compute_dtype
-        lib = ops._lib_for(x)
-        B, Cin = x.shape[0], x.shape[1]
+        Cin = x.shape[1]
         # image -> channels-last with the channel count padded to one 16-byte chunk (zeros; the weights are padded alike)
         cpad = (-Cin) % 8
-        h = torch.zeros((B, x.shape[2], x.shape[3], Cin + cpad), dtype=dt, device=x.device)
-        xc = x.detach().contiguous().float()
-        check(lib.psg_nchw_to_nhwc(ptr(xc), ptr(h), Cin + cpad, B, Cin, x.shape[2] * x.shape[3], _lib.dtype_code(dt), stream_ptr()),
-              "psg_nchw_to_nhwc")
+        h = ops.nchw_to_nhwc(x, dt, width=Cin + cpad)
         for i, m in enumerate(self.encoder):
             if isinstance(m, nn.Conv2d):
                 pin = cpad if i == 0 else 0
@@ -190,7 +186,7 @@ class VAEEncoder(nn.Module):
             eps = torch.randn_like(mu) if generator is None else torch.randn(mu.shape, dtype=mu.dtype, device=mu.device, generator=generator)
         eps = eps.to(device=mu.device, dtype=torch.float32).contiguous()
         latent = torch.empty_like(mu)
-        check(lib.psg_reparam_f32(ptr(mu), ptr(logvar), ptr(eps), ptr(latent), mu.numel(), stream_ptr()), "psg_reparam_f32")
+        check(ops._lib_for(mu).psg_reparam_f32(ptr(mu), ptr(logvar), ptr(eps), ptr(latent), mu.numel(), stream_ptr()), "psg_reparam_f32")
         return latent, mu, logvar
 
 
@@ -267,11 +263,7 @@ class VAEDecoder(nn.Module):
         wf = _prepared(self._cache, ("fc", dt), [conv.weight, conv.bias],
                        lambda: (_prep(conv.weight, dt, pad_out=opad), torch.nn.functional.pad(conv.bias.detach().float(), (0, opad)).contiguous()))
         y = _conv(x, wf[0], wf[1], conv.in_channels, cout + opad, 3, 1, 1, act=ACT_TANH)
-        lib = ops._lib_for(y)
-        B, H, W, _ = y.shape
-        img = torch.empty((B, cout, H, W), dtype=torch.float32, device=y.device)
-        check(lib.psg_nhwc_to_nchw(ptr(y), cout + opad, ptr(img), B, cout, H * W, _lib.dtype_code(dt), stream_ptr()), "psg_nhwc_to_nchw")
-        return img
+        return ops.nhwc_rows_to_nchw(y, cout + opad, cout)
 
 
 class PokemonVAE(nn.Module):
