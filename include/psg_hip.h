@@ -363,6 +363,34 @@ typedef struct psg_wgrad_desc {
 } psg_wgrad_desc;
 int psg_conv_wgrad(const psg_wgrad_desc* d, psg_stream_t stream);
 int64_t psg_conv_wgrad_workspace_bytes(const psg_wgrad_desc* d);
+/* Family pin: v = 0..3 makes every psg_conv_wgrad launch run the kernel family narrow-128, narrow-160, wide or pipe (the
+ * `family` values of psg_conv_wgrad_route) instead of the plan's choice (kernel A/B runs, the route tests); -1 (any other
+ * value) gives the choice back to the plan.  A pin skips the plan's profitability thresholds (column waste, minimum tile
+ * counts, "only where 128 does not divide Cout") and keeps what the kernels need: narrow-160, wide and pipe exist for bf16 and
+ * the stride-1 same-size geometries only, narrow-160 needs Cout % 160 == 0, pipe Cout % 320 == 0, a dY extent below 2 GiB less
+ * 64 rows and - with dbias - at least 10 column tiles.  Pinned where it cannot run, psg_conv_wgrad and psg_conv_wgrad_route
+ * return PSG_ERR_ARG, psg_conv_wgrad_workspace_bytes -1, and nothing is launched. */
+int psg_conv_wgrad_set_variant(int v);
+/* Split pin: n > 0 makes every launch ask for n K splits (the environment variable PSG_WGRAD_SPLITS is the initial value; the
+ * launch gets ceil(steps / ceil(steps / n)) of them); 0 returns the choice to the makespan model. */
+int psg_conv_wgrad_set_splits(int n);
+/* Host-only: which kernels psg_conv_wgrad(d) would launch, and how.  Runs the descriptor checks of
+ * psg_conv_wgrad_workspace_bytes and the same plan - honouring psg_conv_wgrad_set_variant / _set_splits, the PSG_WGRAD_*
+ * environment, psg_set_available_cus and psg_set_reserve_rounds - but reads no operand, initialises no device and launches
+ * nothing (the pointers of d are only tested against NULL: dbias decides whether the bias gradient rides along).
+ * out receives PSG_WGRAD_ROUTE_FIELDS values:
+ *   family       0 narrow-128 (wgrad_kernel<T, GEOM, 128>), 1 narrow-160 (<bf16, GEOM, 160>), 2 wide (wgrad_wide_kernel),
+ *                3 pipe (wgrad_pipe_kernel)
+ *   dtype, geom  psg_dtype; 0 general (strided / resizing), 1 stride-1 same-size 3x3, 2 pointwise
+ *   bias         1: the bias gradient rides in the kernel (dbias != NULL)
+ *   BR, BQ, BKP  tile: rows (co) x columns (q = tap * Cin + ci), and the K step in pixels
+ *   lds, wg_per_cu   dynamic LDS bytes of a workgroup, resident workgroups per CU
+ *   rtiles, qtiles, splits, steps_per_split, grid   tile counts, K splits, K steps of each split but the last, workgroups
+ *   finish       0: tiles written straight into dw, 1: wgrad_sum_kernel, 2: wgrad_reduce_kernel (OIHW 3x3)
+ *   bias_finish  0: no bias gradient, 1: written directly, 2: folded into wgrad_sum_kernel, 3: wgrad_bias_sum_kernel
+ *   launches     kernels launched (1..3) */
+#define PSG_WGRAD_ROUTE_FIELDS 17
+int psg_conv_wgrad_route(const psg_wgrad_desc* d, int32_t* out);
 
 /* Master weight (w_dtype PSG_F32, or PSG_BF16 for the AdamW shadow copy; w_layout PSG_W_OIHW or PSG_W_OHWI memory
  * order; a bf16 source must be OHWI or 1x1) -> prepared forward weight wf [O][Kpad] with k=(kh,kw,ci) and prepared

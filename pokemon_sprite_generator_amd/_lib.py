@@ -87,6 +87,9 @@ SIGNATURES = {
     "psg_conv_route": (c_int, [C.POINTER(ConvDesc), c_void_p]),
     "psg_conv_wgrad": (c_int, [C.POINTER(WgradDesc), c_void_p]),
     "psg_conv_wgrad_workspace_bytes": (c_int64, [C.POINTER(WgradDesc)]),
+    "psg_conv_wgrad_set_variant": (c_int, [c_int]),
+    "psg_conv_wgrad_set_splits": (c_int, [c_int]),
+    "psg_conv_wgrad_route": (c_int, [C.POINTER(WgradDesc), c_void_p]),
     "psg_prep_weight": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "psg_kpad": (c_int64, [c_int64, c_int]),
     "psg_colsum": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),

@@ -29,15 +29,77 @@ struct WgP {
     int B, Hi, Wi, Cin, Ho, Wo, Cout, ks, stride, pad;
     int M, Q, taps;
     int rtiles, qtiles, splits, steps_per_split;   // steps of BKP pixels
-    int BR;                                        // output rows (co) per tile: 128, or 160 = exact tiling of Cout = 320
-    int wide;                                      // 1: wgrad_wide_kernel (128 x 256 tile, 32-pixel K steps)
-    float inv_HoWo, inv_Wo;
     uint32_t x_bytes, dy_bytes;
 };
 
 template <typename T> struct WgCfg;
 template <> struct WgCfg<bf16_t> { static constexpr int BKP = 64; static constexpr int ROWB = 256; };  // bytes per LDS row
 template <> struct WgCfg<float> { static constexpr int BKP = 32; static constexpr int ROWB = 512; };
+
+// ---- pieces the three MFMA kernels share (their staging layouts, swizzle keys and pipelines stay their own) -----------------
+// block -> (split, col tile, row tile), split SLOWEST: workgroups resident together then sweep the same pixel
+// range (every output tile needs the same dY / X rows of that range), so operands are served from L2 instead
+// of each tile streaming its own pixels from HBM.  XCD-aware: each XCD gets a contiguous range of logical ids.
+struct WgTile { int split, rt, qt; };
+__device__ __forceinline__ WgTile wg_tile(const WgP& p) {
+    const int nb = gridDim.x, b0 = blockIdx.x;
+    const int q = nb >> 3, r = nb & 7, xcd = b0 & 7;
+    const int lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b0 >> 3);
+    const int tiles = p.rtiles * p.qtiles;
+    WgTile t;
+    t.split = lid / tiles;
+    const int tix = lid - t.split * tiles;
+    t.rt = tix % p.rtiles; t.qt = tix / p.rtiles;
+    return t;
+}
+// the K steps (of BKP pixels) of a split: the last split may be shorter
+template <int BKP> __device__ __forceinline__ int wg_nsteps(const WgP& p, int step0) {
+    const int total_steps = (p.M + BKP - 1) / BKP;
+    int nsteps = total_steps - step0;
+    if (nsteps > p.steps_per_split) nsteps = p.steps_per_split;
+    return nsteps;
+}
+// Stride-1 geometries: the source pixel of tap (kh, kw) is m + const.  Hardware offsets are unsigned: the (possibly negative)
+// tap shift is folded into a descriptor whose base sits pad rows + pad pixels BEFORE x, so the per-lane offset is >= 0; taps
+// that would read below x are never valid.
+__device__ __forceinline__ u32x4 wg_shifted_x(const WgP& p, int ldxB) {
+    const int g_shift = (p.pad * p.Wi + p.pad) * ldxB;
+    return make_rsrc(reinterpret_cast<const char*>(p.x) - g_shift, p.x_bytes + (uint32_t)g_shift);
+}
+// Transposed fragment reads: ds_read_b64_tr_b16 hands lane i16 column i16 of four consecutive pixel rows; two of them (rows
+// +0..3 and +4..7 of a group) make the 8 consecutive reduction indices of one 16x16x32 operand.
+typedef __attribute__((ext_vector_type(8))) short s16x8;
+__device__ __forceinline__ s16x4 wg_tr(const char* a) { return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a)); }
+__device__ __forceinline__ bf16x8 wg_cat(s16x4 a, s16x4 c) { s16x8 v = {a[0], a[1], a[2], a[3], c[0], c[1], c[2], c[3]}; return *reinterpret_cast<bf16x8*>(&v); }
+__device__ __forceinline__ bf16x8 wg_frag(const char* lo, const char* hi) { return wg_cat(wg_tr(lo), wg_tr(hi)); }
+// 16x16 accumulator tiles -> partial slab ws[split][co][q]: lane (l16, kq) = (lane & 15, lane >> 4) holds rows 4 kq + r of
+// column l16 of each tile; tile (i, j) sits at (co_base + 16 i, q_base + 16 j).  CO_TAIL: Cout need not be a multiple of the tile.
+template <bool CO_TAIL, int NR, int NQ>
+__device__ __forceinline__ void wg_store_tiles(const WgP& p, float* wsb, const f32x4 (&acc)[NR][NQ], int co_base, int q_base, int lane) {
+    const int l16 = lane & 15, kq = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        const int q = q_base + j * 16 + l16;
+        if (q >= p.Q) continue;
+#pragma unroll
+        for (int i = 0; i < NR; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int co = co_base + i * 16 + 4 * kq + r;
+                if (!CO_TAIL || co < p.Cout) wsb[(int64_t)co * p.Q + q] = acc[i][j][r] * p.scale;
+            }
+    }
+}
+// ... and the bias partials bw = bws[split]: column 0 of the ones-product holds the sums (the lanes with lane & 15 == 0 call this)
+template <int NR> __device__ __forceinline__ void wg_store_bias(const WgP& p, float* bw, const f32x4 (&accb)[NR], int co_base, int kq) {
+#pragma unroll
+    for (int i = 0; i < NR; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int co = co_base + i * 16 + 4 * kq + r;
+            if (co < p.Cout) bw[co] = accb[i][r] * p.scale;
+        }
+}
 
 // GEOM selects how the gathered-X row addresses are produced:
 //   0 general (stride 2, any padding): per-row (b, ho, wo) odometer
@@ -73,17 +135,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgP p) {
     // block -> (split, col tile, row tile), split SLOWEST: workgroups resident together then sweep the same pixel
     // range (every output tile needs the same dY / X rows of that range), so operands are served from L2 instead
     // of each tile streaming its own pixels from HBM.  XCD-aware: each XCD gets a contiguous range of logical ids.
-    int lid;
-    {
-        const int nb = gridDim.x, b0 = blockIdx.x;
-        const int q = nb >> 3, r = nb & 7, xcd = b0 & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b0 >> 3);
-    }
-    const int tiles = p.rtiles * p.qtiles;
-    const int split = lid / tiles;
-    const int tix = lid - split * tiles;
-    const int rt = tix % p.rtiles, qt = tix / p.rtiles;
-    const int co0 = rt * BR, q0 = qt * 128;
+    const WgTile tile = wg_tile(p);
+    const int split = tile.split, qt = tile.qt;
+    const int co0 = tile.rt * BR, q0 = qt * 128;
 
     // Tiles go global -> LDS by LDS-DMA (wave-uniform base + lane*16: whole 256/512-byte rows, unpadded).  For bf16
     // the transposed fragment reads (4 consecutive pixel rows x 64-byte column windows per half-wave) are made
@@ -104,9 +158,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgP p) {
     const int HoWo = p.Ho * p.Wo;
 
     const int step0 = split * p.steps_per_split;
-    const int total_steps = (p.M + BKP - 1) / BKP;
-    int nsteps = total_steps - step0;
-    if (nsteps > p.steps_per_split) nsteps = p.steps_per_split;
+    const int nsteps = wg_nsteps<BKP>(p, step0);
 
     constexpr uint32_t OOB = 0x80000000u;          // extents are < 2 GiB (checked on the host)
     constexpr int ESZ = (int)sizeof(T);
@@ -143,10 +195,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgP p) {
     // GEOM 1/2 state: pass 0's pixel and its two linear byte offsets; pass j adds the uniform j*RPP rows
     int g_m = step0 * BKP + sr;
     int g_a = (g_m * (int)p.lddy + a_co) * ESZ;
-    // hardware offsets are unsigned: the (possibly negative) tap shift is folded into a descriptor whose base sits
-    // pad rows + pad pixels BEFORE x, so the per-lane offset is >= 0; taps that would read below x are never valid
-    const int g_shift = (p.pad * p.Wi + p.pad) * ldxB;
-    const u32x4 xrs_g = make_rsrc(reinterpret_cast<const char*>(p.x) - g_shift, p.x_bytes + (uint32_t)g_shift);
+    const u32x4 xrs_g = wg_shifted_x(p, ldxB);
     int g_b = g_m * ldxB + (b_kh * p.Wi + b_kw) * ldxB + b_ci * ESZ;
     // BR = 160: lane e = 256 j + tid of pass j sits at (row e / 20, physical chunk e % 20) of the dY image and fetches the
     // logical chunk (physical ^ key(row)); rows >= M lie beyond the descriptor's extent and read as zeros (no per-row test)
@@ -256,7 +305,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgP p) {
             // group g of k-step s2 reads pixel rows 32*s2 + 8g + {0..3} and + {4..7}, columns tile + 4*p4..+3, and
             // lane i16 receives column i16 of those rows: element e <-> pixel 32*s2 + 8g + e, the 16x16x32 operand order.
             // A half-wave's two blocks sit 8 rows apart in the same columns: conflict-free on this swizzled image.
-            typedef __attribute__((ext_vector_type(8))) short s16x8;
             const int g = lane >> 4, i16 = lane & 15, q4 = i16 >> 2, p4 = i16 & 3;
             const int key0 = (q4 << 2) | ((2 * g) & 3), key1 = (q4 << 2) | ((2 * g + 1) & 3);   // swizzle keys of the 2 rows
             const int rowb = (8 * g + q4) * ROWB + 8 * (p4 & 1);
@@ -270,19 +318,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgP p) {
                 const char* ra = ab + s2 * 32 * AROWB + rowa;
                 const char* rb = bb + s2 * 32 * ROWB + rowb;
 #pragma unroll
-                for (int i = 0; i < NR; ++i) {
-                    s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ra + (((chA + 2 * i) ^ ka0) << 4)));
-                    s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ra + 4 * AROWB + (((chA + 2 * i) ^ ka1) << 4)));
-                    s16x8 av = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-                    af[s2][i] = *reinterpret_cast<bf16x8*>(&av);
-                }
+                for (int i = 0; i < NR; ++i) af[s2][i] = wg_frag(ra + (((chA + 2 * i) ^ ka0) << 4), ra + 4 * AROWB + (((chA + 2 * i) ^ ka1) << 4));
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    s16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(rb + (((chB + 2 * i) ^ key0) << 4)));
-                    s16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(rb + 4 * ROWB + (((chB + 2 * i) ^ key1) << 4)));
-                    s16x8 bv = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
-                    bf[s2][i] = *reinterpret_cast<bf16x8*>(&bv);
-                }
+                for (int i = 0; i < 4; ++i) bf[s2][i] = wg_frag(rb + (((chB + 2 * i) ^ key0) << 4), rb + 4 * ROWB + (((chB + 2 * i) ^ key1) << 4));
             }
             __builtin_amdgcn_sched_barrier(0);      // reads above, MFMA stream below
 #pragma unroll
@@ -329,15 +367,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgP p) {
     if (do_bias) {                                 // column 0 of the ones-product holds the sums
         float* bw = p.bws + (int64_t)split * p.Cout;
         if constexpr (FT16) {
-            if ((lane & 15) == 0) {
-#pragma unroll
-                for (int i = 0; i < NR; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int co = co0 + wr * (BR / 2) + i * 16 + 4 * (lane >> 4) + r;
-                        if (co < p.Cout) bw[co] = accb[i][r] * p.scale;
-                    }
-            }
+            if ((lane & 15) == 0) wg_store_bias(p, bw, accb, co0 + wr * (BR / 2), lane >> 4);
         } else {
             if ((lane & 31) == 0) {
 #pragma unroll
@@ -351,20 +381,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgP p) {
         }
     }
     if constexpr (FT16) {
-        const int l16 = lane & 15, kq = lane >> 4;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int q = q0 + wc * 64 + j * 16 + l16;
-            if (q >= p.Q) continue;
-#pragma unroll
-            for (int i = 0; i < NR; ++i) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int co = co0 + wr * (BR / 2) + i * 16 + 4 * kq + r;
-                    if (co < p.Cout) wsb[(int64_t)co * p.Q + q] = acc[i][j][r] * p.scale;
-                }
-            }
-        }
+        wg_store_tiles<true>(p, wsb, acc, co0 + wr * (BR / 2), q0 + wc * 64, lane);
     } else {
         const int fr = lane & 31, fh = lane >> 5;
 #pragma unroll
@@ -417,24 +434,13 @@ __global__ __launch_bounds__(256, 2) void wgrad_wide_kernel(const WgP p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [buf][dY tile | X tile]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wr = wave & 1, wc = wave >> 1;
-    int lid;
-    {
-        const int nb = gridDim.x, b0 = blockIdx.x;
-        const int q = nb >> 3, r = nb & 7, xcd = b0 & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b0 >> 3);
-    }
-    const int tiles = p.rtiles * p.qtiles;
-    const int split = lid / tiles;
-    const int tix = lid - split * tiles;
-    const int rt = tix % p.rtiles, qt = tix / p.rtiles;
-    const int co0 = rt * BR, q0 = qt * BQ;
+    const WgTile tile = wg_tile(p);
+    const int split = tile.split, qt = tile.qt;
+    const int co0 = tile.rt * BR, q0 = qt * BQ;
 
     const int step0 = split * p.steps_per_split;
-    const int total_steps = (p.M + BKP - 1) / BKP;
-    int nsteps = total_steps - step0;
-    if (nsteps > p.steps_per_split) nsteps = p.steps_per_split;
+    const int nsteps = wg_nsteps<BKP>(p, step0);
 
-    constexpr uint32_t OOB = 0x80000000u;
     const u32x4 yrs = make_rsrc(p.dy, p.dy_bytes);
     const int ldxB = (int)p.ldx * ESZ, lddyB = (int)p.lddy * ESZ;
     // dY staging: pass j = pixels 16 j + srA, one linear offset + a uniform pass stride
@@ -462,11 +468,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_wide_kernel(const WgP p) {
     const unsigned rm_rng = (unsigned)((ho_hi + 1) * p.Wo - 1 - rm_lo);
     typedef __attribute__((address_space(3))) char* lds_ptr_t;
     const uint32_t lds_wave = (uint32_t)(size_t)(lds_ptr_t)smem + (uint32_t)__builtin_amdgcn_readfirstlane(wave) * 1024u;
-    // the tap shift is folded into a descriptor whose base sits pad rows + pad pixels BEFORE x, so the per-lane offset stays
-    // >= 0 (taps that would read below x are never valid)
     int g_mB = step0 * BKP + pxB;
-    const int g_shift = (p.pad * p.Wi + p.pad) * ldxB;
-    const u32x4 xrs_g = make_rsrc(reinterpret_cast<const char*>(p.x) - g_shift, p.x_bytes + (uint32_t)g_shift);
+    const u32x4 xrs_g = wg_shifted_x(p, ldxB);
     int g_b = g_mB * ldxB + (b_kh * p.Wi + b_kw) * ldxB + b_ci * ESZ;
     const int st_rm = BKP % HoWo, st_wo = BKP % p.Wo;
     int g_rm[NPB], g_wo[NPB];
@@ -534,13 +537,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_wide_kernel(const WgP p) {
     const int keyB = (q4 << 2) | ((g & 1) << 1);                                                    // both rows of the X image
     const int rowb = AREG + (((g >> 1) << 4) | ((g & 1) << 2) | q4) * BROWB + 8 * (p4 & 1);   // LDS row (b4, 0, b3, b1 b0); second read + 8 rows
     const int chB = wc * 16 + (p4 >> 1);
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
     auto rd_b = [&](const char* sb, int j) {
         const char* b = sb + rowb + (((chB + 2 * j) ^ keyB) << 4);
-        s16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(b));
-        s16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(b + 8 * BROWB));
-        s16x8 bv = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
-        return *reinterpret_cast<bf16x8*>(&bv);
+        return wg_frag(b, b + 8 * BROWB);
     };
 
     if (nsteps > 0) load_tiles(0);
@@ -552,12 +551,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_wide_kernel(const WgP p) {
         const char* sb = smem + buf * STAGE;
         bf16x8 af[NR];
 #pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(sb + rowa + (((chA + 2 * i) ^ keyA0) << 4)));
-            s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(sb + rowa + 4 * AROWB + (((chA + 2 * i) ^ keyA1) << 4)));
-            s16x8 av = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-            af[i] = *reinterpret_cast<bf16x8*>(&av);
-        }
+        for (int i = 0; i < NR; ++i) af[i] = wg_frag(sb + rowa + (((chA + 2 * i) ^ keyA0) << 4), sb + rowa + 4 * AROWB + (((chA + 2 * i) ^ keyA1) << 4));
         bf16x8 bf[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) bf[j] = rd_b(sb, j);
@@ -579,29 +573,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_wide_kernel(const WgP p) {
 
     float* wsb = p.ws + (int64_t)split * p.Cout * p.Q;
     const int l16 = lane & 15, kq = lane >> 4;
-    if (do_bias && l16 == 0) {             // column 0 of the ones-product holds the sums
-        float* bw = p.bws + (int64_t)split * p.Cout;
-#pragma unroll
-        for (int i = 0; i < NR; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int co = co0 + wr * (BR / 2) + i * 16 + 4 * kq + r;
-                if (co < p.Cout) bw[co] = accb[i][r] * p.scale;
-            }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int q = q0 + wc * 128 + j * 16 + l16;
-        if (q >= p.Q) continue;
-#pragma unroll
-        for (int i = 0; i < NR; ++i) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int co = co0 + wr * (BR / 2) + i * 16 + 4 * kq + r;
-                if (co < p.Cout) wsb[(int64_t)co * p.Q + q] = acc[i][j][r] * p.scale;
-            }
-        }
-    }
+    if (do_bias && l16 == 0)               // column 0 of the ones-product holds the sums
+        wg_store_bias(p, p.bws + (int64_t)split * p.Cout, accb, co0 + wr * (BR / 2), kq);
+    wg_store_tiles<true>(p, wsb, acc, co0 + wr * (BR / 2), q0 + wc * 128, lane);
 #endif
 }
 
@@ -636,23 +610,12 @@ __global__ __launch_bounds__(256, 1) void wgrad_pipe_kernel(const WgP p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wr = wave & 1, wc = wave >> 1;
-    int lid;
-    {
-        const int nb = gridDim.x, b0 = blockIdx.x;
-        const int q = nb >> 3, r = nb & 7, xcd = b0 & 7;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b0 >> 3);
-    }
-    const int tiles = p.rtiles * p.qtiles;
-    const int split = lid / tiles;
-    const int tix = lid - split * tiles;
-    const int rt = tix % p.rtiles, qt = tix / p.rtiles;
-    const int co0 = rt * BR, q0 = qt * BQ;
+    const WgTile tile = wg_tile(p);
+    const int split = tile.split, qt = tile.qt;
+    const int co0 = tile.rt * BR, q0 = qt * BQ;
     const int step0 = split * p.steps_per_split;
-    const int total_steps = (p.M + BKP - 1) / BKP;
-    int nsteps = total_steps - step0;
-    if (nsteps > p.steps_per_split) nsteps = p.steps_per_split;
+    const int nsteps = wg_nsteps<BKP>(p, step0);
 
-    constexpr uint32_t OOB = 0x80000000u;
     const u32x4 yrs = make_rsrc(p.dy, p.dy_bytes);
     const int ldxB = (int)p.ldx * ESZ, lddyB = (int)p.lddy * ESZ;
     // dY staging: element e = 256 j + tid of pass j sits at (row e / 40, physical chunk e % 40) and fetches the logical chunk
@@ -684,8 +647,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_pipe_kernel(const WgP p) {
     typedef __attribute__((address_space(3))) char* lds_ptr_t;
     const uint32_t lds_wave = (uint32_t)(size_t)(lds_ptr_t)smem + (uint32_t)__builtin_amdgcn_readfirstlane(wave) * 1024u;
     int g_mB = step0 * BKP + pxB;
-    const int g_shift = (p.pad * p.Wi + p.pad) * ldxB;
-    const u32x4 xrs_g = make_rsrc(reinterpret_cast<const char*>(p.x) - g_shift, p.x_bytes + (uint32_t)g_shift);
+    const u32x4 xrs_g = wg_shifted_x(p, ldxB);
     int g_b = g_mB * ldxB + (b_kh * p.Wi + b_kw) * ldxB + b_ci * ESZ;
     const int st_rm = BKP % HoWo, st_wo = BKP % p.Wo;
     int g_rm[NPB], g_wo[NPB];
@@ -767,20 +729,13 @@ __global__ __launch_bounds__(256, 1) void wgrad_pipe_kernel(const WgP p) {
     }
     const int rowb = AREG + (((g >> 1) << 4) | ((g & 1) << 2) | q4) * BROWB + 8 * (p4 & 1);
     const int chB = wc * 12 + (p4 >> 1);
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
     auto rd_a = [&](const char* sb, int i) {
         const char* a = sb + rowa + (((chA + 2 * i) ^ key) << 4);
-        s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a));
-        s16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 4 * AROWB));
-        s16x8 av = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-        return *reinterpret_cast<bf16x8*>(&av);
+        return wg_frag(a, a + 4 * AROWB);
     };
     auto rd_b = [&](const char* sb, int j) {
         const char* b = sb + rowb + (((chB + 2 * j) ^ key) << 4);
-        s16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(b));
-        s16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(b + 8 * BROWB));
-        s16x8 bv = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
-        return *reinterpret_cast<bf16x8*>(&bv);
+        return wg_frag(b, b + 8 * BROWB);
     };
 
     // ---- prologue: tiles 0, 1, 2 requested; tiles 0 and 1 landed; tile 0's dY fragments and X fragment 0 in registers
@@ -810,13 +765,8 @@ __global__ __launch_bounds__(256, 1) void wgrad_pipe_kernel(const WgP p) {
         // cycles = four issue slots.  So the non-MFMA work of a group (6 fragment reads, 1-2 DMA pieces, their address VALU) is
         // dealt out by hand, a slice behind each of the group's ten MFMAs, and pinned there with sched_barrier (as one block in
         // front of the ten MFMAs - the first form of this kernel - the pipe sat idle for ~250 of every ~410 cycles).
-        auto trA = [&](const char* sb_, int i, int half) {
-            return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(sb_ + rowa + (((chA + 2 * i) ^ key) << 4) + half * 4 * AROWB));
-        };
-        auto trB = [&](const char* sb_, int j_, int half) {
-            return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(sb_ + rowb + (((chB + 2 * j_) ^ key) << 4) + half * 8 * BROWB));
-        };
-        auto cat = [&](s16x4 a, s16x4 c) { s16x8 v = {a[0], a[1], a[2], a[3], c[0], c[1], c[2], c[3]}; return *reinterpret_cast<bf16x8*>(&v); };
+        auto trA = [&](const char* sb_, int i, int half) { return wg_tr(sb_ + rowa + (((chA + 2 * i) ^ key) << 4) + half * 4 * AROWB); };
+        auto trB = [&](const char* sb_, int j_, int half) { return wg_tr(sb_ + rowb + (((chB + 2 * j_) ^ key) << 4) + half * 8 * BROWB); };
         s16x4 w0 = {0, 0, 0, 0}, w1 = {0, 0, 0, 0};
         // the ones operand is written by hand, two MFMAs ahead of its use: left to the compiler it is a constant that may get
         // rematerialised (v_mov) directly in front of the asm MFMA reading it - a VALU-write -> MFMA-read hazard the hazard
@@ -852,14 +802,14 @@ __global__ __launch_bounds__(256, 1) void wgrad_pipe_kernel(const WgP p) {
                         for (int e = 0; e < 4; ++e) asm volatile("v_mov_b32 %0, 0x3f803f80" : "=v"(onesw[e]));
                     }
                     const bf16x8 ones = *reinterpret_cast<const bf16x8*>(&onesw);
-                    if (j == 3 && i == 8) w0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(sb + biasoff));
-                    if (j == 3 && i == 9) w1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(sb + biasoff + 4 * AROWB));
-                    if (j == 4 && i == 9) { const bf16x8 wf = cat(w0, w1); asm("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(accb) : "v"(wf), "v"(ones)); }
+                    if (j == 3 && i == 8) w0 = wg_tr(sb + biasoff);
+                    if (j == 3 && i == 9) w1 = wg_tr(sb + biasoff + 4 * AROWB);
+                    if (j == 4 && i == 9) { const bf16x8 wf = wg_cat(w0, w1); asm("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(accb) : "v"(wf), "v"(ones)); }
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (rdb) bn = cat(t0, t1);
-            if (rda) { nxt[2 * j] = cat(u0, u1); nxt[2 * j + 1] = cat(v0, v1); }
+            if (rdb) bn = wg_cat(t0, t1);
+            if (rda) { nxt[2 * j] = wg_cat(u0, u1); nxt[2 * j + 1] = wg_cat(v0, v1); }
         }
     };
     // (a step has 6 X fragments, so fragment 0 of every tile sits in bf0)
@@ -968,57 +918,113 @@ __global__ void wgrad_sum_kernel(const float* __restrict__ ws, float* __restrict
     }
 }
 
-static void wgrad_plan(const psg_wgrad_desc* d, WgP& p) {
-    int BKP = d->dtype == PSG_BF16 ? 64 : 32;
-    p.M = d->B * d->Ho * d->Wo;
-    p.taps = d->ksize * d->ksize;
-    p.Q = p.taps * d->Cin;
-    p.wide = 0;
-    {
-        // 160-row tiles where they tile Cout exactly and 128 does not (Cout = 320: 2 tiles instead of 2.5 -> 3)
-        static int off = -1;
-        if (off < 0) { const char* e = getenv("PSG_WGRAD_BR160"); off = (e && atoi(e) == 0) ? 1 : 0; }
-        const bool same = d->stride == 1 && d->Hi == d->Ho && d->Wi == d->Wo;
-        p.BR = (!off && d->dtype == PSG_BF16 && same && d->Cout % 160 == 0 && d->Cout % 128 != 0) ? 160 : 128;
+// ---------------------------------------------------------------------------------------------------------------------
+// Host side.  One row per kernel instantiation, one plan per launch, one settings block: psg_wgrad_init_attrs, the launch, the
+// tile / step / slot counts of the makespan model and psg_conv_wgrad_route all read the row; psg_conv_wgrad_workspace_bytes,
+// psg_conv_wgrad and psg_conv_wgrad_route all read the plan - no number is computed a second time elsewhere.  A new variant is
+// one new row (and, for a new family, its rules in wgrad_fits / wgrad_pays).
+enum WgFamily { WG_NARROW128 = 0, WG_NARROW160 = 1, WG_WIDE = 2, WG_PIPE = 3, WG_FAMILIES = 4 };
+struct WgVariant {
+    int family, dtype, geom;
+    int bias;                      // 0 / 1: the instantiation for launches without / with a bias gradient; -1: one kernel for both
+    int BR, BQ, BKP;               // tile rows (co) x columns (q), K step in pixels
+    int lds, wg_per_cu;            // dynamic LDS bytes; resident workgroups per CU (the slots of the makespan model)
+    void (*kernel)(const WgP);
+};
+// dynamic LDS: wgrad_kernel<T, GEOM, BR> double-buffers a [BKP x BR] dY tile and a [BKP x ROWB] X tile; the wide kernel two
+// 8 KB dY + 16 KB X stages; the pipe kernel four 32 KB stages + 1 KB
+template <typename T> constexpr int wgrad_lds(int BR) { return 2 * WgCfg<T>::BKP * (BR * (int)sizeof(T) + WgCfg<T>::ROWB); }
+template <typename T, int GEOM, int BR> constexpr WgVariant wg_narrow() {
+    return {BR == 160 ? WG_NARROW160 : WG_NARROW128, std::is_same<T, float>::value ? PSG_F32 : PSG_BF16, GEOM, -1,
+            BR, 128, WgCfg<T>::BKP, wgrad_lds<T>(BR), 2, wgrad_kernel<T, GEOM, BR>};
+}
+template <int GEOM> constexpr WgVariant wg_wide() { return {WG_WIDE, PSG_BF16, GEOM, -1, 128, 256, 32, 2 * (8192 + 16384), 2, wgrad_wide_kernel<GEOM>}; }
+template <int GEOM, bool BIAS> constexpr WgVariant wg_pipe() { return {WG_PIPE, PSG_BF16, GEOM, BIAS, 320, 192, 32, 4 * 32768 + 1024, 1, wgrad_pipe_kernel<GEOM, BIAS>}; }
+static const WgVariant WG_VARIANTS[] = {
+    wg_narrow<bf16_t, 0, 128>(), wg_narrow<bf16_t, 1, 128>(), wg_narrow<bf16_t, 2, 128>(),
+    wg_narrow<float, 0, 128>(),  wg_narrow<float, 1, 128>(),  wg_narrow<float, 2, 128>(),
+    wg_narrow<bf16_t, 1, 160>(), wg_narrow<bf16_t, 2, 160>(),
+    wg_wide<1>(), wg_wide<2>(),
+    wg_pipe<1, false>(), wg_pipe<2, false>(), wg_pipe<1, true>(), wg_pipe<2, true>(),
+};
+static const WgVariant* wgrad_variant(int family, int dtype, int geom, bool bias) {
+    for (const WgVariant& v : WG_VARIANTS)
+        if (v.family == family && v.dtype == dtype && v.geom == geom && (v.bias < 0 || v.bias == (int)bias)) return &v;
+    return nullptr;
+}
+// Settings: the environment, read once (PSG_WGRAD_BR160 / _WIDE / _PIPE = 0: that family off, A/B runs; _PIPE_MIN_TILES;
+// _SPLITS = n pins the split count), and the two pins of psg_conv_wgrad_set_variant / _set_splits.
+struct WgSettings {
+    bool family_on[WG_FAMILIES];
+    int pipe_min_tiles;
+    int splits, variant;           // > 0: pinned split count; 0..3: pinned family, -1: the plan's choice
+};
+static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+static WgSettings& wg_settings() {
+    static WgSettings s = {{true, env_int("PSG_WGRAD_BR160", 1) != 0, env_int("PSG_WGRAD_WIDE", 1) != 0, env_int("PSG_WGRAD_PIPE", 1) != 0},
+                           env_int("PSG_WGRAD_PIPE_MIN_TILES", 15), env_int("PSG_WGRAD_SPLITS", -1), -1};
+    return s;
+}
+struct WgPlan {
+    const WgVariant* v;
+    int M, taps, Q;
+    int rtiles, qtiles, splits, steps_per_split, grid;
+    bool native;                   // dw in the kernel's own order (OHWI, or 1x1): wgrad_sum_kernel, else wgrad_reduce_kernel
+    bool direct;                   // tiles land directly in dw: native order, one split, no accumulation
+    bool bias_direct;              // the kernel writes dbias itself: one split, no accumulation
+    int64_t slab_floats, bias_floats;   // workspace layout: [splits][Cout][Q] partial slabs, then [splits][Cout] bias partials
+    int64_t ws_bytes() const { return (slab_floats + bias_floats) * (int64_t)sizeof(float); }
+    bool bias_pending(const psg_wgrad_desc* d) const { return d->dbias && !bias_direct; }
+    bool bias_own_kernel(const psg_wgrad_desc* d) const { return bias_pending(d) && (direct || !native); }   // else folded into wgrad_sum_kernel
+};
+static int ceil_div(int64_t a, int b) { return (int)((a + b - 1) / b); }
+static int wgrad_geom(const psg_wgrad_desc* d) { return d->stride != 1 || d->Hi != d->Ho || d->Wi != d->Wo ? 0 : (d->ksize == 1 ? 2 : 1); }
+// what a family's kernels need (holds for a pinned family too)
+static bool wgrad_fits(const psg_wgrad_desc* d, int family, int M, int Q) {
+    if (family == WG_NARROW128) return true;
+    if (d->dtype != PSG_BF16 || wgrad_geom(d) == 0) return false;            // bf16, stride-1 same-size geometries
+    if (family == WG_NARROW160) return d->Cout % 160 == 0;
+    if (family == WG_WIDE) return true;
+    // pipe: no column tail, rows >= M read as zeros beyond the descriptor's extent, ten q tiles share out the bias fragments
+    return d->Cout % 320 == 0 && ((int64_t)M + 64) * d->lddy * 2 < 0x7FFFFFF0ll && (!d->dbias || ceil_div(Q, 192) >= 10);
+}
+// where a family pays (the plan's own choice only; a pin skips this)
+static bool wgrad_pays(const psg_wgrad_desc* d, int family, int Q) {
+    const WgSettings& s = wg_settings();
+    if (!s.family_on[family]) return false;
+    // 160-row tiles where they tile Cout exactly and 128 does not (Cout = 320: 2 tiles instead of 2.5 -> 3)
+    if (family == WG_NARROW160) return d->Cout % 128 != 0;
+    if (family == WG_WIDE) {
+        // wide (128 x 256) tiles where the 256-column grid wastes < 5 % of the q axis and the narrow grid has >= 200 tiles: below that the
+        // wide grid leaves the chip to split-K alone (7x7 1280->1280 1x1: 100 narrow tiles, 53 -> 61 us wide; 1280->2560: 200 tiles, 99 -> 90 us)
+        const int64_t q256 = ((int64_t)Q + 255) / 256 * 256;
+        const int64_t tiles128 = (int64_t)((d->Cout + 127) / 128) * ((Q + 127) / 128);
+        return q256 * 100 <= (int64_t)Q * 105 && tiles128 >= 200;
     }
-    {
-        // wide (128 x 256) tiles where the 256-column grid wastes < 5 % of the q axis (PSG_WGRAD_WIDE=0: off, A/B runs)
-        static int off = -1;
-        if (off < 0) { const char* e = getenv("PSG_WGRAD_WIDE"); off = (e && atoi(e) == 0) ? 1 : 0; }
-        const bool same = d->stride == 1 && d->Hi == d->Ho && d->Wi == d->Wo;
-        const int64_t q256 = ((int64_t)p.Q + 255) / 256 * 256;
-        // ... and only where the narrow grid has >= 200 tiles: below that the wide grid leaves the chip to split-K alone (7x7 1280->1280 1x1: 100 narrow tiles, 53 -> 61 us wide; 1280->2560: 200 tiles, 99 -> 90 us)
-        const int64_t tiles128 = (int64_t)((d->Cout + 127) / 128) * ((p.Q + 127) / 128);
-        if (!off && d->dtype == PSG_BF16 && same && p.BR == 128 && q256 * 100 <= (int64_t)p.Q * 105 && tiles128 >= 200) { p.wide = 1; BKP = 32; }
-    }
-    // (a weight gradient's tile count is small and its split count is chosen to fill the chip in ONE or two rounds: it always
-    //  plans around the reserve)
-    int kSlots = 2 * avail_cus();
-    {
-        // pipelined 320 x 192 tiles (one 256-thread workgroup per CU, wgrad_pipe_kernel): 320 divides Cout, the 192-column grid
-        // wastes < 4 %, enough tiles, >= 10 q tiles (they share out the bias gradient's fragments) (PSG_WGRAD_PIPE=0: off)
-        static int off = -1;
-        if (off < 0) { const char* e = getenv("PSG_WGRAD_PIPE"); off = (e && atoi(e) == 0) ? 1 : 0; }
-        static int mint = -1;
-        if (mint < 0) { const char* e = getenv("PSG_WGRAD_PIPE_MIN_TILES"); mint = e ? atoi(e) : 15; }
-        const bool same = d->stride == 1 && d->Hi == d->Ho && d->Wi == d->Wo;
-        const int64_t q192 = ((int64_t)p.Q + 191) / 192 * 192;
+    if (family == WG_PIPE) {
+        // pipelined 320 x 192 tiles: the 192-column grid wastes < 4 %, enough tiles, >= 10 q tiles (bias or not)
+        const int64_t q192 = ((int64_t)Q + 191) / 192 * 192;
         const int64_t tiles320 = (int64_t)(d->Cout / 320) * (q192 / 192);
-        const int64_t ext = ((int64_t)p.M + 64) * d->lddy * 2;
-        if (!off && d->dtype == PSG_BF16 && same && d->Cout % 320 == 0 && q192 * 100 <= (int64_t)p.Q * 104 && tiles320 >= mint && q192 / 192 >= 10 &&
-            ext < 0x7FFFFFF0ll) { p.wide = 3; p.BR = 320; BKP = 32; kSlots = avail_cus(); }
+        return q192 * 100 <= (int64_t)Q * 104 && tiles320 >= s.pipe_min_tiles && q192 / 192 >= 10;
     }
-    p.rtiles = (d->Cout + p.BR - 1) / p.BR;
-    p.qtiles = p.wide == 3 ? (p.Q + 191) / 192 : (p.wide ? (p.Q + 255) / 256 : (p.Q + 127) / 128);
-    const int total_steps = (p.M + BKP - 1) / BKP;
-    const int tiles = p.rtiles * p.qtiles;
-    // Split-K choice by a makespan model: 2 workgroups (64 KB LDS each) per CU x 256 CUs = 512 slots; a launch runs
-    // in ceil(blocks/512) rounds of (steps_per_split + fixed prologue/epilogue) K steps, and every extra split adds
-    // one slab of traffic to the deterministic sum pass.  Picking the split count that merely "fills the chip"
-    // leaves e.g. 1035 blocks = 2.02 rounds (a third of the time on 11 stragglers); this picks 966 or 483 instead.
-    const double step_us = (d->dtype == PSG_BF16 ? 1.05 : 8.0) * (p.BR == 160 ? 1.25 : 1.0), fixed_steps = 6.0;
-    const double slab_us = (double)d->Cout * p.Q * 4.0 / 4.0e6;          // one fp32 slab through HBM at ~4 TB/s
-    const bool native = d->dw_layout == PSG_W_OHWI || p.taps == 1;
+    return true;
+}
+// pipe before wide before the 160-row tiles; the wide tiles only where the 160-row tiles do not apply
+static int wgrad_choose_family(const psg_wgrad_desc* d, int M, int Q) {
+    for (int f : {WG_PIPE, WG_NARROW160, WG_WIDE})
+        if (wgrad_fits(d, f, M, Q) && wgrad_pays(d, f, Q)) return f;
+    return WG_NARROW128;
+}
+// Split-K choice by a makespan model: 2 workgroups (64 KB LDS each) per CU x 256 CUs = 512 slots; a launch runs
+// in ceil(blocks/512) rounds of (steps_per_split + fixed prologue/epilogue) K steps, and every extra split adds
+// one slab of traffic to the deterministic sum pass.  Picking the split count that merely "fills the chip"
+// leaves e.g. 1035 blocks = 2.02 rounds (a third of the time on 11 stragglers); this picks 966 or 483 instead.
+// (a weight gradient's tile count is small and its split count is chosen to fill the chip in ONE or two rounds: it always
+//  plans around the reserve)
+static int wgrad_steps_per_split(const psg_wgrad_desc* d, const WgVariant& v, int tiles, int total_steps, int Q, bool native) {
+    const int kSlots = v.wg_per_cu * avail_cus();
+    const double step_us = (d->dtype == PSG_BF16 ? 1.05 : 8.0) * (v.family == WG_NARROW160 ? 1.25 : 1.0), fixed_steps = 6.0;
+    const double slab_us = (double)d->Cout * Q * 4.0 / 4.0e6;          // one fp32 slab through HBM at ~4 TB/s
     int max_splits = (total_steps + 7) / 8;                               // at least 8 K steps per split
     if (max_splits > 256) max_splits = 256;
     if (max_splits < 1) max_splits = 1;
@@ -1033,38 +1039,47 @@ static void wgrad_plan(const psg_wgrad_desc* d, WgP& p) {
         const double cost = rounds * (sps + fixed_steps) * step_us + (direct ? 0.0 : (sp + 1.0) * slab_us + 3.0);
         if (cost < best - 1e-9) { best = cost; best_sps = sps; }
     }
-    {
-        static int force = -2;                             // PSG_WGRAD_SPLITS=n pins the split count (kernel experiments)
-        if (force == -2) { const char* e = getenv("PSG_WGRAD_SPLITS"); force = e ? atoi(e) : -1; }
-        if (force > 0) best_sps = (total_steps + force - 1) / force;
-    }
-    p.steps_per_split = best_sps;
-    p.splits = (total_steps + p.steps_per_split - 1) / p.steps_per_split;
-}
-// dynamic LDS of each kernel variant: wgrad_kernel<T, GEOM, BR> double-buffers a [BKP x BR] dY tile and a [BKP x ROWB] X tile;
-// the wide kernel two 8 KB dY + 16 KB X stages; the pipe kernel four 32 KB stages + 1 KB
-template <typename T> constexpr int wgrad_lds(int BR) { return 2 * WgCfg<T>::BKP * (BR * (int)sizeof(T) + WgCfg<T>::ROWB); }
-constexpr int WG_WIDE_LDS = 2 * (8192 + 16384);
-constexpr int WG_PIPE_LDS = 4 * 32768 + 1024;
-
-// tiles land directly in dw: native order, one split, no accumulation
-static bool wgrad_direct(const psg_wgrad_desc* d, const WgP& p) {
-    return (d->dw_layout == PSG_W_OHWI || p.taps == 1) && p.splits == 1 && !d->accumulate;
+    return best_sps;
 }
 
+// d has passed wgrad_check.  PSG_ERR_ARG: the pinned family cannot run this launch.
+static int wgrad_plan(const psg_wgrad_desc* d, WgPlan& pl) {
+    const WgSettings& s = wg_settings();
+    pl.M = d->B * d->Ho * d->Wo;
+    pl.taps = d->ksize * d->ksize;
+    pl.Q = pl.taps * d->Cin;
+    const bool pinned = s.variant >= 0;
+    const int family = pinned ? s.variant : wgrad_choose_family(d, pl.M, pl.Q);
+    pl.v = wgrad_fits(d, family, pl.M, pl.Q) ? wgrad_variant(family, d->dtype, wgrad_geom(d), d->dbias != nullptr) : nullptr;
+    PSG_REQUIRE(pl.v, PSG_ERR_ARG, "wgrad: the pinned kernel family %d cannot run this launch", family);
+    const WgVariant& v = *pl.v;
+    pl.rtiles = ceil_div(d->Cout, v.BR);
+    pl.qtiles = ceil_div(pl.Q, v.BQ);
+    const int total_steps = ceil_div(pl.M, v.BKP);
+    pl.native = d->dw_layout == PSG_W_OHWI || pl.taps == 1;
+    pl.steps_per_split = s.splits > 0 ? ceil_div(total_steps, s.splits)
+                                      : wgrad_steps_per_split(d, v, pl.rtiles * pl.qtiles, total_steps, pl.Q, pl.native);
+    pl.splits = ceil_div(total_steps, pl.steps_per_split);
+    pl.grid = pl.rtiles * pl.qtiles * pl.splits;
+    pl.direct = pl.native && pl.splits == 1 && !d->accumulate;
+    pl.bias_direct = d->dbias && pl.splits == 1 && !d->accumulate_bias;
+    pl.slab_floats = pl.direct ? 0 : (int64_t)pl.splits * d->Cout * pl.Q;
+    pl.bias_floats = pl.bias_pending(d) ? (int64_t)pl.splits * d->Cout : 0;
+    return PSG_OK;
+}
 }  // namespace psg
 using namespace psg;
 
 extern "C" {
 
 int psg_wgrad_init_attrs(void) {
-    int rc = set_max_lds(wgrad_lds<bf16_t>(128), wgrad_kernel<bf16_t, 0>, wgrad_kernel<bf16_t, 1>, wgrad_kernel<bf16_t, 2>);
-    if (!rc) rc = set_max_lds(wgrad_lds<float>(128), wgrad_kernel<float, 0>, wgrad_kernel<float, 1>, wgrad_kernel<float, 2>);
-    if (!rc) rc = set_max_lds(wgrad_lds<bf16_t>(160), wgrad_kernel<bf16_t, 1, 160>, wgrad_kernel<bf16_t, 2, 160>);
-    if (!rc) rc = set_max_lds(WG_PIPE_LDS, wgrad_pipe_kernel<1, false>, wgrad_pipe_kernel<2, false>, wgrad_pipe_kernel<1, true>, wgrad_pipe_kernel<2, true>);
-    if (!rc) rc = set_max_lds(WG_WIDE_LDS, wgrad_wide_kernel<1>, wgrad_wide_kernel<2>);
-    return rc;
+    for (const WgVariant& v : WG_VARIANTS)
+        if (int rc = set_max_lds(v.lds, v.kernel)) return rc;
+    return PSG_OK;
 }
+
+int psg_conv_wgrad_set_variant(int v) { wg_settings().variant = (v >= 0 && v < WG_FAMILIES) ? v : -1; return PSG_OK; }
+int psg_conv_wgrad_set_splits(int n) { wg_settings().splits = n > 0 ? n : 0; return PSG_OK; }
 
 static int wgrad_check(const psg_wgrad_desc* d) {
     PSG_REQUIRE(d, PSG_ERR_ARG, "wgrad: null descriptor");
@@ -1082,12 +1097,26 @@ static int wgrad_check(const psg_wgrad_desc* d) {
 }
 
 int64_t psg_conv_wgrad_workspace_bytes(const psg_wgrad_desc* d) {
-    if (wgrad_check(d) != PSG_OK) return -1;
-    WgP p;
-    wgrad_plan(d, p);
-    const int64_t slabs = wgrad_direct(d, p) ? 0 : (int64_t)p.splits * d->Cout * p.Q;
-    const int64_t bias = (d->dbias && !(p.splits == 1 && !d->accumulate_bias)) ? (int64_t)p.splits * d->Cout : 0;
-    return (slabs + bias) * (int64_t)sizeof(float);
+    WgPlan pl;
+    if (wgrad_check(d) != PSG_OK || wgrad_plan(d, pl) != PSG_OK) return -1;
+    return pl.ws_bytes();
+}
+
+int psg_conv_wgrad_route(const psg_wgrad_desc* d, int32_t* out) {
+    PSG_REQUIRE(out, PSG_ERR_ARG, "wgrad_route: null pointer");
+    for (int f = 0; f < PSG_WGRAD_ROUTE_FIELDS; ++f) out[f] = 0;
+    int rc = wgrad_check(d);
+    if (rc) return rc;
+    WgPlan pl;
+    if ((rc = wgrad_plan(d, pl))) return rc;
+    const WgVariant& v = *pl.v;
+    const int own = pl.bias_own_kernel(d);
+    const int32_t r[PSG_WGRAD_ROUTE_FIELDS] = {
+        v.family, v.dtype, v.geom, d->dbias ? 1 : 0, v.BR, v.BQ, v.BKP, v.lds, v.wg_per_cu,
+        pl.rtiles, pl.qtiles, pl.splits, pl.steps_per_split, pl.grid,
+        pl.direct ? 0 : (pl.native ? 1 : 2), !d->dbias ? 0 : (pl.bias_direct ? 1 : (own ? 3 : 2)), 1 + own + (pl.direct ? 0 : 1)};
+    for (int f = 0; f < PSG_WGRAD_ROUTE_FIELDS; ++f) out[f] = r[f];
+    return PSG_OK;
 }
 
 int psg_conv_wgrad(const psg_wgrad_desc* d, psg_stream_t stream) {
@@ -1095,80 +1124,50 @@ int psg_conv_wgrad(const psg_wgrad_desc* d, psg_stream_t stream) {
     if (rc) return rc;
     PSG_REQUIRE(d->x && d->dy && d->dw, PSG_ERR_ARG, "wgrad: null pointer");
     PSG_REQUIRE(aligned16(d->x) && aligned16(d->dy) && aligned16(d->dw), PSG_ERR_ALIGN, "wgrad: x/dy/dw must be 16-byte aligned");
-    WgP p;
-    wgrad_plan(d, p);
-    const bool direct = wgrad_direct(d, p);
-    const bool native = d->dw_layout == PSG_W_OHWI || p.taps == 1;
-    const bool bias_direct = d->dbias && p.splits == 1 && !d->accumulate_bias;
-    const int64_t slab_floats = direct ? 0 : (int64_t)p.splits * d->Cout * p.Q;
-    const int64_t bias_floats = (d->dbias && !bias_direct) ? (int64_t)p.splits * d->Cout : 0;
-    if (slab_floats + bias_floats > 0) {
+    WgPlan pl;
+    if ((rc = wgrad_plan(d, pl))) return rc;
+    if (pl.ws_bytes() > 0) {
         PSG_REQUIRE(d->ws && aligned16(d->ws), PSG_ERR_ARG, "wgrad: workspace missing or not 16-byte aligned");
-        PSG_REQUIRE(d->ws_bytes >= (slab_floats + bias_floats) * (int64_t)sizeof(float), PSG_ERR_WORKSPACE, "wgrad: workspace too small");
+        PSG_REQUIRE(d->ws_bytes >= pl.ws_bytes(), PSG_ERR_WORKSPACE, "wgrad: workspace too small");
     }
-    p.x = d->x; p.dy = d->dy; p.ws = direct ? d->dw : (float*)d->ws; p.ldx = d->ldx; p.lddy = d->lddy;
+    WgP p;
+    p.x = d->x; p.dy = d->dy; p.ws = pl.direct ? d->dw : (float*)d->ws; p.ldx = d->ldx; p.lddy = d->lddy;
     p.scale = d->scale == 0.f ? 1.0f : d->scale;
-    p.bws = !d->dbias ? nullptr : (bias_direct ? d->dbias : (float*)d->ws + slab_floats);
+    p.bws = !d->dbias ? nullptr : (pl.bias_direct ? d->dbias : (float*)d->ws + pl.slab_floats);
     p.B = d->B; p.Hi = d->Hi; p.Wi = d->Wi; p.Cin = d->Cin; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;
     p.ks = d->ksize; p.stride = d->stride; p.pad = d->pad;
-    p.inv_HoWo = 1.0f / (float)(d->Ho * d->Wo); p.inv_Wo = 1.0f / (float)d->Wo;
+    p.M = pl.M; p.Q = pl.Q; p.taps = pl.taps;
+    p.rtiles = pl.rtiles; p.qtiles = pl.qtiles; p.splits = pl.splits; p.steps_per_split = pl.steps_per_split;
     {
         const int64_t esz = d->dtype == PSG_BF16 ? 2 : 4;
         const int64_t xb = (((int64_t)d->B * d->Hi * d->Wi - 1) * d->ldx + d->Cin) * esz
                            + (int64_t)(d->pad * d->Wi + d->pad) * d->ldx * esz;      // (+ the shifted-base slack of GEOM 1/2)
-        const int64_t yb = (((int64_t)p.M - 1) * d->lddy + d->Cout) * esz;
+        const int64_t yb = (((int64_t)pl.M - 1) * d->lddy + d->Cout) * esz;
         PSG_REQUIRE(xb < 0x7FFFFFF0ll && yb < 0x7FFFFFF0ll, PSG_ERR_SHAPE, "wgrad: operand extent >= 2 GiB");
         p.x_bytes = (uint32_t)(xb - (int64_t)(d->pad * d->Wi + d->pad) * d->ldx * esz); p.dy_bytes = (uint32_t)yb;
     }
-    const int grid = p.rtiles * p.qtiles * p.splits;
     hipStream_t s = (hipStream_t)stream;
     {
-        static int dbg = -1;                               // PSG_WGRAD_DEBUG=1: print the plan of every launch
-        if (dbg < 0) { const char* e = getenv("PSG_WGRAD_DEBUG"); dbg = e ? atoi(e) : 0; }
-        if (dbg) fprintf(stderr, "psg wgrad: M=%d Cout=%d Q=%d wide=%d BR=%d tiles=%dx%d splits=%d steps/split=%d grid=%d direct=%d\n", p.M, d->Cout,
-                         p.Q, p.wide, p.BR, p.rtiles, p.qtiles, p.splits, p.steps_per_split, grid, (int)direct);
-    }
-    {
         const double esz = d->dtype == PSG_BF16 ? 2.0 : 4.0;
-        ProfScope prof(PROF_WGRAD, 2.0 * (double)p.M * (double)p.Cout * (double)p.Q, s,
-                       ((double)d->B * d->Hi * d->Wi * d->Cin + (double)p.M * d->Cout) * esz + (double)d->Cout * p.Q * 4.0);
-        const int geom = d->stride != 1 || d->Hi != d->Ho || d->Wi != d->Wo ? 0 : (d->ksize == 1 ? 2 : 1);
-#define PSG_WG_LAUNCH(G)                                                                                               \
-        if (d->dtype == PSG_BF16) hipLaunchKernelGGL((wgrad_kernel<bf16_t, G>), dim3(grid), dim3(256), wgrad_lds<bf16_t>(128), s, p); \
-        else hipLaunchKernelGGL((wgrad_kernel<float, G>), dim3(grid), dim3(256), wgrad_lds<float>(128), s, p);
-        if (p.wide == 3) {
-            if (p.bws) {
-                if (geom == 1) hipLaunchKernelGGL((wgrad_pipe_kernel<1, true>), dim3(grid), dim3(256), WG_PIPE_LDS, s, p);
-                else hipLaunchKernelGGL((wgrad_pipe_kernel<2, true>), dim3(grid), dim3(256), WG_PIPE_LDS, s, p);
-            } else {
-                if (geom == 1) hipLaunchKernelGGL((wgrad_pipe_kernel<1, false>), dim3(grid), dim3(256), WG_PIPE_LDS, s, p);
-                else hipLaunchKernelGGL((wgrad_pipe_kernel<2, false>), dim3(grid), dim3(256), WG_PIPE_LDS, s, p);
-            }
-        } else if (p.wide) {
-            if (geom == 1) hipLaunchKernelGGL((wgrad_wide_kernel<1>), dim3(grid), dim3(256), WG_WIDE_LDS, s, p);
-            else hipLaunchKernelGGL((wgrad_wide_kernel<2>), dim3(grid), dim3(256), WG_WIDE_LDS, s, p);
-        } else if (p.BR == 160) {
-            if (geom == 1) hipLaunchKernelGGL((wgrad_kernel<bf16_t, 1, 160>), dim3(grid), dim3(256), wgrad_lds<bf16_t>(160), s, p);
-            else hipLaunchKernelGGL((wgrad_kernel<bf16_t, 2, 160>), dim3(grid), dim3(256), wgrad_lds<bf16_t>(160), s, p);
-        } else if (geom == 0) { PSG_WG_LAUNCH(0) } else if (geom == 1) { PSG_WG_LAUNCH(1) } else { PSG_WG_LAUNCH(2) }
-#undef PSG_WG_LAUNCH
+        ProfScope prof(PROF_WGRAD, 2.0 * (double)pl.M * (double)p.Cout * (double)pl.Q, s,
+                       ((double)d->B * d->Hi * d->Wi * d->Cin + (double)pl.M * d->Cout) * esz + (double)d->Cout * pl.Q * 4.0);
+        hipLaunchKernelGGL(pl.v->kernel, dim3(pl.grid), dim3(256), pl.v->lds, s, p);
     }
     PSG_LAUNCH_CHECK("wgrad");
-    const bool bias_pending = d->dbias && !bias_direct;
-    if (bias_pending && (direct || !native)) {
-        hipLaunchKernelGGL(wgrad_bias_sum_kernel, dim3((d->Cout + 255) / 256), dim3(256), 0, s, p.bws, d->dbias, d->Cout, p.splits, d->accumulate_bias);
+    if (pl.bias_own_kernel(d)) {
+        hipLaunchKernelGGL(wgrad_bias_sum_kernel, dim3((d->Cout + 255) / 256), dim3(256), 0, s, p.bws, d->dbias, d->Cout, pl.splits, d->accumulate_bias);
         PSG_LAUNCH_CHECK("wgrad_bias_sum");
     }
-    if (direct) return PSG_OK;
-    if (native) {                                  // Cout*Q is a multiple of 16 (Cin, Cout multiples of 4)
-        const int64_t n4 = (int64_t)d->Cout * p.Q / 4;
+    if (pl.direct) return PSG_OK;
+    if (pl.native) {                               // Cout*Q is a multiple of 16 (Cin, Cout multiples of 4)
+        const int64_t n4 = (int64_t)d->Cout * pl.Q / 4;
         int g = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
         if (g < (d->Cout + 255) / 256) g = (d->Cout + 255) / 256;       // enough workgroups to cover the bias channels
-        hipLaunchKernelGGL(wgrad_sum_kernel, dim3(g), dim3(256), 0, s, (const float*)d->ws, d->dw, n4, p.splits, d->accumulate,
-                           bias_pending ? p.bws : nullptr, d->dbias, d->Cout, d->accumulate_bias);
+        hipLaunchKernelGGL(wgrad_sum_kernel, dim3(g), dim3(256), 0, s, (const float*)d->ws, d->dw, n4, pl.splits, d->accumulate,
+                           pl.bias_pending(d) ? p.bws : nullptr, d->dbias, d->Cout, d->accumulate_bias);
     } else {
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(d->Cout, (d->Cin + 255) / 256), dim3(256), 0, s, (const float*)d->ws, d->dw,
-                           d->Cout, d->Cin, p.taps, p.splits, d->accumulate);
+                           d->Cout, d->Cin, pl.taps, pl.splits, d->accumulate);
     }
     PSG_LAUNCH_CHECK("wgrad_reduce");
     return PSG_OK;

@@ -287,6 +287,8 @@ def test_conv3x3_large_tiles(psg, B, H, Cin, Cout):
     ref.backward(gy)
     xd = to_cl(x.detach(), dtype).to(DEV).requires_grad_(True)
     for layout in ("oihw", "ohwi"):                 # torch-contiguous weights, and the parameter arena's channels_last order
+        if Cout == 320:
+            assert _wgrad_family(B, H, Cin, Cout, 3, layout=layout) == "narrow160"
         wd = w.detach().to(DEV)
         if layout == "ohwi":
             wd = wd.contiguous(memory_format=torch.channels_last)
@@ -873,8 +875,20 @@ def test_conv_epilogue_kinds_bitwise(psg, M, K, N):
         assert torch.isfinite(ya.float()).all()
 
 
-# (B, H, Cin, Cout, ks): shapes whose (tap, ci) axis tiles by 256 columns with < 5 % waste, so the weight gradient takes the
-# wide 128 x 256 tile (32-pixel K steps): exact tiling, a q tail (Cin 248: 2232 of 2304 columns), a Cout tail (192 = 1.5
+def _wgrad_family(B, H, Cin, Cout, ks, dbias=True, layout="ohwi", accumulate=False, ldx=0):
+    """The kernel family psg_conv_wgrad would run for a bf16 stride-1 conv's weight gradient as ops.conv2d launches it
+    (psg_conv_wgrad_route, host only, under the current pins): "narrow128", "narrow160", "wide" or "pipe"."""
+    from pokemon_sprite_generator_amd import _lib
+    from tests import wgrad_cases as W
+    c = W._mk("probe", B=B, H=H, Cin=Cin, Cout=Cout, ks=ks, dbias=dbias, layout=layout if ks == 3 else "oihw", acc=accumulate, ldx=ldx)
+    rc, r = W.route_of(_lib.init(0), W.make_desc(c, "bf16"))
+    assert rc == 0, _lib.load().psg_last_error()
+    return W.FAMILIES[r[0]]
+
+
+# (B, H, Cin, Cout, ks): shapes whose (tap, ci) axis tiles by 256 columns with < 5 % waste - written for the wide 128 x 256 tile
+# (32-pixel K steps).  The plan itself takes that kernel only where the narrow grid has >= 200 tiles (of these: 1280 -> 3840), so
+# the others run with the family pinned to it (psg_conv_wgrad_set_variant): exact tiling, a q tail (Cin 248: 2232 of 2304 columns), a Cout tail (192 = 1.5
 # row tiles), pixel counts that are not multiples of 32, the three map widths with borders, pointwise layers, batch large
 # enough for several splits, and a row stride wider than Cin (a concat slice)
 WIDE_CASES = [(3, 14, 256, 128, 3), (5, 7, 248, 192, 3), (2, 27, 256, 128, 3), (37, 4, 512, 256, 3), (3, 9, 1280, 128, 1),
@@ -886,6 +900,24 @@ WIDE_CASES = [(3, 14, 256, 128, 3), (5, 7, 248, 192, 3), (2, 27, 256, 128, 3), (
 @pytest.mark.parametrize("layout", ["oihw", "ohwi"])
 @pytest.mark.parametrize("B,H,Cin,Cout,ks", WIDE_CASES)
 def test_wgrad_wide_tiles(psg, B, H, Cin, Cout, ks, layout):
+    from pokemon_sprite_generator_amd import ops, _lib
+    lib = _lib.init(0)
+    planned = _wgrad_family(B, H, Cin, Cout, ks, layout=layout, ldx=64)
+    if Cout == 320:
+        assert planned == "narrow160"
+    else:
+        assert planned == ("wide" if (Cin, Cout) == (1280, 3840) else "narrow128")
+        lib.psg_conv_wgrad_set_variant(2)
+    try:
+        if Cout != 320:
+            for acc in (False, True):
+                assert _wgrad_family(B, H, Cin, Cout, ks, layout=layout, accumulate=acc, ldx=64) == "wide"
+        _wgrad_wide_tiles(B, H, Cin, Cout, ks, layout)
+    finally:
+        lib.psg_conv_wgrad_set_variant(-1)
+
+
+def _wgrad_wide_tiles(B, H, Cin, Cout, ks, layout):
     from pokemon_sprite_generator_amd import ops
     dtype = torch.bfloat16
     pad = 1 if ks == 3 else 0
@@ -969,8 +1001,8 @@ def test_conv_splitk_matches_unsplit(psg, dtype, B, H, Cin, Cout, ks, stride):
         assert maxrel(outs[True][i], outs[False][i]) < (2e-5 if dtype == torch.float32 else 1.6e-2), what + " split vs unsplit"
 
 
-# (B, H, Cin, Cout, ks): Cout % 320 == 0, the (tap, ci) axis a multiple of 192, >= 40 tiles of 320 x 192 and NO bias gradient in
-# the launch: the software-pipelined one-wave-per-SIMD kernel (ring of four stages).  Pixel counts chosen to give 1, 2, 3, 4, 5,
+# (B, H, Cin, Cout, ks): Cout % 320 == 0, the 192-column grid wastes < 4 % of the (tap, ci) axis, >= 15 tiles of 320 x 192 in >= 10
+# columns, with and without a bias gradient in the launch: the software-pipelined one-wave-per-SIMD kernel (ring of four stages).  Pixel counts chosen to give 1, 2, 3, 4, 5,
 # 7 and many K steps (prologue / steady state / tail paths), M not a multiple of 32, borders at every map width, 1x1 layers.
 PIPE_CASES = [(2, 4, 1280, 640, 3), (4, 4, 1280, 640, 3), (6, 4, 1024, 320, 3), (2, 7, 1280, 640, 3), (3, 7, 1024, 320, 3), (1, 14, 1280, 640, 3),
               (5, 14, 1024, 320, 3), (2, 27, 1024, 320, 3), (3, 9, 1920, 1280, 1), (33, 7, 1280, 640, 3),
@@ -992,6 +1024,7 @@ def test_wgrad_pipe_tiles(psg, B, H, Cin, Cout, ks, with_bias):
     ref.backward(gy)
     xd = to_cl(x, dtype).to(DEV)
     for layout in ("oihw", "ohwi"):
+        assert _wgrad_family(B, H, Cin, Cout, ks, dbias=with_bias, layout=layout) == "pipe"
         wd = w.detach().to(DEV)
         if layout == "ohwi" and ks == 3:
             wd = wd.contiguous(memory_format=torch.channels_last)

@@ -22,7 +22,7 @@ sys.path.insert(0, os.getcwd())
 # The two lists below are kept by hand next to `_lib.SIGNATURES` and must follow it: an entry added there whose last pointer is
 # not a stream, or that takes a workspace byte count, has to be named here or its line is tagged wrongly (for both trees alike).
 NO_STREAM = {"psg_set_seed_source", "psg_attn_path_counts", "psg_profile_end", "psg_profile_bytes", "psg_stream_create_cu_mask",
-             "psg_stream_destroy", "psg_attn_route", "psg_groupnorm_route", "psg_conv_route"}
+             "psg_stream_destroy", "psg_attn_route", "psg_groupnorm_route", "psg_conv_route", "psg_conv_wgrad_route"}
 # entries whose second-to-last argument is the byte count of the workspace before it
 WS_BYTES = {"psg_colsum", "psg_attn_bwd_longq", "psg_feat_l1", "psg_kl_f32", "psg_layernorm_bwd", "psg_bert_embed_ln_bwd", "psg_embed_scatter"}
 
