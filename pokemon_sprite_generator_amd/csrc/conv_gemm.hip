@@ -5,106 +5,115 @@
 #include <cstring>
 #include <mutex>
 #include <queue>
-#include <type_traits>
 #include <vector>
 
 namespace psg {
 
-// the (dtype, BM, BN) tiles of conv_gemm_kernel: each is instantiated in a conv_tile_<dtype>_<BM>_<BN>.o (Makefile TILES)
-#define PSG_CONV_TILES(X)                                                      \
-    X(float, 128, 128) X(float, 128, 64) X(float, 64, 64)                      \
-    X(bf16_t, 128, 128) X(bf16_t, 128, 64) X(bf16_t, 64, 64) X(bf16_t, 128, 160) X(bf16_t, 64, 160)
+// One row per (dtype, BM, BN) tile of conv_gemm_kernel; each is instantiated in its own conv_tile_<dtype>_<BM>_<BN>.o, which
+// exports the tile's kernels (conv_kernels: null where a (mode, split, class) combination is not built).  The plan's scoring
+// and split-K estimate, psg_conv_init_attrs, the range of the tile pin and the launch read these rows and nothing else: fp32
+// and parity-class launches have no 160-wide tile because there is no such row / kernel.  (The Makefile's TILES is the
+// build's list of the same tiles: a row without its object is an undefined symbol when the library is loaded.)
+struct ConvTile {
+    int dtype, BM, BN;
+    int cand;                      // the candidate number PSG_CONV_TILE / psg_conv_set_tile pins
+    double eff;                    // measured relative MFMA efficiency of the tile shape
+    // (a K <= 640 boost for 128x64 - three resident workgroups hiding the short loop ends - paid before the epilogue was
+    //  specialised per kind; since then 128x128 wins those layers by 10 %: gemm_direct.py)
+    const ConvKernels& (*kernels)();
+};
+#define PSG_TILE(D, T, BM, BN, CAND, EFF) {D, BM, BN, CAND, EFF, conv_kernels<T, BM, BN>}
+static const ConvTile CONV_TILES[] = {
+    PSG_TILE(PSG_BF16, bf16_t, 128, 128, 0, 1.0), PSG_TILE(PSG_BF16, bf16_t, 128, 64, 1, 0.78), PSG_TILE(PSG_BF16, bf16_t, 64, 64, 2, 0.55),
+    PSG_TILE(PSG_BF16, bf16_t, 128, 160, 3, 1.0), PSG_TILE(PSG_BF16, bf16_t, 64, 160, 4, 0.70),  // 160 = 2 x 5 x 16: only the 16x16x32 bf16 tiles divide it
+    PSG_TILE(PSG_F32, float, 128, 128, 0, 1.0),   PSG_TILE(PSG_F32, float, 128, 64, 1, 0.78),   PSG_TILE(PSG_F32, float, 64, 64, 2, 0.55),
+};
+#undef PSG_TILE
 
-#define X(T, BM, BN)                                                          \
-    extern template int launch_conv<T, BM, BN>(const ConvP&, hipStream_t);    \
-    extern template int set_conv_attrs<T, BM, BN>();
-PSG_CONV_TILES(X)
-#undef X
+// Settings: the environment, read once (PSG_CONV_TILE = candidate pins the tile; PSG_CONV_SPLITK / PSG_CONV_PW / PSG_EPI_LDS /
+// PSG_EPI_KINDS = 0 turn split-K, the persistent pointwise kernel, the LDS-staged stores and the per-kind epilogues off;
+// PSG_CONV_TAPCLASS = 0 / 1 / 2), and the pins of psg_conv_set_tile / _set_tapclass / _set_pw (kernel A/B runs, tests).
+struct ConvSettings {
+    int tile;                      // pinned candidate, -1: the plan's choice.  A pinned launch is never split
+    bool splitk;
+    int tapcls;                    // border-class form: 0 off, 1 where tapcls_pays says so, 2 on every launch it applies to
+    bool pw, epi_lds, epi_kinds;
+};
+static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+static int tile_pin(int c) { for (const ConvTile& t : CONV_TILES) if (t.cand == c) return c; return -1; }
+static int tapcls_pin(int v) { return v < 0 ? 0 : (v > 2 ? 2 : v); }
+static ConvSettings& conv_settings() {
+    static ConvSettings s = {tile_pin(env_int("PSG_CONV_TILE", -1)), env_int("PSG_CONV_SPLITK", 1) != 0, tapcls_pin(env_int("PSG_CONV_TAPCLASS", 1)),
+                             env_int("PSG_CONV_PW", 1) != 0, env_int("PSG_EPI_LDS", 1) != 0, env_int("PSG_EPI_KINDS", 1) != 0};
+    return s;
+}
+static int64_t g_tapcls_launches = 0, g_pw_launches = 0;
 
-
-// persistent pointwise kernel (conv_pw.hip)
-bool conv_pw_applicable(const ConvP& p, int dtype);
-void conv_pw_grid(const ConvP& p, int& mtiles, int& ntiles, int& grid);
-int launch_conv_pw(const ConvP& p, hipStream_t stream);
-int conv_pw_set_attrs();
+// gather mode of a launch (MODE of conv_gemm_kernel)
+static int conv_mode(const ConvP& p) { return p.ntap > 0 ? 3 : (!p.fast ? 2 : (!p.transposed ? 0 : (p.stride == 1 ? 1 : 2))); }
+static int64_t conv_ws_bytes(const ConvP& p, int splits) { return splits > 1 ? (int64_t)splits * p.M * p.N * 4 : 0; }
+static double conv_tile_count(const ConvP& p, const ConvTile& t) { return (double)(((int64_t)p.M + t.BM - 1) / t.BM) * (double)((p.N + t.BN - 1) / t.BN); }
 
 // tile choice: maximise (useful fraction of the tile grid) x (chip fill of the last wave) x (tile efficiency); then, for
 // grids that leave most of the chip idle (small M: sampling, small batches), split-K on top
-struct ConvPlan { int BM, BN, splits, kt_per_split; };
-static int g_tile = -2;                                // PSG_CONV_TILE=0..4 / psg_conv_set_tile pins a candidate (kernel A/B runs, tests)
-static int tile_setting() {
-    if (g_tile == -2) { const char* e = getenv("PSG_CONV_TILE"); const int v = e ? atoi(e) : -1; g_tile = (v >= 0 && v <= 4) ? v : -1; }
-    return g_tile;
-}
+struct ConvPlan { const ConvTile* tile; int splits, kt_per_split; };
 static ConvPlan conv_plan(const ConvP& p, int dtype, bool may_split) {
+    const ConvSettings& st = conv_settings();
     const int64_t M = p.M;
-    ConvPlan pl = {128, 128, 1, p.KT};
-    const int force = tile_setting();
-    const int cand[5][2] = {{128, 128}, {128, 64}, {64, 64}, {128, 160}, {64, 160}};
-    double eff[5] = {1.0, 0.78, 0.55, 1.0, 0.70};      // measured relative MFMA efficiency of the tile shapes
-    // (a K <= 640 boost for 128x64 - three resident workgroups hiding the short loop ends - paid before the epilogue was
-    //  specialised per kind; since then 128x128 wins those layers by 10 %: gemm_direct.py)
-    if (dtype != PSG_BF16 || p.ntap > 0) eff[3] = eff[4] = 0.0;   // 160 = 2 x 5 x 16: only the 16x16x32 bf16 tiles divide it
+    const int mode = conv_mode(p);
+    ConvPlan pl = {nullptr, 1, p.KT};
+    if (st.tile >= 0) {                                    // pinned: that row (none: no such tile for the dtype), unsplit
+        for (const ConvTile& t : CONV_TILES) if (t.dtype == dtype && t.cand == st.tile) pl.tile = &t;
+        return pl;
+    }
     // resident workgroups on the chip (2 per CU; psg_set_available_cus / psg_set_reserve_rounds)
     const double slots = 2.0 * avail_cus_for((double)((M + 127) / 128) * (double)((p.N + 127) / 128) / 512.0);
     double best = -1.0;
-    for (int c = 0; c < 5; ++c) {
-        const double tiles = (double)((M + cand[c][0] - 1) / cand[c][0]) * (double)((p.N + cand[c][1] - 1) / cand[c][1]);
-        const double useful = (double)M * p.N / (tiles * cand[c][0] * cand[c][1]);
+    for (const ConvTile& t : CONV_TILES) {
+        if (t.dtype != dtype || !t.kernels().gemm[mode][0][0]) continue;
+        const double tiles = conv_tile_count(p, t);
+        const double useful = (double)M * p.N / (tiles * t.BM * t.BN);
         const double waves = ceil(tiles / slots);
-        double score = useful * (tiles / (waves * slots)) * eff[c];
-        if (force >= 0) score = (c == force) ? 1.0 : 0.0;
-        if (score > best) { best = score; pl.BM = cand[c][0]; pl.BN = cand[c][1]; }
+        const double score = useful * (tiles / (waves * slots)) * t.eff;
+        if (score > best) { best = score; pl.tile = &t; }
     }
     // Split-K: when the unsplit grid fills less than ~60 % of the chip and the K loop is long enough to share.  Estimated time
-    // of (tile shape c, s splits) in K steps of a 128 x 128 tile: rounds x (steps per split + 6 of prologue / epilogue) x
+    // of (tile t, s splits) in K steps of a 128 x 128 tile: rounds x (steps per split + 6 of prologue / epilogue) x
     // (tile area / efficiency) + the partial tiles' trip through memory ((s + 1) x M x N x 4 bytes at ~3 TB/s, 0.9 us per step).
-    static int nosplit = -1;
-    if (nosplit < 0) { const char* e = getenv("PSG_CONV_SPLITK"); nosplit = (e && atoi(e) == 0) ? 1 : 0; }
-    if (may_split && !nosplit && p.ntap == 0 && force < 0 && p.KT >= 16) {
-        const double tiles0 = (double)((M + pl.BM - 1) / pl.BM) * (double)((p.N + pl.BN - 1) / pl.BN);
-        if (tiles0 < 0.6 * slots || best < 0.6) {
-            auto est = [&](int c, int s) {
-                const double tiles = (double)((M + cand[c][0] - 1) / cand[c][0]) * (double)((p.N + cand[c][1] - 1) / cand[c][1]);
-                const int per = (p.KT + s - 1) / s;
-                const double rounds = ceil(tiles * s / slots);
-                const double step = (double)cand[c][0] * cand[c][1] / (128.0 * 128.0) / eff[c];
-                const double fin = s > 1 ? ((s + 1.0) * (double)M * p.N * 4.0 / 3.0e6 + 4.0) / 0.9 : 0.0;
-                return rounds * (per + 6.0) * step + fin;
-            };
-            int bc = 0;
-            for (int c = 0; c < 5; ++c) if (cand[c][0] == pl.BM && cand[c][1] == pl.BN) bc = c;
-            double tbest = est(bc, 1);
-            const int svals[9] = {2, 3, 4, 5, 6, 8, 10, 12, 16};
-            for (int c = 0; c < 5; ++c) {
-                if (eff[c] <= 0.0) continue;
-                for (int si = 0; si < 9; ++si) {
-                    const int s = svals[si];
-                    if (p.KT / s < 8) break;                       // at least 8 K steps per split
-                    if ((double)s * M * p.N * 4.0 > 256.0e6) break;   // partial tiles: <= 256 MB
-                    const double t = est(c, s);
-                    if (t < tbest * 0.9) { tbest = t; pl.BM = cand[c][0]; pl.BN = cand[c][1]; pl.splits = s; }
-                }
+    if (may_split && st.splitk && pl.tile && p.KT >= 16 && (conv_tile_count(p, *pl.tile) < 0.6 * slots || best < 0.6)) {
+        auto est = [&](const ConvTile& t, int s) {
+            const int per = (p.KT + s - 1) / s;
+            const double rounds = ceil(conv_tile_count(p, t) * s / slots);
+            const double step = (double)t.BM * t.BN / (128.0 * 128.0) / t.eff;
+            const double fin = s > 1 ? ((s + 1.0) * (double)M * p.N * 4.0 / 3.0e6 + 4.0) / 0.9 : 0.0;
+            return rounds * (per + 6.0) * step + fin;
+        };
+        double tbest = est(*pl.tile, 1);
+        const int svals[9] = {2, 3, 4, 5, 6, 8, 10, 12, 16};
+        for (const ConvTile& t : CONV_TILES) {
+            if (t.dtype != dtype || !t.kernels().gemm[mode][1][0]) continue;
+            for (int si = 0; si < 9; ++si) {
+                const int s = svals[si];
+                if (p.KT / s < 8) break;                       // at least 8 K steps per split
+                if ((double)s * M * p.N * 4.0 > 256.0e6) break;   // partial tiles: <= 256 MB
+                const double e = est(t, s);
+                if (e < tbest * 0.9) { tbest = e; pl.tile = &t; pl.splits = s; }
             }
-            if (pl.splits > 1) { pl.kt_per_split = (p.KT + pl.splits - 1) / pl.splits; pl.splits = (p.KT + pl.kt_per_split - 1) / pl.kt_per_split; }
         }
+        if (pl.splits > 1) { pl.kt_per_split = (p.KT + pl.splits - 1) / pl.splits; pl.splits = (p.KT + pl.kt_per_split - 1) / pl.kt_per_split; }
     }
     return pl;
 }
 
-// Border-class form (TapCls in conv_gemm_kernel.h): PSG_CONV_TAPCLASS=0 / psg_conv_set_tapclass(0) turns it off, 1 (default)
-// uses it where the estimate below says it pays, 2 on every launch it applies to (per-layer A/B runs).
-static int g_tapcls = -1;
-static int64_t g_tapcls_launches = 0;
-static int tapcls_setting() {
-    if (g_tapcls < 0) { const char* e = getenv("PSG_CONV_TAPCLASS"); g_tapcls = e ? atoi(e) : 1; }
-    return g_tapcls;
-}
-
-// bf16, taps-innermost fast path, stride-1 3x3 pad 1 (forward or data gradient), at least 3 x 3 positions, unsplit
-static bool tapcls_applicable(const ConvP& p, int dtype) {
-    return dtype == PSG_BF16 && p.fast && p.ntap == 0 && p.ks == 3 && p.stride == 1 && p.pad == 1 && p.Ho >= 3 && p.Wo >= 3 &&
+// Border-class form (TapCls in conv_gemm_kernel.h; ConvSettings::tapcls).  It applies to: a tile with the kernel (bf16), the
+// taps-innermost fast path, stride-1 3x3 pad 1 (forward or data gradient), at least 3 x 3 positions, unsplit
+static bool tapcls_applicable(const ConvP& p, const ConvKernels& k) {
+    return k.gemm[conv_mode(p)][0][1] && p.fast && p.ks == 3 && p.stride == 1 && p.pad == 1 && p.Ho >= 3 && p.Wo >= 3 &&
            p.splits == 1 && (int64_t)p.M + 9 * 128 < (1 << 24);
+}
+static int tapcls_mtiles(const ConvP& p, int BM) {
+    const TapCls c = tapcls_of(p, BM, 1 << 30, p.transposed != 0);
+    return c.r0 / BM + (c.nrow + BM - 1) / BM;
 }
 
 // Makespan estimate of the plain and the border-class grid of a BM x BN plan.  The two resident workgroups of a CU share its
@@ -145,43 +154,44 @@ static bool tapcls_pays(const ConvP& p, int BM, int BN) {
     return pays;
 }
 
-// One launch of psg_conv_fwd as the host planned it: the tile, the K split, the border-class order, persistent pointwise or
-// per-tile kernel, and the grid.  conv_plan_launch decides, launch_planned only reads - so psg_conv_route reports what
-// psg_conv_fwd runs, from the same code.
-struct ConvLaunch {
-    ConvP p;                       // the launch's parameters: splits, kt_per_split, tapcls (and the parity-class fields) set
-    int BM, BN, mode, pw, epi_lds; // epi_lds: the launch stores through the LDS staging (bf16, unsplit, 16-byte row chunks)
-    int mtiles, ntiles, grid;
-};
-
-static int conv_plan_launch(const ConvP& p0, int dtype, ConvLaunch& L) {
+// The plan of one launch: the tile, the K split, the border-class order, persistent pointwise or per-tile kernel, the grid,
+// the LDS and workspace bytes and the profile's work figures (ConvLaunch).  "No kernel for this (dtype, tile, mode, split,
+// class)" is decided here, from the tile table, for psg_conv_route and psg_conv_fwd alike.  size_only: stop once the split
+// (ws_bytes) is known - psg_conv_fwd_workspace_bytes, which must not pay for tapcls_pays.
+static int conv_plan_launch(const ConvP& p0, int dtype, bool size_only, ConvLaunch& L) {
+    const ConvSettings& st = conv_settings();
     ConvP& p = L.p;
     p = p0;
     ConvPlan pl = conv_plan(p, dtype, p.ws != nullptr);
-    p.splits = 1; p.kt_per_split = p.KT;
-    if (pl.splits > 1) {
-        if (p.ws != nullptr && (int64_t)pl.splits * p.M * p.N * 4 <= p.ws_bytes) { p.splits = pl.splits; p.kt_per_split = pl.kt_per_split; }
-        else pl = conv_plan(p, dtype, false);          // workspace too small: the best UNSPLIT tile, not the split plan's tile
-    }
-    const int BM = pl.BM, BN = pl.BN;
+    if (conv_ws_bytes(p, pl.splits) > p.ws_bytes) pl = conv_plan(p, dtype, false);   // workspace too small: the best UNSPLIT tile, not the split plan's tile
+    PSG_REQUIRE(pl.tile, PSG_ERR_ARG, "conv_gemm: no %s tile for candidate %d", dtype == PSG_BF16 ? "bf16" : "fp32", st.tile);
+    const int BM = pl.tile->BM, BN = pl.tile->BN;
+    const ConvKernels& k = pl.tile->kernels();
+    p.splits = pl.splits; p.kt_per_split = pl.kt_per_split;
+    L.ws_bytes = conv_ws_bytes(p, p.splits);
+    if (size_only) return PSG_OK;
+    p.tapcls = (st.tapcls && tapcls_applicable(p, k) && (st.tapcls == 2 || tapcls_pays(p, BM, BN))) ? 1 : 0;
     L.BM = BM; L.BN = BN; L.mode = conv_mode(p);
-    // (only a pinned tile gets here with a 160-wide tile the dtype / mode has no kernel for: the plan scores them 0)
-    if (BN == 160 && dtype != PSG_BF16) return set_error(PSG_ERR_ARG, "conv_gemm: no %s %dx%d tile", "fp32", BM, BN);
-    if (BN == 160 && L.mode == 3) return set_error(PSG_ERR_ARG, "conv_gemm: no 160-wide parity-class kernel");
-    p.tapcls = 0;
-    if (tapcls_setting() && tapcls_applicable(p, dtype) && (tapcls_setting() == 2 || tapcls_pays(p, BM, BN))) p.tapcls = 1;
-    L.pw = (BM == 128 && BN == 128 && p.splits == 1 && conv_pw_applicable(p, dtype)) ? 1 : 0;
-    if (L.pw) conv_pw_grid(p, L.mtiles, L.ntiles, L.grid);
-    else {
-        L.mtiles = conv_mtiles(p, BM); L.ntiles = (p.N + BN - 1) / BN;
-        L.grid = L.mtiles * L.ntiles * (p.splits > 1 ? p.splits : 1);
+    L.kernel = k.gemm[L.mode][p.splits > 1][p.tapcls]; L.finish = k.finish;
+    // (only a pinned tile gets here without a kernel - 160 wide, parity class: the plan skips the null entries)
+    PSG_REQUIRE(L.kernel, PSG_ERR_ARG, "conv_gemm: no %s %dx%d kernel for mode %d", dtype == PSG_BF16 ? "bf16" : "fp32", BM, BN, L.mode);
+    L.pw = (st.pw && BM == 128 && BN == 128 && conv_pw_plan(dtype, L)) ? 1 : 0;
+    if (!L.pw) {
+        L.mtiles = p.tapcls ? tapcls_mtiles(p, BM) : (p.M + BM - 1) / BM; L.ntiles = (p.N + BN - 1) / BN;
+        L.grid = L.mtiles * L.ntiles * p.splits;
+        L.lds = conv_lds(BM, BN, p.tapcls);
     }
+    p.mtiles = L.mtiles; p.ntiles = L.ntiles;
     L.epi_lds = (p.epi_lds && p.splits == 1) ? 1 : 0;
+    // useful FLOPs; algorithmic bytes: every input pixel, weight and output element once (+ the epilogue's residual / saved tensors)
+    L.flops = 2.0 * (double)p.M * (double)p.N * (double)p.taps * (double)p.Cin;
+    L.abytes = ((double)p.B * p.Hi * p.Wi * p.Cin + (double)p.N * p.taps * p.Cin + (double)p.M * p.N * (1.0 + (p.residual || p.dact_u ? 1.0 : 0.0) + (p.preact ? 1.0 : 0.0))) *
+               (dtype == PSG_BF16 ? 2.0 : 4.0);
     return PSG_OK;
 }
 
 // The launches of a descriptor that conv_setup accepted: one, or up to four for the data gradient of a stride-2 3x3 conv
-static int conv_plan_all(const ConvP& p, int dtype, ConvLaunch (&L)[4], int& n) {
+static int conv_plan_all(const ConvP& p, int dtype, bool size_only, ConvLaunch (&L)[4], int& n) {
     n = 0;
     if (p.transposed && p.stride == 2 && p.fast && p.ks == 3) {
         // Data gradient of a stride-2 conv: a result pixel (ho, wo) is reached only by the taps with
@@ -204,37 +214,36 @@ static int conv_plan_all(const ConvP& p, int dtype, ConvLaunch (&L)[4], int& n) 
                 q.M = p.B * q.sub_nH * q.sub_nW;
                 q.taps = q.ntap;                           // (profiling: useful FLOPs of this class)
                 q.KT = q.ntap * p.tpt;
-                const int rc = conv_plan_launch(q, dtype, L[n]);
+                const int rc = conv_plan_launch(q, dtype, size_only, L[n]);
                 if (rc) return rc;
                 ++n;
             }
         return PSG_OK;
     }
-    const int rc = conv_plan_launch(p, dtype, L[0]);
+    const int rc = conv_plan_launch(p, dtype, size_only, L[0]);
     if (rc) return rc;
     n = 1;
     return PSG_OK;
 }
 
-static int launch_planned(const ConvLaunch& L, int dtype, hipStream_t s) {
+static int launch_planned(const ConvLaunch& L, hipStream_t s) {
     ConvP p = L.p;
-    const int BM = L.BM, BN = L.BN;
 #ifdef PSG_ABL
     if (PSG_ABL & 8) { const char* e = getenv("PSG_DBG_PTR"); p.ws = (e && p.splits <= 1) ? reinterpret_cast<float*>(strtoull(e, nullptr, 0)) : (p.splits <= 1 ? nullptr : p.ws); }
 #endif
-    {
-        static int dbg = -1;                               // PSG_CONV_DEBUG=1: print the tile chosen for every launch
-        if (dbg < 0) { const char* e = getenv("PSG_CONV_DEBUG"); dbg = e ? atoi(e) : 0; }
-        if (dbg) fprintf(stderr, "psg conv: M=%d N=%d Cin=%d ks=%d tr=%d fast=%d epi_lds=%d -> tile %dx%d splits=%d tapcls=%d\n", p.M, p.N, p.Cin, p.ks, p.transposed,
-                         p.fast, p.epi_lds, BM, BN, p.splits, p.tapcls);
+    ProfScope prof(p.transposed ? PROF_CONV_DGRAD : PROF_CONV_FWD, L.flops, s, L.abytes);
+    const ConvP fin = p;                               // (the finishing kernel runs the epilogue: it keeps the operands)
+    if (p.splits > 1) { p.bias = nullptr; p.rowadd = nullptr; p.residual = nullptr; p.preact = nullptr; p.dact_u = nullptr; }
+    if (L.pw) hipLaunchKernelGGL(L.pw_kernel, dim3(L.grid), dim3(256), L.lds, s, p, L.mtiles * L.ntiles, L.aux_bytes);
+    else hipLaunchKernelGGL(L.kernel, dim3(L.grid), dim3(256), L.lds, s, p);
+    g_pw_launches += L.pw; g_tapcls_launches += p.tapcls;
+    PSG_LAUNCH_CHECK(L.pw ? "conv_pw launch" : "conv_gemm launch");
+    if (p.splits > 1) {
+        const int64_t n = (int64_t)p.M * (p.N >> 2);
+        hipLaunchKernelGGL(L.finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, fin);
+        PSG_LAUNCH_CHECK("conv_splitk_finish launch");
     }
-    if (L.pw) return launch_conv_pw(p, s);
-    if (p.tapcls) ++g_tapcls_launches;
-#define X(T, TBM, TBN) \
-    if ((dtype == PSG_BF16) == std::is_same<T, bf16_t>::value && BM == TBM && BN == TBN) return launch_conv<T, TBM, TBN>(p, s);
-    PSG_CONV_TILES(X)
-#undef X
-    return set_error(PSG_ERR_ARG, "conv_gemm: no %s %dx%d tile", dtype == PSG_BF16 ? "bf16" : "fp32", BM, BN);
+    return PSG_OK;
 }
 
 }  // namespace psg
@@ -243,10 +252,11 @@ using namespace psg;
 extern "C" {
 
 int psg_conv_init_attrs(void) {
-    int rc;
-#define X(T, BM, BN) if ((rc = set_conv_attrs<T, BM, BN>())) return rc;
-    PSG_CONV_TILES(X)
-#undef X
+    for (const ConvTile& t : CONV_TILES)
+        for (const auto& mode : t.kernels().gemm)
+            for (const auto& split : mode)
+                for (int cls = 0; cls < 2; ++cls)
+                    if (split[cls]) if (int rc = set_max_lds(conv_lds(t.BM, t.BN, cls), split[cls])) return rc;
     return conv_pw_set_attrs();
 }
 
@@ -299,14 +309,10 @@ static int conv_setup(const psg_conv_desc* d, ConvP& p) {
     p.M = (int)M; p.taps = taps; p.cpt = d->Cin / CH; p.Kpad = (int)Kpad; p.KT = (int)(Kpad / (8 * CH));
     p.fast = (p.cpt % 8 == 0) ? 1 : 0; p.tpt = p.fast ? p.cpt / 8 : 1;
     p.act = d->act; p.alpha = d->alpha; p.flags = d->flags;
-    {
-        // coalesced (LDS-staged) stores need 16-byte row chunks: bf16, channel counts and row strides multiples of 8
-        static int off = -1;
-        if (off < 0) { const char* e = getenv("PSG_EPI_LDS"); off = (e && atoi(e) == 0) ? 1 : 0; }
-        p.epi_lds = (!off && d->dtype == PSG_BF16 && d->Cout % 8 == 0 && d->ldy % 8 == 0 && (!d->preact || d->ld_preact % 8 == 0) &&
-                     (!d->residual || d->ld_residual % 8 == 0) && (!d->dact_u || d->ld_dact % 8 == 0)) ? 1 : 0;
-    }
-    { static int gen = -1; if (gen < 0) { const char* e = getenv("PSG_EPI_KINDS"); gen = (e && atoi(e) == 0) ? 1 : 0; } p.epi_generic = (gen || (d->flags & PSG_CONV_GENERIC_EPILOGUE)) ? 1 : 0; }
+    // coalesced (LDS-staged) stores need 16-byte row chunks: bf16, channel counts and row strides multiples of 8
+    p.epi_lds = (conv_settings().epi_lds && d->dtype == PSG_BF16 && d->Cout % 8 == 0 && d->ldy % 8 == 0 && (!d->preact || d->ld_preact % 8 == 0) &&
+                 (!d->residual || d->ld_residual % 8 == 0) && (!d->dact_u || d->ld_dact % 8 == 0)) ? 1 : 0;
+    p.epi_generic = (!conv_settings().epi_kinds || (d->flags & PSG_CONV_GENERIC_EPILOGUE)) ? 1 : 0;
     p.drop_thresh = d->drop_p > 0.f ? drop_thresh(d->drop_p) : 0u;
     p.drop_scale = d->drop_p > 0.f ? 1.0f / (1.0f - d->drop_p) : 1.0f;
     p.drop_seed = d->drop_seed;
@@ -333,9 +339,12 @@ static int conv_setup(const psg_conv_desc* d, ConvP& p) {
 int64_t psg_conv_fwd_workspace_bytes(const psg_conv_desc* d) {
     ConvP p;
     if (conv_setup(d, p) != PSG_OK) return -1;
-    if (p.transposed && p.stride == 2 && p.fast && p.ks == 3) return 0;
-    const ConvPlan pl = conv_plan(p, d->dtype, true);
-    return pl.splits > 1 ? (int64_t)pl.splits * p.M * p.N * 4 : 0;
+    static float any_ws;                               // plan as psg_conv_fwd would with an unlimited workspace
+    p.ws = &any_ws; p.ws_bytes = INT64_MAX;
+    ConvLaunch L[4];
+    int n = 0;
+    if (conv_plan_all(p, d->dtype, true, L, n)) return 0;    // (a pinned tile the dtype has no row for: pinned launches are never split)
+    return L[0].ws_bytes;                              // (parity-class launches - the only plans of more than one - are never split)
 }
 
 int psg_conv_fwd(const psg_conv_desc* d, psg_stream_t stream) {
@@ -344,9 +353,9 @@ int psg_conv_fwd(const psg_conv_desc* d, psg_stream_t stream) {
     if (rc) return rc;
     ConvLaunch L[4];
     int n = 0;
-    if ((rc = conv_plan_all(p, d->dtype, L, n))) return rc;
+    if ((rc = conv_plan_all(p, d->dtype, false, L, n))) return rc;
     for (int i = 0; i < n; ++i)
-        if ((rc = launch_planned(L[i], d->dtype, (hipStream_t)stream))) return rc;
+        if ((rc = launch_planned(L[i], (hipStream_t)stream))) return rc;
     return PSG_OK;
 }
 
@@ -357,7 +366,7 @@ int psg_conv_route(const psg_conv_desc* d, int32_t* out) {
     if (rc) return rc;
     ConvLaunch L[4];
     int n = 0;
-    if ((rc = conv_plan_all(p, d->dtype, L, n))) return rc;
+    if ((rc = conv_plan_all(p, d->dtype, false, L, n))) return rc;
     for (int i = 0; i < 1 + 4 * PSG_CONV_ROUTE_FIELDS; ++i) out[i] = 0;
     out[0] = n;
     for (int i = 0; i < n; ++i) {
@@ -369,8 +378,10 @@ int psg_conv_route(const psg_conv_desc* d, int32_t* out) {
     return PSG_OK;
 }
 
-int psg_conv_set_tile(int c) { psg::g_tile = (c >= 0 && c <= 4) ? c : -1; return PSG_OK; }
-int psg_conv_set_tapclass(int on) { psg::g_tapcls = on < 0 ? 0 : (on > 2 ? 2 : on); return PSG_OK; }
-int64_t psg_conv_tapclass_launches(void) { return psg::g_tapcls_launches; }
+int psg_conv_set_tile(int c) { conv_settings().tile = tile_pin(c); return PSG_OK; }
+int psg_conv_set_tapclass(int on) { conv_settings().tapcls = tapcls_pin(on); return PSG_OK; }
+int psg_conv_set_pw(int on) { conv_settings().pw = on != 0; return PSG_OK; }
+int64_t psg_conv_tapclass_launches(void) { return g_tapcls_launches; }
+int64_t psg_conv_pw_launches(void) { return g_pw_launches; }
 
 }  // extern "C"

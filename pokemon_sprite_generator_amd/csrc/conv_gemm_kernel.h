@@ -141,6 +141,14 @@ __device__ __forceinline__ void conv_value(const ConvP& p, int m, int n, f32x4& 
 // arithmetic, branch-free.  EK_GENERIC keeps the run-time form (SiLU / ReLU / tanh, activation-gradient backward forms,
 // and every fp32 launch: the exact path's arithmetic order does not change).
 enum { EK_PLAIN = 0, EK_DROP = 1, EK_GELU = 2, EK_GELU_DROP = 3, EK_DMUL = 4, EK_GENERIC = 5 };
+// the kind of a launch: conv_gemm_kernel switches on it, the host picks conv_pw.hip's instantiation by it (same bits either way)
+__host__ __device__ __forceinline__ int conv_epi_kind(const ConvP& p) {
+    if (p.epi_generic) return EK_GENERIC;
+    if (p.dact_u) return ((p.flags & PSG_CONV_DACT_MUL) && !p.drop_thresh) ? EK_DMUL : EK_GENERIC;
+    if (p.act == PSG_ACT_NONE) return p.drop_thresh ? EK_DROP : EK_PLAIN;
+    if (p.act == PSG_ACT_GELU) return p.drop_thresh ? EK_GELU_DROP : EK_GELU;
+    return EK_GENERIC;
+}
 // AUX_LATER: stop before the aux operand (the residual, or EK_DMUL's saved derivative) enters - conv_aux_k applies it
 // later to the same fp32 value, so the result is the one-step form's bit for bit.
 template <typename T, int EK, bool AUX_LATER = false>
@@ -238,10 +246,6 @@ __host__ __device__ __forceinline__ TapCls tapcls_of(const ConvP& p, int BM, int
         t0 += nt;
     }
     return c;
-}
-static inline int tapcls_mtiles(const ConvP& p, int BM) {
-    const TapCls c = tapcls_of(p, BM, 1 << 30, p.transposed != 0);
-    return c.r0 / BM + (c.nrow + BM - 1) / BM;
 }
 // output position (sample b, ho, wo) of class row r, 0 <= r < c.nrow (fastdiv: rows < 2^24, checked on the host)
 __device__ __forceinline__ void tapcls_pix(const TapCls& c, float inv_hw, float inv_nw, int r, int& b, int& ho, int& wo) {
@@ -904,15 +908,9 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvP p) {
             if (p.preact) stage_and_flush(std::integral_constant<int, 0>{});
             stage_and_flush(std::integral_constant<int, 1>{});
             };
-            int ek = EK_GENERIC;
-            if (!p.epi_generic) {
-                if (p.dact_u) { if ((p.flags & PSG_CONV_DACT_MUL) && !p.drop_thresh) ek = EK_DMUL; }
-                else if (p.act == PSG_ACT_NONE) ek = p.drop_thresh ? EK_DROP : EK_PLAIN;
-                else if (p.act == PSG_ACT_GELU) ek = p.drop_thresh ? EK_GELU_DROP : EK_GELU;
-            }
             // (the parity-class kernels keep the run-time form: their tap tables leave no scalar registers for more copies)
             if constexpr (MODE == 3) { epilogue(std::integral_constant<int, EK_GENERIC>{}); return; }
-            else switch (ek) {
+            else switch (conv_epi_kind(p)) {
                 case EK_PLAIN: epilogue(std::integral_constant<int, EK_PLAIN>{}); break;
                 case EK_DROP: epilogue(std::integral_constant<int, EK_DROP>{}); break;
                 case EK_GELU: epilogue(std::integral_constant<int, EK_GELU>{}); break;
@@ -1001,66 +999,29 @@ __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(const ConvP p) 
 // dynamic LDS of a BM x BN conv_gemm_kernel: two [W tile | X tile] buffers of 128-byte rows (+ the border-class row table)
 constexpr int conv_lds(int BM, int BN, bool cls) { return 2 * (BM + BN) * 128 + (cls ? BM * 4 : 0); }
 
-// gather mode of a launch (MODE of conv_gemm_kernel) and its M-tile count: launch_conv and the host's plan (conv_gemm.hip)
-static inline int conv_mode(const ConvP& p) { return p.ntap > 0 ? 3 : (!p.fast ? 2 : (!p.transposed ? 0 : (p.stride == 1 ? 1 : 2))); }
-static inline int conv_mtiles(const ConvP& p, int BM) { return p.tapcls ? tapcls_mtiles(p, BM) : (p.M + BM - 1) / BM; }
+// The kernels of one (dtype, BM, BN) tile, indexed [MODE][SPLITK][CLS] (null: that combination is not instantiated), and the
+// split-K finishing kernel.  conv_tile.hip defines conv_kernels<T, BM, BN>() - the addresses are taken where the kernels are
+// instantiated, one translation unit per tile; conv_gemm.hip's tile table points at them.
+typedef void (*ConvKernel)(const ConvP);
+struct ConvKernels { ConvKernel gemm[4][2][2]; ConvKernel finish; };
+template <typename T, int BM, int BN> const ConvKernels& conv_kernels();
+typedef void (*ConvPwKernel)(const ConvP, int, uint32_t);      // conv_pw.hip's persistent pointwise kernel
 
-template <typename T, int BM, int BN>
-int launch_conv(const ConvP& p, hipStream_t stream) {
-    const size_t lds = conv_lds(BM, BN, p.tapcls);
-    ConvP q = p;
-    q.mtiles = conv_mtiles(p, BM);
-    q.ntiles = (p.N + BN - 1) / BN;
-    const int grid = q.mtiles * q.ntiles * (q.splits > 1 ? q.splits : 1);
-    // algorithmic bytes: every input pixel, weight and output element once (+ the epilogue's residual / saved tensors)
-    const double esz = (double)sizeof(T);
-    const double abytes = ((double)p.B * p.Hi * p.Wi * p.Cin + (double)p.N * p.taps * p.Cin + (double)p.M * p.N * (1.0 + (p.residual || p.dact_u ? 1.0 : 0.0) + (p.preact ? 1.0 : 0.0))) * esz;
-    ProfScope prof(p.transposed ? PROF_CONV_DGRAD : PROF_CONV_FWD, 2.0 * (double)p.M * (double)p.N * (double)p.taps * (double)p.Cin, stream, abytes);
-    const ConvP fin = q;                               // (the finishing kernel runs the epilogue: it keeps the operands)
-    if (q.splits > 1) { q.bias = nullptr; q.rowadd = nullptr; q.residual = nullptr; q.preact = nullptr; q.dact_u = nullptr; }
-    const int mode = conv_mode(p);
-    if (p.tapcls) {
-        if (q.splits > 1 || (mode != 0 && mode != 1) || p.ks != 3 || p.stride != 1 || p.pad != 1 || p.Ho < 3 || p.Wo < 3)
-            return set_error(PSG_ERR_ARG, "conv_gemm: border-class form needs an unsplit stride-1 3x3 pad-1 launch");
-        if constexpr (sizeof(T) == 2) {
-            if (mode == 0) hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, 0, false, true>), dim3(grid), dim3(256), lds, stream, q);
-            else hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, 1, false, true>), dim3(grid), dim3(256), lds, stream, q);
-        } else return set_error(PSG_ERR_ARG, "conv_gemm: no fp32 border-class kernel");
-    } else if (q.splits > 1) {
-        if (mode == 0) hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, 0, true>), dim3(grid), dim3(256), lds, stream, q);
-        else if (mode == 1) hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, 1, true>), dim3(grid), dim3(256), lds, stream, q);
-        else if (mode == 2) hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, 2, true>), dim3(grid), dim3(256), lds, stream, q);
-        else return set_error(PSG_ERR_ARG, "conv_gemm: parity-class launches are never split");
-    } else if (mode == 3) {
-        // (the 160-wide tiles are not built for the parity-class mode: its tap tables push the kernel past the scalar
-        //  register file - one layer, the first downsample's data gradient, runs 128x128 instead)
-        if constexpr (BN != 160) hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, 3>), dim3(grid), dim3(256), lds, stream, q);
-        else return set_error(PSG_ERR_ARG, "conv_gemm: no 160-wide parity-class kernel");
-    } else if (mode == 0) hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, 0>), dim3(grid), dim3(256), lds, stream, q);
-    else if (mode == 1) hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, 1>), dim3(grid), dim3(256), lds, stream, q);
-    else hipLaunchKernelGGL((conv_gemm_kernel<T, BM, BN, 2>), dim3(grid), dim3(256), lds, stream, q);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "conv_gemm launch");
-    if (q.splits > 1) {
-        const int64_t n = (int64_t)q.M * (q.N >> 2);
-        hipLaunchKernelGGL((conv_splitk_finish_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, fin);
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "conv_splitk_finish launch");
-    }
-    return PSG_OK;
-}
-
-template <typename T, int BM, int BN>
-int set_conv_attrs() {
-    constexpr int lds = conv_lds(BM, BN, false);
-    int rc = set_max_lds(lds, conv_gemm_kernel<T, BM, BN, 0>, conv_gemm_kernel<T, BM, BN, 1>, conv_gemm_kernel<T, BM, BN, 2>,
-                         conv_gemm_kernel<T, BM, BN, 0, true>, conv_gemm_kernel<T, BM, BN, 1, true>, conv_gemm_kernel<T, BM, BN, 2, true>);
-    if constexpr (BN != 160)
-        if (!rc) rc = set_max_lds(lds, conv_gemm_kernel<T, BM, BN, 3>);
-    if constexpr (sizeof(T) == 2)
-        if (!rc) rc = set_max_lds(conv_lds(BM, BN, true), conv_gemm_kernel<T, BM, BN, 0, false, true>, conv_gemm_kernel<T, BM, BN, 1, false, true>);
-    return rc;
-}
+// One launch of psg_conv_fwd as the host planned it (conv_gemm.hip: conv_plan_launch decides, launch_planned only reads - so
+// psg_conv_route reports what psg_conv_fwd runs, from the same code).
+struct ConvLaunch {
+    ConvP p;                       // the kernel's argument: splits, kt_per_split, tapcls, mtiles, ntiles (and the parity-class fields) set
+    int BM, BN, mode, pw, epi_lds; // epi_lds: the launch stores through the LDS staging (bf16, unsplit, 16-byte row chunks)
+    int mtiles, ntiles, grid, lds;
+    ConvKernel kernel, finish;     // the tile's kernel for (mode, split, class) and, for a split launch, the finishing kernel - or
+    ConvPwKernel pw_kernel;        // (pw) the pointwise instantiation for (epilogue kind, aux, preact, transposed)
+    uint32_t aux_bytes;            // (pw) extent of the residual / saved derivative for its bounds-checked loads
+    int64_t ws_bytes;              // split-K workspace the launch uses (0: unsplit)
+    double flops, abytes;          // ProfScope: useful FLOPs and algorithmic operand bytes
+};
+// conv_pw.hip: fills pw_kernel, aux_bytes, the tile counts, the persistent grid and the LDS bytes if L.p qualifies for the kernel
+bool conv_pw_plan(int dtype, ConvLaunch& L);
+int conv_pw_set_attrs();
 
 }  // namespace psg
 

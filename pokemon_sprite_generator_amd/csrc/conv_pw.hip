@@ -253,106 +253,53 @@ __global__ __launch_bounds__(256, 2) void conv_pw_kernel(const ConvP p, const in
 #endif
 }
 
-// ---- host side ----------------------------------------------------------------------------------------------------------
-static int g_pw_on = -1;                                 // PSG_CONV_PW=0 / psg_conv_set_pw(0): every pointwise layer on conv_gemm_kernel (A/B, tests)
-static int64_t g_pw_launches = 0;
-static int pw_enabled() {
-    if (g_pw_on < 0) { const char* e = getenv("PSG_CONV_PW"); g_pw_on = (e && atoi(e) == 0) ? 0 : 1; }
-    return g_pw_on;
-}
-
-static int pw_kind(const ConvP& p) {
-    if (p.epi_generic) return -1;
-    if (p.dact_u) return ((p.flags & PSG_CONV_DACT_MUL) && !p.drop_thresh) ? EK_DMUL : -1;
-    if (p.act == PSG_ACT_NONE) return p.drop_thresh ? EK_DROP : EK_PLAIN;
-    if (p.act == PSG_ACT_GELU) return p.drop_thresh ? EK_GELU_DROP : EK_GELU;
-    return -1;
-}
-
+// ---- host side: the instantiations, and the plan of a launch (conv_gemm.hip launches it) -----------------------------------
 static constexpr int PW_LDS = 2 * 256 * 128 + 4 * 16 * (64 * 2 + 16);
 
-#define PSG_PW_FOR_ALL(X)                                                                                  \
-    X(EK_PLAIN, false, false) X(EK_PLAIN, true, false) X(EK_DROP, false, false) X(EK_DROP, true, false)   \
-    X(EK_GELU, false, false) X(EK_GELU, false, true) X(EK_GELU_DROP, false, false) X(EK_GELU_DROP, false, true) \
-    X(EK_DMUL, true, false)
+struct PwVariant { int ek; bool aux, pre; ConvPwKernel kernel[2]; };      // kernel[transposed]
+template <int EK, bool AUX, bool PRE> constexpr PwVariant pw_variant() {
+    return {EK, AUX, PRE, {conv_pw_kernel<EK, AUX, PRE, false>, conv_pw_kernel<EK, AUX, PRE, true>}};
+}
+static const PwVariant PW_VARIANTS[] = {
+    pw_variant<EK_PLAIN, false, false>(), pw_variant<EK_PLAIN, true, false>(), pw_variant<EK_DROP, false, false>(), pw_variant<EK_DROP, true, false>(),
+    pw_variant<EK_GELU, false, false>(), pw_variant<EK_GELU, false, true>(), pw_variant<EK_GELU_DROP, false, false>(), pw_variant<EK_GELU_DROP, false, true>(),
+    pw_variant<EK_DMUL, true, false>(),
+};
 
-// PSG_PW_FOR_ALL has a conv_pw_kernel for p's (epilogue kind, aux, preact)
-static bool pw_instantiated(const ConvP& p) {
-    const int ek = pw_kind(p);
-    const bool aux = p.dact_u || p.residual, pre = p.preact != nullptr;
-#define X(EK, AUX, PRE) if (ek == EK && aux == AUX && pre == PRE) return true;
-    PSG_PW_FOR_ALL(X)
-#undef X
-    return false;
+int conv_pw_set_attrs() {
+    for (const PwVariant& v : PW_VARIANTS)
+        if (int rc = set_max_lds(PW_LDS, v.kernel[0], v.kernel[1])) return rc;
+    return PSG_OK;
 }
 
 // Whole 128 x 128 tiles, K a whole number (>= 3) of 64-channel slices, bf16, the staged (16-byte row) store conditions, an
 // epilogue kind with a branch-free copy, no per-sample add, and enough tiles that a resident workgroup gets at least two.
-bool conv_pw_applicable(const ConvP& p, int dtype) {
-    if (!pw_enabled() || dtype != PSG_BF16 || p.taps != 1 || p.stride != 1 || !p.fast || p.ntap > 0 || p.splits > 1) return false;
+bool conv_pw_plan(int dtype, ConvLaunch& L) {
+    const ConvP& p = L.p;
+    if (dtype != PSG_BF16 || p.taps != 1 || p.stride != 1 || !p.fast || p.ntap > 0 || p.splits > 1) return false;
     if (!p.epi_lds || p.rowadd || p.M % 128 || p.N % 128 || p.KT < 3 || p.Cin % 64) return false;
-    if (!pw_instantiated(p)) return false;
-    if (p.dact_u && p.residual) return false;
-    const int64_t tiles = (int64_t)(p.M / 128) * (p.N / 128);
-    if (tiles < 3 * (int64_t)avail_cus_for((double)tiles / 512.0)) return false;   // (1.5 tiles per resident slot: most workgroups get a second tile)
     const void* aux = p.dact_u ? p.dact_u : p.residual;
+    const int ek = conv_epi_kind(p);
+    L.pw_kernel = nullptr;
+    for (const PwVariant& v : PW_VARIANTS)
+        if (v.ek == ek && v.aux == (aux != nullptr) && v.pre == (p.preact != nullptr)) L.pw_kernel = v.kernel[p.transposed != 0];
+    if (!L.pw_kernel) return false;
+    if (p.dact_u && p.residual) return false;
+    const int64_t total = (int64_t)(p.M / 128) * (p.N / 128);
+    const int cus = avail_cus_for((double)total / 512.0);
+    if (total < 3 * cus) return false;                   // (1.5 tiles per resident slot: most workgroups get a second tile)
+    L.aux_bytes = 0u;
     if (aux) {
-        const int64_t ld = p.dact_u ? p.lddact : p.ldres;
-        if (((int64_t)p.M - 1) * ld * 2 + (int64_t)p.N * 2 >= 0x7FFFFFF0ll || !aligned16(aux)) return false;
+        const int64_t ld = p.dact_u ? p.lddact : p.ldres, bytes = ((int64_t)p.M - 1) * ld * 2 + (int64_t)p.N * 2;
+        if (bytes >= 0x7FFFFFF0ll || !aligned16(aux)) return false;
+        L.aux_bytes = (uint32_t)bytes;
     }
     if (p.preact && (p.ldpre % 8 || !aligned16(p.preact))) return false;
     if (p.bias && !aligned16(p.bias)) return false;
+    // the persistent grid: the resident slots, at most one per tile (a virtual block keeps its XCD: v and v + G agree mod 8)
+    L.mtiles = p.M / 128; L.ntiles = p.N / 128; L.lds = PW_LDS;
+    L.grid = (int)(2 * cus < total ? 2 * cus : total) & ~7;
     return true;
 }
 
-int conv_pw_set_attrs() {
-#define X(EK, AUX, PRE)                                                                                                                                   \
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pw_kernel<EK, AUX, PRE, false>), hipFuncAttributeMaxDynamicSharedMemorySize, PW_LDS)); \
-    PSG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pw_kernel<EK, AUX, PRE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PW_LDS));
-    PSG_PW_FOR_ALL(X)
-#undef X
-    return PSG_OK;
-}
-
-// tile counts and the persistent grid (resident slots, at most one per tile) of a launch conv_pw_applicable accepted
-void conv_pw_grid(const ConvP& p, int& mtiles, int& ntiles, int& grid) {
-    mtiles = p.M / 128; ntiles = p.N / 128;
-    const int total = mtiles * ntiles;
-    grid = 2 * avail_cus_for((double)total / 512.0);
-    if (grid > total) grid = total;
-    grid &= ~7;                                          // (a virtual block keeps its XCD: v and v + G agree mod 8)
-}
-
-int launch_conv_pw(const ConvP& p0, hipStream_t stream) {
-    ConvP p = p0;
-    int grid;
-    conv_pw_grid(p, p.mtiles, p.ntiles, grid);
-    const int total = p.mtiles * p.ntiles;
-    const int ek = pw_kind(p);
-    const bool aux = (p.dact_u || p.residual), pre = p.preact != nullptr;
-    const int64_t ldaux = p.dact_u ? p.lddact : p.ldres;
-    const uint32_t aux_bytes = aux ? (uint32_t)(((int64_t)p.M - 1) * ldaux * 2 + (int64_t)p.N * 2) : 0u;
-    const double abytes = ((double)p.M * p.Cin + (double)p.N * p.Cin + (double)p.M * p.N * (1.0 + (aux ? 1.0 : 0.0) + (pre ? 1.0 : 0.0))) * 2.0;
-    ProfScope prof(p.transposed ? PROF_CONV_DGRAD : PROF_CONV_FWD, 2.0 * (double)p.M * (double)p.N * (double)p.Cin, stream, abytes);
-    bool done = false;
-#define X(EK, AUX, PRE)                                                                                                    \
-    if (!done && ek == EK && aux == AUX && pre == PRE) {                                                                   \
-        if (p.transposed) hipLaunchKernelGGL((conv_pw_kernel<EK, AUX, PRE, true>), dim3(grid), dim3(256), PW_LDS, stream, p, total, aux_bytes); \
-        else hipLaunchKernelGGL((conv_pw_kernel<EK, AUX, PRE, false>), dim3(grid), dim3(256), PW_LDS, stream, p, total, aux_bytes);            \
-        done = true;                                                                                                       \
-    }
-    PSG_PW_FOR_ALL(X)
-#undef X
-    if (!done) return set_error(PSG_ERR_ARG, "conv_pw: no kernel for epilogue kind %d", ek);       // (conv_pw_applicable rules it out)
-    ++g_pw_launches;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "conv_pw launch");
-    return PSG_OK;
-}
-
 }  // namespace psg
-
-extern "C" {
-int psg_conv_set_pw(int on) { psg::g_pw_on = on ? 1 : 0; return PSG_OK; }
-int64_t psg_conv_pw_launches(void) { return psg::g_pw_launches; }
-}

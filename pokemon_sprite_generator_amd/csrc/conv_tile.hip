@@ -13,6 +13,19 @@ typedef bf16_t tile_t;
 #else
 typedef float tile_t;
 #endif
-template int launch_conv<tile_t, PSG_TILE_BM, PSG_TILE_BN>(const ConvP&, hipStream_t);
-template int set_conv_attrs<tile_t, PSG_TILE_BM, PSG_TILE_BN>();
+// What is built: the border-class form for bf16 modes 0 / 1, unsplit; the parity-class mode unsplit and not 160 wide (its tap
+// tables push a 160-wide kernel past the scalar register file - one layer, the first downsample's data gradient, runs
+// 128x128 instead); everything else of (MODE 0..3) x SPLITK x CLS.
+template <typename T, int BM, int BN, int MODE, bool SPLITK, bool CLS> constexpr ConvKernel conv_variant() {
+    if constexpr (CLS ? (sizeof(T) != 2 || MODE > 1 || SPLITK) : (MODE == 3 && (SPLITK || BN == 160))) return nullptr;
+    else return conv_gemm_kernel<T, BM, BN, MODE, SPLITK, CLS>;
+}
+template <typename T, int BM, int BN> const ConvKernels& conv_kernels() {
+#define PSG_MODE(M) {{conv_variant<T, BM, BN, M, false, false>(), conv_variant<T, BM, BN, M, false, true>()}, \
+                     {conv_variant<T, BM, BN, M, true, false>(), conv_variant<T, BM, BN, M, true, true>()}}
+    static const ConvKernels k = {{PSG_MODE(0), PSG_MODE(1), PSG_MODE(2), PSG_MODE(3)}, conv_splitk_finish_kernel<T>};
+#undef PSG_MODE
+    return k;
+}
+template const ConvKernels& conv_kernels<tile_t, PSG_TILE_BM, PSG_TILE_BN>();
 }  // namespace psg

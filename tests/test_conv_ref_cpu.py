@@ -76,6 +76,45 @@ def test_route_query_checks_what_the_launch_checks(lib):
     assert K.query_route(lib, cc)[1][0][3] == 1 and K.query_route(lib, dict(cc, tile=-1, ws="ok"))[1][0][3] > 1
 
 
+def test_workspace_query_is_the_split_of_the_route(lib):
+    """psg_conv_fwd_workspace_bytes and psg_conv_route plan through the same entry: with a workspace of any size offered, every
+    case (under its own settings) is routed with splits x M x N x 4 bytes of it when the route splits, and asks for 0 otherwise."""
+    bad = []
+    for c in K.CASES:
+        with K.settings(lib, c):
+            need = int(lib.psg_conv_fwd_workspace_bytes(C.byref(K.make_desc(c, K.FAKE_PTRS))))
+            rc, launches = K.route_of(lib, K.make_desc(c, K.FAKE_PTRS, 0x900000, 1 << 40))
+        assert rc == 0, c["name"]
+        L = [dict(zip(K.ROUTE_FIELDS, l)) for l in launches]
+        want = L[0]["splits"] * L[0]["M"] * c["Cout"] * 4 if L[0]["splits"] > 1 else 0
+        if need != want or any(l["splits"] != 1 for l in L[1:]) or (c["tile"] >= 0 and need):
+            bad.append(f"{c['name']}: workspace query {need}, route {[(l['splits'], l['M']) for l in L]} x Cout {c['Cout']}")
+    assert not bad, "\n".join(bad)
+    d = K.make_desc(K.CASES[0], K.FAKE_PTRS); d.Cin = 60
+    assert int(lib.psg_conv_fwd_workspace_bytes(C.byref(d))) == -1
+
+
+def test_combinations_without_a_kernel_are_an_error_of_the_plan(lib):
+    """No fp32 tile is 160 wide and no parity-class kernel is (candidates 3 and 4): pinned there, psg_conv_route returns PSG_ERR_ARG
+    in every gather mode, not a route.  There is no fp32 border-class kernel either: with psg_conv_set_tapclass(2) an fp32 launch
+    keeps the plain order - the setting forces the form only where it applies.  Smallest shapes of the mat.* cases."""
+    modes = {0: dict(H=3, W=5), 1: dict(H=3, W=5, tr=1), 2: dict(H=3, W=5), 3: dict(H=5, W=8, stride=2, tr=1)}
+    mk = lambda dn, mode, **kw: K._mk("nokernel", None, dtype=dn, B=3, Cin={"bf16": (64, 24), "f32": (32, 12)}[dn][mode == 2], Cout=12, ks=3,
+                                      **modes[mode], **kw)
+    for tile in (3, 4):
+        for mode in modes:
+            assert K.query_route(lib, mk("f32", mode, tile=tile))[0] == -6, (tile, mode)
+        assert K.query_route(lib, mk("bf16", 3, tile=tile))[0] == -6, tile
+        with K.settings(lib, mk("f32", 0, tile=tile)):             # (a pinned launch is never split: nothing to ask for)
+            assert int(lib.psg_conv_fwd_workspace_bytes(C.byref(K.make_desc(mk("f32", 0), K.FAKE_PTRS)))) == 0
+    for tile in (-1, 0, 1, 2):
+        for mode in (0, 1):
+            rc, launches = K.query_route(lib, mk("f32", mode, tile=tile, tapcls=2))
+            L = dict(zip(K.ROUTE_FIELDS, launches[0]))
+            assert rc == 0 and (L["mode"], L["tapcls"]) == (mode, 0), (tile, mode, L)
+            assert dict(zip(K.ROUTE_FIELDS, K.query_route(lib, mk("bf16", mode, tile=tile, tapcls=2))[1][0]))["tapcls"] == 1
+
+
 def test_case_shapes_are_tiny():
     for c in K.CASES:
         g = K.geom(c)

@@ -10,7 +10,7 @@ cd $ROOT/pokemon_sprite_generator_amd/csrc
 FL="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off"
 for A in "$@"; do
   D=$ROOT/build_abl/a$A; mkdir -p $D
-  for t in 128_128 128_64 64_64 128_160 64_160; do
+  for t in $(sed -n 's/^TILES := //p' Makefile | tr ' ' '\n' | sed -n 's/^bf16_//p'); do      # the Makefile's bf16 tiles
     bm=${t%_*}; bn=${t#*_}
     /opt/rocm/bin/hipcc $FL -DPSG_ABL=$A -DPSG_TILE_BF16=1 -DPSG_TILE_BM=$bm -DPSG_TILE_BN=$bn -c conv_tile.hip -o $D/conv_tile_bf16_$t.o &
   done
