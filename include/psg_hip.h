@@ -47,7 +47,8 @@ enum psg_status {
     PSG_ERR_ARG = -6
 };
 enum psg_dtype { PSG_F32 = 0, PSG_BF16 = 1 };
-enum psg_act { PSG_ACT_NONE = 0, PSG_ACT_SILU = 1, PSG_ACT_GELU = 2, PSG_ACT_RELU = 3, PSG_ACT_TANH = 4 };   /* RELU / TANH: the frozen VAE (vae_decoder.py:82-91,185) */
+enum psg_act { PSG_ACT_NONE = 0, PSG_ACT_SILU = 1, PSG_ACT_GELU = 2, PSG_ACT_RELU = 3, PSG_ACT_TANH = 4,   /* RELU / TANH: the frozen VAE (vae_decoder.py:82-91,185) */
+               PSG_ACT_QUICK_GELU = 5 };   /* x * sigmoid(1.702 x): both CLIP towers (transformers' `quick_gelu`, clip_loss.py:22); any other value is PSG_ERR_ARG */
 /* Bits of the device-side NaN/Inf flag word of one train step (the reference's five host-side
  * check_for_nans scans, improved_diffusion_trainer.py:353-393).  A step whose word has any bit of
  * PSG_FLAG_SKIP_MASK set is skipped like the reference's `continue`: no optimizer step, no scheduler
@@ -550,6 +551,53 @@ int psg_embed_scatter(const float* dz, int64_t lddz, const int64_t* key, const i
                       int N, int64_t V, int64_t skip_key, int accumulate, void* ws, int64_t ws_bytes, psg_stream_t stream);
 int64_t psg_embed_scatter_workspace_bytes(int64_t rows, int N);
 int psg_embed_scatter_chunk_rows(void);
+
+/* ---------------------------------------------------------------------------
+ * CLIP text-image alignment loss (clip.hip) - src/models/clip_loss.py: CLIPLoss.forward = CLIPProcessor + CLIPModel
+ * (openai/clip-vit-base-patch32, frozen) + -mean(cosine), the third term of stage 3's loss (final_trainer.py:469-473).
+ * The towers' GEMMs are psg_conv_fwd Linears (PSG_ACT_QUICK_GELU in the MLP), their norms psg_layernorm, the vision
+ * tower's attention psg_attn_fwd / psg_attn_bwd; these are the parts CLIP alone has.  No atomics; the same inputs give the
+ * same bits.
+ * ------------------------------------------------------------------------- */
+/* clip_loss.py:52,55 - `(image + 1) / 2` and CLIPProcessor(images=..., do_rescale=False) (transformers' CLIPImageProcessor:
+ * resize to `S` bicubically, centre crop, normalise) in one pass: img fp32 NCHW [B,3,Hi,Wi] -> y, the patch rows
+ * [B * (S/P)^2, 3*P*P] in `dtype` (row stride ldy >= 3*P*P): pixel (oy, ox) of channel c lands in row
+ * (b * S/P + oy/P) * S/P + ox/P, column c*P*P + (oy%P)*P + ox%P - the flattening of the patch embedding's
+ * Conv2d(3, width, P, stride=P, bias=False) weight (CLIPVisionEmbeddings.patch_embedding), so that embedding is one Linear.
+ *   v = a * img + b;  v = resize(v) when Hi != S (no resampling arithmetic at all otherwise);  y = (v - mean[c]) * inv_std[c]
+ * with CLIP's mean (0.48145466, 0.4578275, 0.40821073) and inv_std = fp32(1 / std), std = (0.26862954, 0.26130258, 0.27577711).
+ * The resize is the processor's FLOAT path, F.interpolate(mode='bicubic', align_corners=False, antialias=True): per axis the
+ * Keys cubic with a = -0.5 at (sample + 0.5 - centre), centre = (Hi/S)(o + 0.5), over the window
+ * [trunc(centre - 1.5), trunc(centre + 2.5)) clipped to the image (at most 4 samples), the weights renormalised to sum 1;
+ * no clamp, no quantisation.  Centre and weights are evaluated in fp64 and each weight rounded once (as psg_image_prep_fwd
+ * takes its source index), the taps are combined in fp32, rows first.  The processor's PIL path (through uint8, overshoot
+ * clipped; up to 0.41 away in normalised units on noise, not differentiable) is NOT reproduced.
+ * Only Hi == Wi <= S and S % P == 0: a non-square image needs the centre crop and a larger one the widened antialias window -
+ * PSG_ERR_SHAPE. */
+int psg_clip_prep_fwd(const float* img, void* y, int64_t ldy, int B, int Hi, int Wi, int S, int P, float a, float b,
+                      int dtype, psg_stream_t stream);
+/* Its backward as a gather: dimg (fp32 NCHW [B,3,Hi,Wi], every element written once) = (the forward's weights applied to the
+ * dy elements whose windows hold the pixel - a bounded set, about (4 S/Hi + 2)^2 outputs - summed in a fixed order (columns in
+ * chunks of 8, rows, columns of the chunk) in fp64 and rounded once; the one dy element when Hi == S) * inv_std[c] * a.  Nothing is clamped, so there is no mask and the
+ * image is not an operand. */
+int psg_clip_prep_bwd(const void* dy, int64_t lddy, float* dimg, int B, int Hi, int Wi, int S, int P, float a, int dtype,
+                      psg_stream_t stream);
+/* CLIPTextTransformer's causal self-attention (transformers modeling_clip.py: the causal mask of CLIPTextTransformer.forward
+ * inside CLIPAttention): psg_attn_fwd's operands and argument order, key s takes part for query l iff s <= l.  Padding
+ * follows the pooled EOS position, so no key lengths are needed.  Forward only: L == S <= 128, head_dim 16 / 32 / 64
+ * (PSG_ERR_SHAPE otherwise), drop_p must be 0 (PSG_ERR_ARG), seed is ignored, lse may be NULL.  q, k, v, o start on a
+ * 4-element boundary with row strides that are multiples of 4.  One workgroup per (sample, head): K / V staged once in LDS
+ * as fp32, one query row per lane, fp32 arithmetic with a running maximum; row 0 is v[0] itself.  Its own entry:
+ * psg_attn_fwd never routes here, psg_attn_route and psg_attn_path_counts do not know it. */
+int psg_attn_fwd_causal(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                        void* o, int64_t ldo, float* lse, int B, int heads, int L, int S, int d, float scale,
+                        float drop_p, uint64_t seed, int dtype, psg_stream_t stream);
+/* clip_loss.py:60-67: out[0] (fp32 device scalar) = -mean_b( normalize(u[b]) . normalize(v[b]) ) for u, v [B, D] in `dtype`
+ * (D and the row strides multiples of 4), F.normalize's x / max(||x||, 1e-12).  du (may be NULL; `dtype`, row stride lddu)
+ * = d out / d u = -(v^ / max(||u||, eps) - [||u|| > eps] cos u / ||u||^2) / B; v gets no gradient (the text side is a
+ * constant).  One pass in one workgroup, fp32 accumulation in a fixed order. */
+int psg_cosine_loss(const void* u, int64_t ldu, const void* v, int64_t ldv, void* du, int64_t lddu, float* out, int B,
+                    int D, int dtype, psg_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Optimizer side — improved_diffusion_trainer.py:399-413

@@ -16,11 +16,12 @@ from .inference import LatentGenerator, LinearNoiseScheduler, gradio_ddpm_sample
 from .vae import PokemonVAE, VAEDecoder, VAEEncoder
 from .text_encoder import TextEncoder
 from .losses import CombinedLoss, VGGPerceptualLoss
+from .clip_loss import CLIPLoss
 from .final import FinalPokemonGenerator, FinalStepper
 from .data import SpriteDataset, SpriteLoader, create_data_loaders, draw_params
 
 __all__ = ["UNet", "UNetBlock", "ResBlock", "CrossAttentionBlock", "TimestepEmbedding", "NoiseScheduler",
            "ImprovedDiffusionTrainer", "DiffusionTrainer", "DiffusionStepper", "FusedAdamW", "GradArena", "ParamArena",
-           "BucketedAllReduce", "LatentGenerator", "LinearNoiseScheduler", "gradio_ddpm_sample", "PokemonVAE", "VAEEncoder", "VAEDecoder", "TextEncoder", "VGGPerceptualLoss", "CombinedLoss",
+           "BucketedAllReduce", "LatentGenerator", "LinearNoiseScheduler", "gradio_ddpm_sample", "PokemonVAE", "VAEEncoder", "VAEDecoder", "TextEncoder", "VGGPerceptualLoss", "CombinedLoss", "CLIPLoss",
            "FinalPokemonGenerator", "FinalStepper", "SpriteDataset", "SpriteLoader", "create_data_loaders", "draw_params", "PsgError", "LIB_PATH"]
 __version__ = "0.1.0"

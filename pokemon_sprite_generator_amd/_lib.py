@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PSG_LIB_PATH") or os.path.join(_HERE, "libpsg_hip.so")   # override: A/B kernel builds in one GPU session
 
 PSG_F32, PSG_BF16 = 0, 1
-ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU, ACT_TANH = 0, 1, 2, 3, 4
+ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU, ACT_TANH, ACT_QUICK_GELU = 0, 1, 2, 3, 4, 5
 CONV_SAVE_DACT, CONV_DACT_MUL, CONV_GENERIC_EPILOGUE = 1, 2, 4          # enum psg_conv_flags
 # enum psg_flag: bits of the per-step NaN/Inf flag word
 FLAG_NOISY_BAD, FLAG_T_RANGE, FLAG_PRED_BAD, FLAG_LOSS_BAD, FLAG_FALLBACK, FLAG_INPUT_BAD, FLAG_SKIP_MASK = 1, 2, 4, 8, 16, 32, 47
@@ -124,6 +124,11 @@ SIGNATURES = {
     "psg_feat_l1_workspace_bytes": (c_int64, []),
     "psg_kl_f32": (c_int, [c_void_p] * 5 + [c_int64, c_void_p, c_int64, c_void_p]),
     "psg_kl_workspace_bytes": (c_int64, []),
+    "psg_clip_prep_fwd": (c_int, [c_void_p, c_void_p, c_int64] + [c_int] * 5 + [c_float, c_float, c_int, c_void_p]),
+    "psg_clip_prep_bwd": (c_int, [c_void_p, c_int64, c_void_p] + [c_int] * 5 + [c_float, c_int, c_void_p]),
+    "psg_attn_fwd_causal": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]
+                            + [c_int] * 5 + [c_float, c_float, c_uint64, c_int, c_void_p]),
+    "psg_cosine_loss": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p]),
     "psg_layernorm": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_float,
                               c_int, c_int, c_void_p]),
     "psg_layernorm_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,

@@ -281,6 +281,7 @@ static int conv_setup(const psg_conv_desc* d, ConvP& p) {
     PSG_REQUIRE(!d->preact || (aligned16(d->preact) && d->ld_preact % 4 == 0), PSG_ERR_ALIGN, "conv_fwd: preact alignment");
     PSG_REQUIRE(!d->dact_u || (aligned16(d->dact_u) && d->ld_dact % 4 == 0), PSG_ERR_ALIGN, "conv_fwd: dact_u alignment");
     PSG_REQUIRE(d->drop_p >= 0.f && d->drop_p < 1.f, PSG_ERR_ARG, "conv_fwd: drop_p %f", d->drop_p);
+    PSG_REQUIRE(d->act >= PSG_ACT_NONE && d->act <= PSG_ACT_QUICK_GELU, PSG_ERR_ARG, "conv_fwd: unknown act %d", d->act);
     PSG_REQUIRE(!(d->residual && d->dact_u), PSG_ERR_ARG, "conv_fwd: residual and dact_u are mutually exclusive");
     PSG_REQUIRE((d->flags & ~(PSG_CONV_SAVE_DACT | PSG_CONV_DACT_MUL | PSG_CONV_GENERIC_EPILOGUE)) == 0, PSG_ERR_ARG, "conv_fwd: unknown flags 0x%x", d->flags);
     PSG_REQUIRE(!(d->flags & PSG_CONV_SAVE_DACT) || (d->preact && !d->dact_u), PSG_ERR_ARG, "conv_fwd: SAVE_DACT needs preact (forward form)");

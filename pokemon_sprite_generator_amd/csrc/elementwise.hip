@@ -798,6 +798,7 @@ int psg_version(void) { return 100; }
 int psg_conv_init_attrs(void);   // conv_gemm.hip
 int psg_wgrad_init_attrs(void);  // wgrad.hip
 int psg_attn_init_attrs(void);   // attention.hip
+int psg_clip_init_attrs(void);   // clip.hip
 
 int psg_init(int device) {
     PSG_HIP_CHECK(hipSetDevice(device));
@@ -805,6 +806,7 @@ int psg_init(int device) {
     if ((rc = psg_conv_init_attrs()) != PSG_OK) return rc;
     if ((rc = psg_wgrad_init_attrs()) != PSG_OK) return rc;
     if ((rc = psg_attn_init_attrs()) != PSG_OK) return rc;
+    if ((rc = psg_clip_init_attrs()) != PSG_OK) return rc;
     return PSG_OK;
 }
 
@@ -1095,6 +1097,7 @@ int psg_dropout_apply(const void* x, int64_t ldx, void* y, int64_t ldy, int64_t 
 int psg_epilogue_bwd(const void* dy, int64_t lddy, const void* u, int64_t ldu, void* g, int64_t ldg, int64_t rows, int cols,
                      int act, float alpha, float drop_p, uint64_t seed, int dtype, psg_stream_t stream) {
     PSG_REQUIRE(dy && g && (u || act == PSG_ACT_NONE), PSG_ERR_ARG, "epilogue_bwd: null pointer");
+    PSG_REQUIRE(act >= PSG_ACT_NONE && act <= PSG_ACT_QUICK_GELU, PSG_ERR_ARG, "epilogue_bwd: unknown act %d", act);
     PSG_REQUIRE(rows > 0 && cols > 0 && (cols & 3) == 0 && ((lddy | ldg) & 3) == 0 && (!u || (ldu & 3) == 0) && drop_p >= 0.f && drop_p < 1.f,
                 PSG_ERR_SHAPE, "epilogue_bwd: bad shape");
     const int gr = grid_for(rows * (cols / 4), 256, 8192);

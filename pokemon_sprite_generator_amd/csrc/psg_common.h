@@ -155,6 +155,12 @@ __device__ __forceinline__ void gelu_both_fast(float x, float& y, float& dy) {
     y = x * cdf;
     dy = cdf + x * 0.39894228040143268f * e;
 }
+// quick-GELU x * sigmoid(1.702 x): the activation of both CLIP towers (transformers' `quick_gelu`)
+__device__ __forceinline__ float quick_gelu_f(float x) { return x * sigmoidf_(1.702f * x); }
+__device__ __forceinline__ float quick_gelu_grad(float x) {
+    const float s = sigmoidf_(1.702f * x);
+    return s * (1.0f + 1.702f * x * (1.0f - s));
+}
 // (value, derivative) of an activation; FAST selects the bf16-grade GELU above
 template <bool FAST>
 __device__ __forceinline__ void act_both(float x, int act, float& y, float& dy) {
@@ -171,14 +177,19 @@ __device__ __forceinline__ void act_both(float x, int act, float& y, float& dy) 
         y = fmaxf(x, 0.f); dy = x > 0.f ? 1.0f : 0.f;
     } else if (act == PSG_ACT_TANH) {
         y = tanhf(x); dy = 1.0f - y * y;
+    } else if (act == PSG_ACT_QUICK_GELU) {
+        const float s = sigmoidf_(1.702f * x);
+        y = x * s;
+        dy = s * (1.0f + 1.702f * x * (1.0f - s));
     } else { y = x; dy = 1.0f; }
 }
 __device__ __forceinline__ float act_f(float x, int act) {
-    return act == PSG_ACT_SILU ? silu_f(x) : (act == PSG_ACT_GELU ? gelu_f(x) : (act == PSG_ACT_RELU ? fmaxf(x, 0.f) : (act == PSG_ACT_TANH ? tanhf(x) : x)));
+    return act == PSG_ACT_SILU ? silu_f(x) : (act == PSG_ACT_GELU ? gelu_f(x) : (act == PSG_ACT_RELU ? fmaxf(x, 0.f) : (act == PSG_ACT_TANH ? tanhf(x) : (act == PSG_ACT_QUICK_GELU ? quick_gelu_f(x) : x))));
 }
 __device__ __forceinline__ float act_grad(float x, int act) {
     if (act == PSG_ACT_RELU) return x > 0.f ? 1.0f : 0.f;
     if (act == PSG_ACT_TANH) { const float t = tanhf(x); return 1.0f - t * t; }
+    if (act == PSG_ACT_QUICK_GELU) return quick_gelu_grad(x);
     return act == PSG_ACT_SILU ? silu_grad(x) : (act == PSG_ACT_GELU ? gelu_grad(x) : 1.0f);
 }
 

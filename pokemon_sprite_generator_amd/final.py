@@ -8,7 +8,8 @@
     backward, clip_grad_norm_(1.0), torch.optim step over the text encoder's requires_grad parameters.
 
 Built: the text-encoder phase.  Not built: the joint phase (`unfreeze_vae_decoder` / `unfreeze_unet` raise - there are no VAE
-weight gradients) and the CLIP loss model (`clip_loss` is an optional callable of the caller's).
+weight gradients).  `clip_loss` is an optional callable `(reconstruction, texts) -> scalar`: `clip_loss.CLIPLoss` is the
+reference's (final_trainer.py:469-473), with `texts` a list of descriptions or an int64 tensor of CLIP token ids.
 """
 from typing import Any, Callable, Dict, List, Optional
 

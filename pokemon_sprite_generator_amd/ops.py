@@ -13,10 +13,11 @@ import threading
 import torch
 
 from . import _lib
-from ._lib import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SILU, ConvDesc, WgradDesc, check, dtype_code, ptr, stream_ptr
+from ._lib import ACT_GELU, ACT_NONE, ACT_QUICK_GELU, ACT_RELU, ACT_SILU, ConvDesc, WgradDesc, check, dtype_code, ptr, stream_ptr
 
 __all__ = ["conv2d", "linear", "group_norm", "group_norm_split", "attention_self", "attention_cross", "attention_cross_longq",
-           "cross_in_proj", "upsample_bilinear", "nchw_to_nhwc", "nchw_to_nhwc_grad", "nhwc_to_nchw", "image_out", "recon_loss", "max_pool2x2", "image_prep", "feature_l1", "kl_loss", "text_pool", "timestep_sinusoid", "WeightCache", "ACT_NONE", "ACT_SILU", "ACT_GELU", "ACT_RELU"]
+           "cross_in_proj", "upsample_bilinear", "nchw_to_nhwc", "nchw_to_nhwc_grad", "nhwc_to_nchw", "image_out", "recon_loss", "max_pool2x2", "image_prep", "feature_l1", "kl_loss", "clip_prep", "attention_causal", "cosine_loss", "text_pool", "timestep_sinusoid", "WeightCache", "ACT_NONE", "ACT_SILU", "ACT_GELU", "ACT_RELU",
+           "ACT_QUICK_GELU"]
 
 
 def _lib_for(t):
@@ -1318,6 +1319,20 @@ def attention_cross(q, kv, heads, drop_p=0.0, seed=0):
     return _AttnFn.apply(q, kv, heads, drop_p, seed)
 
 
+def attention_causal(qkv, heads):
+    """Causal self-attention over packed qkv [B, L, 3E] (key s serves query l iff s <= l): psg_attn_fwd_causal, CLIP's text tower.
+    Forward only - the text side of the loss is a constant: a qkv that asks for a gradient is refused."""
+    if torch.is_grad_enabled() and qkv.requires_grad:
+        raise _lib.PsgError("attention_causal is forward only: run it under torch.no_grad()")
+    lib = _lib_for(qkv)
+    qr, _, io, dims, E = _attn_operands(qkv, None, heads)      # qr: the tensor behind io's raw addresses (a copy when qkv's
+    B, _, L, _, d = dims                                       # layout was irregular) - it must outlive the launch
+    o = torch.empty((B, L, E), dtype=qkv.dtype, device=qkv.device)
+    check(lib.psg_attn_fwd_causal(*io, ptr(o), E, None, *dims, float(d) ** -0.5, 0.0, 0, dtype_code(qkv.dtype), stream_ptr()),
+          "psg_attn_fwd_causal")
+    return o
+
+
 class _AttnLongQFn(torch.autograd.Function):
     """Cross-attention of very many queries over few keys (the VAE decoder's text attention): q [B,L,E], kv [B,S,2E], no
     dropout.  Forward: psg_attn_fwd, the launch of `attention_cross`; backward: psg_attn_bwd_longq."""
@@ -1561,6 +1576,73 @@ class _KLFn(torch.autograd.Function):
 def kl_loss(mu, logvar):
     """The KL term of CombinedLoss (mean over all latent elements) as an fp32 device scalar."""
     return _KLFn.apply(mu, logvar)[0]
+
+
+# ---------------------------------------------------------------------------
+# stage 3's CLIP loss around the two towers (src/models/clip_loss.py)
+# ---------------------------------------------------------------------------
+class _ClipPrepFn(torch.autograd.Function):
+    """fp32 NCHW image [B,3,H,H] -> the vision tower's patch rows [B, (size/patch)^2, 3*patch^2] in `dtype` (psg_clip_prep_fwd):
+    a img + b, antialiased bicubic resize to `size` if H differs, CLIP normalisation.  Nothing is saved: the pass is linear in
+    the image.  Backward: psg_clip_prep_bwd, a gather with the forward's weights."""
+
+    @staticmethod
+    def forward(ctx, img, a, b, size, patch, dtype):
+        lib = _lib_for(img)
+        if img.dim() != 4 or img.shape[1] != 3:
+            raise _lib.PsgError(f"clip_prep: expected a [B,3,H,W] image, got {tuple(img.shape)}")
+        x = img.detach().contiguous().float()
+        B, _, Hi, Wi = x.shape
+        size, patch = int(size), int(patch)
+        cols = 3 * patch * patch
+        y = torch.empty((B, (size // max(patch, 1)) ** 2, cols), dtype=dtype, device=x.device)
+        check(lib.psg_clip_prep_fwd(ptr(x), ptr(y), cols, B, Hi, Wi, size, patch, float(a), float(b), dtype_code(dtype), stream_ptr()),
+              "psg_clip_prep_fwd")
+        ctx.meta = (B, Hi, Wi, size, patch, float(a), tuple(img.shape))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, Hi, Wi, size, patch, a, shape = ctx.meta
+        lib = _lib_for(dy)
+        dyr, lddy = _rows(dy)
+        dimg = torch.empty((B, 3, Hi, Wi), dtype=torch.float32, device=dy.device)
+        check(lib.psg_clip_prep_bwd(ptr(dyr), lddy, ptr(dimg), B, Hi, Wi, size, patch, a, dtype_code(dy.dtype), stream_ptr()),
+              "psg_clip_prep_bwd")
+        return dimg.view(shape), None, None, None, None, None
+
+
+def clip_prep(img, size, patch, a=0.5, b=0.5, dtype=torch.float32):
+    """clip_loss.py:52,55 for the image in one pass (see _ClipPrepFn): square images no larger than `size`."""
+    return _ClipPrepFn.apply(img, a, b, size, patch, dtype)
+
+
+class _CosineLossFn(torch.autograd.Function):
+    """-mean_b(normalize(u[b]) . normalize(v[b])) of u, v [B, D] as an fp32 device tensor [1]: psg_cosine_loss.  The gradient
+    with respect to `u` is produced by the forward's own pass; `v` is a constant."""
+
+    @staticmethod
+    def forward(ctx, u, v):
+        lib = _lib_for(u)
+        if u.dim() != 2 or u.shape != v.shape or u.dtype != v.dtype:
+            raise _lib.PsgError(f"cosine_loss: {tuple(u.shape)} {u.dtype} and {tuple(v.shape)} {v.dtype} must be equal [B, D] operands")
+        ur, ldu = _rows(u)
+        vr, ldv = _rows(v.detach())
+        B, D = u.shape
+        du = torch.empty((B, D), dtype=u.dtype, device=u.device) if ctx.needs_input_grad[0] else None
+        out = torch.empty(1, dtype=torch.float32, device=u.device)
+        check(lib.psg_cosine_loss(ptr(ur), ldu, ptr(vr), ldv, ptr(du), D, ptr(out), B, D, dtype_code(u.dtype), stream_ptr()), "psg_cosine_loss")
+        ctx.du = du
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        return (ctx.du.float() * g[0]).to(ctx.du.dtype), None
+
+
+def cosine_loss(u, v):
+    """clip_loss.py:60-67: -(F.normalize(u) * F.normalize(v)).sum(-1).mean() as an fp32 device scalar; the gradient reaches `u` only."""
+    return _CosineLossFn.apply(u, v.detach())[0]
 
 
 # ---------------------------------------------------------------------------
