@@ -108,6 +108,11 @@ int psg_sampler_update_f32(float* x, const float* eps, const float* z, int mode,
 
 /* VAE reparameterisation, src/models/vae_decoder.py:120-123: out = mu + eps * exp(0.5 * logvar) (fp32, separately rounded). */
 int psg_reparam_f32(const float* mu, const float* logvar, const float* eps, float* out, int64_t n, psg_stream_t stream);
+/* Its backward (stage 1 trains the encoder through the sample, vae_decoder.py:120-123): dmu = dlatent,
+ * dlogvar = dlatent * eps * 0.5 * exp(0.5 * logvar); either output may be NULL; accumulate != 0 adds into what dmu / dlogvar
+ * hold. */
+int psg_reparam_bwd_f32(const float* dlatent, const float* logvar, const float* eps, float* dmu, float* dlogvar, int accumulate,
+                        int64_t n, psg_stream_t stream);
 
 /* SmoothL1Loss(beta) mean + its gradient — improved_diffusion_trainer.py:300,388,396.
  * loss_out: fp32 device scalar; grad (may be NULL) = dL/dpred * grad_scale.  Deterministic
@@ -399,6 +404,35 @@ int psg_conv_wgrad_route(const psg_wgrad_desc* d, int32_t* out);
 int psg_prep_weight(const void* w, int w_dtype, int w_layout, void* wf, void* wd, int O, int I, int ksize, int dtype,
                     psg_stream_t stream);
 int64_t psg_kpad(int64_t K, int dtype);
+
+/* ---------------------------------------------------------------------------
+ * Gradients of nn.Conv2d(kernel 4, stride 2, padding 1 or 2) - the three downsampling convolutions of the VAE encoder
+ * (src/models/vae_decoder.py:78-89), which stage 1 trains.  Channels-last row-strided operands in `dtype` (bf16 or fp32),
+ * fp32 accumulation; Cin and Cout multiples of 8, every pointer and row 16-byte aligned, Ho = (Hi + 2 pad - 4) / 2 + 1 (Wo
+ * alike).  Everything is validated on the host before a launch (PSG_ERR_ARG: null pointer, pad, cin_real, layout;
+ * PSG_ERR_DTYPE; PSG_ERR_SHAPE: geometry, channel counts, a leading dimension below the channel count; PSG_ERR_ALIGN;
+ * PSG_ERR_WORKSPACE).  The forward of these layers is psg_conv_fwd (ksize 4), unchanged.
+ * ------------------------------------------------------------------------- */
+/* Data gradient (src/models/vae_decoder.py:78-89).  g [B,Ho,Wo,Cout]: the gradient at the pre-activation; wd: the
+ * data-gradient weight of psg_prep_weight(..., ksize = 4), [Cin][psg_kpad(16 Cout)] with k = (kh, kw, co); dx [B,Hi,Wi,Cin]:
+ * every element is written, nothing is pre-zeroed.  Per parity class ((h+pad)&1, (w+pad)&1) of the input pixel a dense GEMM
+ * of K = 4 Cout (bf16: v_mfma_f32_16x16x32_bf16; fp32: v_mfma_f32_16x16x4_f32 on fp32 operands). */
+int psg_conv4s2_dgrad(const void* g, int64_t ldg, const void* wd, void* dx, int64_t lddx, int B, int Hi, int Wi, int Cin,
+                      int Ho, int Wo, int Cout, int pad, int dtype, psg_stream_t stream);
+/* Weight gradient (src/models/vae_decoder.py:78-89): dw[co,ci,kh,kw] = sum_{b,oh,ow} g[b,oh,ow,co] x[b,2oh-pad+kh,2ow-pad+kw,ci]
+ * into an fp32 master in psg_w_layout order, of which only the first cin_real <= Cin input channels exist (the image conv
+ * runs 3 channels padded to 8; its master is [32,3,4,4]); dbias (may be NULL) = column sums of g, from the same pass.
+ * accumulate / accumulate_bias != 0 add into what dw / dbias hold.  M = B Ho Wo is split into fp32 partial slabs in ws
+ * (>= psg_conv4s2_wgrad_workspace_bytes, 16-byte aligned), added in a fixed order by a second kernel: no atomics, bitwise
+ * reproducible.  The workspace query returns -1 (and sets psg_last_error) for arguments the launch would refuse. */
+int64_t psg_conv4s2_wgrad_workspace_bytes(int B, int Ho, int Wo, int Cin, int Cout, int dtype);
+int psg_conv4s2_wgrad(const void* x, int64_t ldx, const void* g, int64_t ldg, float* dw, int dw_layout, int cin_real,
+                      float* dbias, int B, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int pad, int accumulate,
+                      int accumulate_bias, int dtype, void* ws, int64_t ws_bytes, psg_stream_t stream);
+/* Split pin of psg_conv4s2_wgrad (src/models/vae_decoder.py:78-89 has no counterpart: a test hook like
+ * psg_conv_wgrad_set_splits): n > 0 asks for n slabs of whole 16-row steps (the launch gets ceil(M / rows per slab) of
+ * them); 0 returns the choice to the plan. */
+int psg_conv4s2_wgrad_set_splits(int n);
 
 /* Column sums: out[g, c] = sum_{r<R} a[(g*R + r), c] for g<groups.  groups=1 gives a bias
  * gradient (fp32 out); groups=B, R=HW gives the gradient of the per-sample rowadd.  out_dtype

@@ -92,6 +92,12 @@ SIGNATURES = {
     "psg_conv_wgrad_route": (c_int, [C.POINTER(WgradDesc), c_void_p]),
     "psg_prep_weight": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "psg_kpad": (c_int64, [c_int64, c_int]),
+    "psg_conv4s2_dgrad": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64] + [c_int] * 9 + [c_void_p]),
+    "psg_conv4s2_wgrad_workspace_bytes": (c_int64, [c_int] * 6),
+    "psg_conv4s2_wgrad": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p] + [c_int] * 11
+                          + [c_void_p, c_int64, c_void_p]),
+    "psg_conv4s2_wgrad_set_splits": (c_int, [c_int]),
+    "psg_reparam_bwd_f32": (c_int, [c_void_p] * 5 + [c_int, c_int64, c_void_p]),
     "psg_colsum": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "psg_colsum_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),
     "psg_epilogue_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_float, c_float,

@@ -866,6 +866,28 @@ int psg_reparam_f32(const float* mu, const float* logvar, const float* eps, floa
     return PSG_OK;
 }
 
+__global__ void reparam_bwd_kernel(const float* __restrict__ dlat, const float* __restrict__ logvar, const float* __restrict__ eps,
+                                   float* __restrict__ dmu, float* __restrict__ dlogvar, int accumulate, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float d = dlat[i];
+        if (dmu) dmu[i] = accumulate ? __fadd_rn(dmu[i], d) : d;
+        if (dlogvar) {
+            const float v = __fmul_rn(__fmul_rn(d, eps[i]), __fmul_rn(0.5f, expf(__fmul_rn(0.5f, logvar[i]))));
+            dlogvar[i] = accumulate ? __fadd_rn(dlogvar[i], v) : v;
+        }
+    }
+}
+
+int psg_reparam_bwd_f32(const float* dlatent, const float* logvar, const float* eps, float* dmu, float* dlogvar, int accumulate,
+                        int64_t n, psg_stream_t stream) {
+    PSG_REQUIRE(dlatent && (dmu || dlogvar) && (!dlogvar || (logvar && eps)), PSG_ERR_ARG, "reparam_bwd: null pointer");
+    if (n <= 0) return PSG_OK;
+    hipLaunchKernelGGL(reparam_bwd_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, dlatent, logvar, eps, dmu, dlogvar,
+                       accumulate, n);
+    PSG_LAUNCH_CHECK("reparam_bwd");
+    return PSG_OK;
+}
+
 int64_t psg_reduce_workspace_bytes(void) { return (int64_t)RED_BLOCKS * sizeof(float); }
 
 int psg_smooth_l1_f32(const float* pred, const float* target, float* grad, float* loss_out, int32_t* nan_flag,

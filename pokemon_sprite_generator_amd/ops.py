@@ -15,7 +15,7 @@ import torch
 from . import _lib
 from ._lib import ACT_GELU, ACT_NONE, ACT_QUICK_GELU, ACT_RELU, ACT_SILU, ConvDesc, WgradDesc, check, dtype_code, ptr, stream_ptr
 
-__all__ = ["conv2d", "linear", "group_norm", "group_norm_split", "attention_self", "attention_cross", "attention_cross_longq",
+__all__ = ["conv2d", "conv4s2_relu", "reparam", "linear", "group_norm", "group_norm_split", "attention_self", "attention_cross", "attention_cross_longq",
            "cross_in_proj", "upsample_bilinear", "nchw_to_nhwc", "nchw_to_nhwc_grad", "nhwc_to_nchw", "image_out", "recon_loss", "max_pool2x2", "image_prep", "feature_l1", "kl_loss", "clip_prep", "attention_causal", "cosine_loss", "text_pool", "timestep_sinusoid", "WeightCache", "ACT_NONE", "ACT_SILU", "ACT_GELU", "ACT_RELU",
            "ACT_QUICK_GELU"]
 
@@ -720,6 +720,123 @@ def conv2d(x, weight, bias=None, stride=1, rowadd=None, residual=None, act=ACT_N
 def linear(x, weight, bias=None, residual=None, act=ACT_NONE, alpha=1.0, drop_p=0.0, seed=0, out=None):
     """x: [..., Cin]; weight: fp32 [Cout, Cin] parameter.  nn.Linear of unet.py, with the fused epilogue."""
     return _ConvFn.apply(x, weight, bias, None, residual, 1, act, alpha, drop_p, seed, out)
+
+
+def _prepared_4s2(cache, key, weight, dtype, pad_in, need_wd):
+    """(wf, wd) of a trainable 4x4 stride-2 conv weight: `prep_weight`'s forward operand and, when asked, the data-gradient
+    operand [Cin][Kpad(16 Cout)]; kept in `cache` until the parameter's version counter or WeightCache.epoch moves."""
+    stamp = (weight.data_ptr(), weight._version, WeightCache.epoch)
+    ent = cache.get(key)
+    if ent is None or ent[0] != stamp or (need_wd and ent[2] is None):
+        ent = (stamp,) + prep_weight(weight, dtype, pad_in=pad_in, with_wd=bool(need_wd))
+        cache[key] = ent
+    return ent[1], ent[2]
+
+
+class _Conv4s2Fn(torch.autograd.Function):
+    """y = relu(conv(x, W, kernel 4, stride 2, pad 1 | 2) + bias) - the VAE encoder's downsampling convolutions
+    (vae_decoder.py:78-89).  Forward: psg_conv_fwd, the frozen encoder's launch.  Backward: psg_epilogue_bwd on the SAVED
+    OUTPUT ([y > 0] is [u > 0] for ReLU: no pre-activation is kept), psg_conv4s2_dgrad (skipped when x needs no gradient: the
+    image conv) and psg_conv4s2_wgrad (weight + bias gradient in one pass, delivered like `_deliver_gemm_grads`).  x may
+    carry more channels than the weight (the image's 3 in 8 columns): the extra ones are zero and get no weight gradient."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, pad, cache, key):
+        lib = _lib_for(x)
+        dtype = x.dtype
+        Cout, cin_real = weight.shape[0], weight.shape[1]
+        Cin = x.shape[-1]
+        if weight.dim() != 4 or weight.shape[2] != 4 or weight.shape[3] != 4 or Cin < cin_real:
+            raise _lib.PsgError(f"conv4s2_relu: weight {tuple(weight.shape)} on an input of {Cin} channels")
+        xr, ldx = _rows(x)
+        geom = _conv_geom(x, 4, 2, pad)
+        wf, wd = _prepared_4s2(cache, key, weight, dtype, Cin - cin_real, ctx.needs_input_grad[0])
+        y = torch.empty((geom[0], geom[3], geom[4], Cout), dtype=dtype, device=x.device)
+        _conv_launch(lib, dtype, xr, ldx, wf, 0, y, Cout, geom, Cin, Cout, bias=bias, act=ACT_RELU)
+        ctx.save_for_backward(xr, y)
+        ctx.weight_param, ctx.bias_param = weight, bias
+        ctx.meta = (geom, Cin, cin_real, Cout, ldx, tuple(x.shape), wd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xr, y = ctx.saved_tensors
+        geom, Cin, cin_real, Cout, ldx, x_shape, wd = ctx.meta
+        B, Hi, Wi, Ho, Wo, _, _, pad = geom
+        weight, bias = ctx.weight_param, ctx.bias_param
+        lib = _lib_for(dy)
+        dtype = dy.dtype
+        code = dtype_code(dtype)
+        dyr, lddy = _rows(dy)
+        M = B * Ho * Wo
+        g = torch.empty((M, Cout), dtype=dtype, device=dy.device)
+        check(lib.psg_epilogue_bwd(ptr(dyr), lddy, ptr(y), Cout, ptr(g), Cout, M, Cout, ACT_RELU, 1.0, 0.0, 0, code, stream_ptr()),
+              "psg_epilogue_bwd")
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(x_shape, dtype=dtype, device=dy.device)
+            check(lib.psg_conv4s2_dgrad(ptr(g), Cout, ptr(wd), ptr(dx), Cin, B, Hi, Wi, Cin, Ho, Wo, Cout, pad, code, stream_ptr()),
+                  "psg_conv4s2_dgrad")
+        want_w, want_b = ctx.needs_input_grad[1], bias is not None and ctx.needs_input_grad[2]
+        bo, bacc, be = _param_out(bias) if want_b else (None, False, None)
+        if want_w:
+            wo, wacc, we = _param_out(weight)
+            layout, out = weight_layout(wo), wo
+            if layout is None:                       # exotic strides: compute contiguous, copy back
+                out, layout = torch.empty(wo.shape, dtype=wo.dtype, device=wo.device), W_OIHW
+                if wacc:
+                    out.copy_(wo)
+            need = lib.psg_conv4s2_wgrad_workspace_bytes(B, Ho, Wo, Cin, Cout, code)
+            if need < 0:
+                check(-1, "psg_conv4s2_wgrad_workspace_bytes")
+            ws = _lib.workspace(need, dy.device)
+            check(lib.psg_conv4s2_wgrad(ptr(xr), ldx, ptr(g), Cout, ptr(out), layout, cin_real, ptr(bo), B, Hi, Wi, Cin, Ho, Wo, Cout, pad,
+                                        int(wacc), int(bacc), code, ptr(ws), ws.numel(), stream_ptr()), "psg_conv4s2_wgrad")
+            if out is not wo:
+                wo.copy_(out)
+            dw = _param_ret(wo, we)
+        elif want_b:                                 # (frozen weight, trainable bias)
+            _colsum(lib, g, Cout, M, 1, Cout, dtype, torch.float32, out=bo, accumulate=bacc)
+        if want_b:
+            db = _param_ret(bo, be)
+        return dx, dw, db, None, None, None
+
+
+def conv4s2_relu(x, weight, bias, pad, cache, key):
+    """relu(nn.Conv2d(kernel_size=4, stride=2, padding=pad)(x)) on channels-last x [B,H,W,Cin >= weight's]; weight: the fp32
+    OIHW parameter.  `cache` / `key`: where the caller keeps the prepared operands (see `_prepared_4s2`)."""
+    return _Conv4s2Fn.apply(x, weight, bias, pad, cache, key)
+
+
+class _ReparamFn(torch.autograd.Function):
+    """latent = mu + eps * exp(0.5 logvar) in fp32 (psg_reparam_f32, vae_decoder.py:120-123); backward: psg_reparam_bwd_f32."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, eps):
+        lib = _lib_for(mu)
+        if mu.shape != logvar.shape or mu.shape != eps.shape:
+            raise _lib.PsgError(f"reparam: shapes {tuple(mu.shape)}, {tuple(logvar.shape)}, {tuple(eps.shape)} differ")
+        m, lv, e = mu.detach().contiguous().float(), logvar.detach().contiguous().float(), eps.detach().contiguous().float()
+        out = torch.empty_like(m)
+        check(lib.psg_reparam_f32(ptr(m), ptr(lv), ptr(e), ptr(out), m.numel(), stream_ptr()), "psg_reparam_f32")
+        ctx.save_for_backward(lv, e)
+        return out
+
+    @staticmethod
+    def backward(ctx, dlat):
+        lv, e = ctx.saved_tensors
+        lib = _lib_for(dlat)
+        d = dlat.contiguous().float()
+        dmu = torch.empty_like(lv) if ctx.needs_input_grad[0] else None
+        dlv = torch.empty_like(lv) if ctx.needs_input_grad[1] else None
+        if dmu is not None or dlv is not None:
+            check(lib.psg_reparam_bwd_f32(ptr(d), ptr(lv), ptr(e), ptr(dmu), ptr(dlv), 0, d.numel(), stream_ptr()), "psg_reparam_bwd_f32")
+        return dmu, dlv, None
+
+
+def reparam(mu, logvar, eps):
+    """The VAE's reparameterised sample mu + eps * exp(0.5 logvar) (fp32), differentiable in mu and logvar."""
+    return _ReparamFn.apply(mu, logvar, eps)
 
 
 class _QKVFn(torch.autograd.Function):
@@ -1429,8 +1546,9 @@ def conv_infer(x, wf, bias, Cin, Cout, ks=1, stride=1, pad=0, act=ACT_NONE, resi
     return y
 
 
-def prep_weight(w, dtype, pad_in=0, pad_out=0):
-    """fp32 OIHW parameter -> prepared forward weight [O'][Kpad] in `dtype`; optional zero padding of Cin / Cout."""
+def prep_weight(w, dtype, pad_in=0, pad_out=0, with_wd=None):
+    """fp32 OIHW parameter -> prepared forward weight [O'][Kpad] in `dtype`; optional zero padding of Cin / Cout.
+    `with_wd` given (True / False): returns (wf, wd), wd the data-gradient operand [I'][Kpad'] from the same launch or None."""
     lib = _lib_for(w)
     O, I, kh, kw = w.shape
     src = w.detach().float()
@@ -1441,9 +1559,10 @@ def prep_weight(w, dtype, pad_in=0, pad_out=0):
     code = dtype_code(dtype)
     kp = lib.psg_kpad(kh * kw * I, code)
     wf = torch.empty((O, kp), dtype=dtype, device=w.device)
-    check(lib.psg_prep_weight(ptr(src), dtype_code(torch.float32), W_OHWI, ptr(wf), None, O, I, kh, code, stream_ptr()),
+    wd = torch.empty((I, lib.psg_kpad(kh * kw * O, code)), dtype=dtype, device=w.device) if with_wd else None
+    check(lib.psg_prep_weight(ptr(src), dtype_code(torch.float32), W_OHWI, ptr(wf), ptr(wd), O, I, kh, code, stream_ptr()),
           "psg_prep_weight")
-    return wf
+    return wf if with_wd is None else (wf, wd)
 
 
 

@@ -1,10 +1,19 @@
-"""Frozen VAE encoder / decoder on the MI355X kernels (reference: src/models/vae_decoder.py).
+"""VAE encoder / decoder on the MI355X kernels (reference: src/models/vae_decoder.py).
 
 The VAE sits either side of the U-Net path: stage 2 encodes every image batch with the FROZEN encoder before the train
 step (improved_diffusion_trainer.py:198-208,357-358) and decodes sampled latents for monitoring (:598); stage 3 and the
-demo decode with it.  Its parameters are never trained here (they are containers with the reference's names and shapes, so
-`load_state_dict` takes a stage-1 checkpoint's 'vae_state_dict' halves unchanged), and the encoder runs under
-`torch.no_grad()`.  The DECODER is differentiable with respect to its inputs: stage 3 trains the text encoder through it
+demo decode with it.  By default its parameters are never trained here (they are containers with the reference's names and
+shapes, so `load_state_dict` takes a stage-1 checkpoint's 'vae_state_dict' halves unchanged), and the encoder runs under
+`torch.no_grad()`.
+
+What is trainable: the ENCODER, opt-in.  `VAEEncoder(..., trainable=True)` has parameters that require grad and, with grad mode
+on, runs the autograd nodes of `ops`: `ops.conv4s2_relu` for the three 4x4 stride-2 convolutions (psg_conv4s2_dgrad /
+psg_conv4s2_wgrad, csrc/conv4s2.hip), `ResNetBlock.nhwc_grad`, `ops.conv2d` for the mu / logvar projections and `ops.reparam`
+for the sample - gradients reach all 70 of its parameters (stage 1, src/training/vae_trainer.py).  What is still missing:
+the DECODER's weight gradients (a decoder with a trainable parameter raises, `_require_frozen`), the stage-1 stepper (two
+learning rates, two clip norms, KL annealing) and the joint phase of stage 3.
+
+The DECODER is differentiable with respect to its inputs: stage 3 trains the text encoder through it
 (final_trainer.py:215-236), so when grad mode is on and `text_emb` or `latent` requires grad, `VAEDecoder.forward` runs the
 autograd nodes of `ops` (data gradients only; the cross-attention backward is psg_attn_bwd_longq).  Every other call runs the
 inference launches, unchanged.
@@ -145,9 +154,10 @@ class VAEEncoder(nn.Module):
     """vae_decoder.py:68-125: 215 -> 107 -> 53 -> 27 by three 4x4 stride-2 convolutions (+ReLU, ResNetBlock), four more
     ResNetBlocks up to 512 channels, mu / logvar 3x3 projections, reparameterised sample."""
 
-    def __init__(self, input_channels: int = 3, latent_dim: int = 8, compute_dtype: torch.dtype = torch.float32):
+    def __init__(self, input_channels: int = 3, latent_dim: int = 8, compute_dtype: torch.dtype = torch.float32, trainable: bool = False):
         super().__init__()
         self.latent_dim = latent_dim
+        self.trainable = bool(trainable)
         self.encoder = nn.Sequential(
             nn.Conv2d(input_channels, 32, kernel_size=4, stride=2, padding=1), nn.ReLU(), ResNetBlock(32, 32),
             nn.Conv2d(32, 64, kernel_size=4, stride=2, padding=1), nn.ReLU(), ResNetBlock(64, 64),
@@ -158,14 +168,54 @@ class VAEEncoder(nn.Module):
         self.logvar_proj = nn.Conv2d(512, latent_dim, kernel_size=3, padding=1)
         self.compute_dtype = compute_dtype
         self._cache = {}
+        self._epoch = ops.WeightCache.epoch
+        for p in self.parameters():                  # frozen unless asked: gradients exist only on the trainable path
+            p.requires_grad_(self.trainable)
 
-    @torch.no_grad()
     def forward(self, x: torch.Tensor, eps: torch.Tensor = None, generator: torch.Generator = None):
         """x [B,3,H,W] -> (latent, mu, logvar), each [B,latent_dim,h,w] fp32 (215 -> 27).  `eps` (default: randn of mu's
         shape, from `generator` when given - a data-parallel rank's own stream) is the reparameterisation noise the
-        reference draws with randn_like (:121)."""
+        reference draws with randn_like (:121).  A `trainable` encoder called with grad mode on runs the autograd nodes of
+        `ops` and its outputs carry gradients to all its parameters; every other call runs the inference launches."""
         if not x.is_cuda:
             raise _lib.PsgError("VAEEncoder (MI355X build) needs GPU tensors; there is no CPU fallback")
+        if self.trainable and torch.is_grad_enabled():
+            return self._forward_train(x, eps, generator)
+        with torch.no_grad():
+            return self._forward_infer(x, eps, generator)
+
+    def _draw_eps(self, mu, eps, generator):
+        if eps is None:
+            eps = torch.randn_like(mu) if generator is None else torch.randn(mu.shape, dtype=mu.dtype, device=mu.device, generator=generator)
+        return eps.detach().to(device=mu.device, dtype=torch.float32).contiguous()
+
+    def _forward_train(self, x, eps, generator):
+        """The encoder on the autograd nodes of `ops` (stage 1, vae_trainer.py): the three 4x4 stride-2 convolutions are
+        `ops.conv4s2_relu` (own gradient kernels), everything else the nodes the decoder and the U-Net already use."""
+        if x.requires_grad:
+            raise _lib.PsgError("VAEEncoder: the image has requires_grad=True, but nothing differentiates with respect to the image "
+                                "(the first convolution's data gradient is never computed); detach it")
+        dt = self.compute_dtype
+        Cin = x.shape[1]
+        cpad = (-Cin) % 8
+        h = ops.nchw_to_nhwc(x, dt, width=Cin + cpad)
+        for i, m in enumerate(self.encoder):
+            if isinstance(m, nn.Conv2d):
+                h = ops.conv4s2_relu(h, m.weight, m.bias, m.padding[0], self._cache, (i, dt, "train"))
+            elif isinstance(m, ResNetBlock):
+                h = m.nhwc_grad(h)               # (called directly: ResNetBlock.forward guards its own, frozen, entry)
+        mu = ops.nhwc_to_nchw(ops.conv2d(h, self.mu_proj.weight, self.mu_proj.bias))
+        logvar = ops.nhwc_to_nchw(ops.conv2d(h, self.logvar_proj.weight, self.logvar_proj.bias))
+        return ops.reparam(mu, logvar, self._draw_eps(mu, eps, generator)), mu, logvar
+
+    def _forward_infer(self, x, eps, generator):
+        if self.trainable and self._epoch != ops.WeightCache.epoch:
+            # an optimizer wrote the parameters through raw pointers (WeightCache.invalidate): version counters did not move
+            self._cache.clear()
+            for m in self.encoder:
+                if isinstance(m, ResNetBlock):
+                    m._cache.clear()
+            self._epoch = ops.WeightCache.epoch
         dt = self.compute_dtype
         Cin = x.shape[1]
         # image -> channels-last with the channel count padded to one 16-byte chunk (zeros; the weights are padded alike)
