@@ -5,170 +5,131 @@ to run an op raises (``load()``), it never reroutes to a CPU or eager path.
 """
 import ctypes as C
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PSG_LIB_PATH") or os.path.join(_HERE, "libpsg_hip.so")   # override: A/B kernel builds in one GPU session
-
-PSG_F32, PSG_BF16 = 0, 1
-ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU, ACT_TANH, ACT_QUICK_GELU = 0, 1, 2, 3, 4, 5
-CONV_SAVE_DACT, CONV_DACT_MUL, CONV_GENERIC_EPILOGUE = 1, 2, 4          # enum psg_conv_flags
-# enum psg_flag: bits of the per-step NaN/Inf flag word
-FLAG_NOISY_BAD, FLAG_T_RANGE, FLAG_PRED_BAD, FLAG_LOSS_BAD, FLAG_FALLBACK, FLAG_INPUT_BAD, FLAG_SKIP_MASK = 1, 2, 4, 8, 16, 32, 47
-
-c_void_p, c_int, c_int64, c_float, c_uint64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64
-
-
-class ConvDesc(C.Structure):
-    """struct psg_conv_desc (include/psg_hip.h)."""
-    _fields_ = [
-        ("dtype", C.c_int32), ("B", C.c_int32), ("Hi", C.c_int32), ("Wi", C.c_int32), ("Cin", C.c_int32),
-        ("Ho", C.c_int32), ("Wo", C.c_int32), ("Cout", C.c_int32),
-        ("ksize", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32),
-        ("transposed", C.c_int32), ("act", C.c_int32),
-        ("alpha", C.c_float), ("drop_p", C.c_float), ("flags", C.c_int32), ("drop_seed", C.c_uint64),
-        ("ldx", C.c_int64), ("ldy", C.c_int64), ("ld_rowadd", C.c_int64), ("ld_residual", C.c_int64),
-        ("ld_preact", C.c_int64), ("ld_dact", C.c_int64), ("ldw", C.c_int64),
-        ("x", c_void_p), ("w", c_void_p), ("y", c_void_p), ("bias", c_void_p), ("rowadd", c_void_p),
-        ("residual", c_void_p), ("preact", c_void_p), ("dact_u", c_void_p),
-        ("ws", c_void_p), ("ws_bytes", C.c_int64),
-    ]
-
-
-class WgradDesc(C.Structure):
-    """struct psg_wgrad_desc (include/psg_hip.h)."""
-    _fields_ = [
-        ("dtype", C.c_int32), ("B", C.c_int32), ("Hi", C.c_int32), ("Wi", C.c_int32), ("Cin", C.c_int32),
-        ("Ho", C.c_int32), ("Wo", C.c_int32), ("Cout", C.c_int32),
-        ("ksize", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32), ("accumulate", C.c_int32),
-        ("dw_layout", C.c_int32), ("accumulate_bias", C.c_int32), ("scale", C.c_float), ("reserved1", C.c_int32),
-        ("ldx", C.c_int64), ("lddy", C.c_int64),
-        ("x", c_void_p), ("dy", c_void_p), ("dw", c_void_p), ("dbias", c_void_p), ("ws", c_void_p), ("ws_bytes", C.c_int64),
-    ]
-
-
-# name -> (restype, argtypes); every symbol include/psg_hip.h declares
-SIGNATURES = {
-    "psg_last_error": (C.c_char_p, []),
-    "psg_version": (c_int, []),
-    "psg_init": (c_int, [c_int]),
-    "psg_noise_add_f32": (c_int, [c_void_p] * 7 + [c_int64, c_int64, c_int, c_int, c_void_p]),
-    "psg_noise_fallback_f32": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_void_p]),
-    "psg_ddpm_update_f32": (c_int, [c_void_p] * 7 + [c_int64, c_void_p]),
-    "psg_sampler_update_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int] + [c_float] * 4 + [c_int64, c_void_p]),
-    "psg_reparam_f32": (c_int, [c_void_p] * 4 + [c_int64, c_void_p]),
-    "psg_smooth_l1_f32": (c_int, [c_void_p] * 5 + [c_float, c_float, c_int64, c_void_p, c_void_p]),
-    "psg_reduce_workspace_bytes": (c_int64, []),
-    "psg_nchw_to_nhwc": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
-    "psg_nhwc_to_nchw": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "psg_text_pool": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "psg_timestep_sinusoid": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
-    "psg_upsample_bilinear_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64] + [c_int] * 7 + [c_void_p]),
-    "psg_upsample_bilinear_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64] + [c_int] * 7 + [c_void_p]),
-    "psg_add": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p]),
-    "psg_set_seed_source": (c_int, [c_void_p]),
-    "psg_sum_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p]),
-    "psg_groupnorm_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64] + [c_void_p] * 4 + [c_int] * 4 + [c_float, c_int, c_int, c_void_p, c_void_p]),
-    "psg_groupnorm_fwd_workspace_bytes": (c_int64, [c_int, c_int]),
-    "psg_groupnorm_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64] + [c_void_p] * 4 + [c_void_p, c_int64, c_void_p, c_void_p]
-                          + [c_int] * 7 + [c_void_p, c_void_p]),
-    "psg_groupnorm_bwd_res": (c_int, [c_void_p, c_int64, c_void_p, c_int64] + [c_void_p] * 4 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]
-                              + [c_int] * 7 + [c_void_p, c_void_p]),
-    "psg_groupnorm_bwd_workspace_bytes": (c_int64, [c_int, c_int]),
-    "psg_groupnorm_route": (c_int, [c_int] * 7 + [c_void_p]),
-    "psg_conv_fwd": (c_int, [C.POINTER(ConvDesc), c_void_p]),
-    "psg_conv_fwd_workspace_bytes": (c_int64, [C.POINTER(ConvDesc)]),
-    "psg_conv_set_pw": (c_int, [c_int]),
-    "psg_conv_pw_launches": (c_int64, []),
-    "psg_conv_set_tapclass": (c_int, [c_int]),
-    "psg_conv_tapclass_launches": (c_int64, []),
-    "psg_conv_set_tile": (c_int, [c_int]),
-    "psg_conv_route": (c_int, [C.POINTER(ConvDesc), c_void_p]),
-    "psg_conv_wgrad": (c_int, [C.POINTER(WgradDesc), c_void_p]),
-    "psg_conv_wgrad_workspace_bytes": (c_int64, [C.POINTER(WgradDesc)]),
-    "psg_conv_wgrad_set_variant": (c_int, [c_int]),
-    "psg_conv_wgrad_set_splits": (c_int, [c_int]),
-    "psg_conv_wgrad_route": (c_int, [C.POINTER(WgradDesc), c_void_p]),
-    "psg_prep_weight": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "psg_kpad": (c_int64, [c_int64, c_int]),
-    "psg_conv4s2_dgrad": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64] + [c_int] * 9 + [c_void_p]),
-    "psg_conv4s2_wgrad_workspace_bytes": (c_int64, [c_int] * 6),
-    "psg_conv4s2_wgrad": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p] + [c_int] * 11
-                          + [c_void_p, c_int64, c_void_p]),
-    "psg_conv4s2_wgrad_set_splits": (c_int, [c_int]),
-    "psg_reparam_bwd_f32": (c_int, [c_void_p] * 5 + [c_int, c_int64, c_void_p]),
-    "psg_colsum": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
-    "psg_colsum_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),
-    "psg_epilogue_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_float, c_float,
-                                 c_uint64, c_int, c_void_p]),
-    "psg_dropout_apply": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_float, c_uint64, c_float, c_int, c_void_p]),
-    "psg_attn_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]
-                     + [c_int] * 5 + [c_float, c_float, c_uint64, c_int, c_void_p]),
-    "psg_attn_fwd_varlen": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]
-                            + [c_int] * 5 + [c_float, c_float, c_uint64, c_int, c_void_p, c_void_p]),
-    "psg_attn_fwd_varlen_train": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]
-                                  + [c_int] * 5 + [c_float, c_float, c_uint64, c_int, c_void_p, c_void_p]),
-    "psg_attn_bwd_varlen": (c_int, [c_void_p, c_int64] * 5 + [c_void_p, c_void_p] + [c_void_p, c_int64] * 3
-                            + [c_int] * 5 + [c_float, c_float, c_uint64, c_int, c_void_p, c_void_p]),
-    "psg_attn_path_counts": (c_int, [c_void_p, c_void_p, c_void_p]),
-    "psg_attn_set_paths": (c_int, [c_int]),
-    "psg_attn_route": (c_int, [c_int] * 7 + [c_int64] * 5 + [c_int, c_void_p]),
-    "psg_attn_bwd": (c_int, [c_void_p, c_int64] * 5 + [c_void_p, c_void_p] + [c_void_p, c_int64] * 3
-                     + [c_int] * 5 + [c_float, c_float, c_uint64, c_int, c_void_p]),
-    "psg_attn_bwd_longq": (c_int, [c_void_p, c_int64] * 5 + [c_void_p, c_void_p] + [c_void_p, c_int64] * 3
-                           + [c_int] * 5 + [c_float, c_float, c_uint64, c_int, c_void_p, c_int64, c_void_p]),
-    "psg_attn_bwd_longq_workspace_bytes": (c_int64, [c_int] * 5),
-    "psg_recon_loss_f32": (c_int, [c_void_p] * 4 + [c_int64, c_float, c_float, c_void_p, c_void_p]),
-    "psg_recon_loss_workspace_bytes": (c_int64, []),
-    "psg_maxpool2x2_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p] + [c_int] * 5 + [c_void_p]),
-    "psg_maxpool2x2_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64] + [c_int] * 5 + [c_void_p]),
-    "psg_image_prep_fwd": (c_int, [c_void_p, c_void_p, c_int64] + [c_int] * 5 + [c_float, c_float, c_int, c_void_p]),
-    "psg_image_prep_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p] + [c_int] * 5 + [c_float, c_float, c_int, c_void_p]),
-    "psg_feat_l1": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_int, c_void_p,
-                            c_int64, c_void_p]),
-    "psg_feat_l1_workspace_bytes": (c_int64, []),
-    "psg_kl_f32": (c_int, [c_void_p] * 5 + [c_int64, c_void_p, c_int64, c_void_p]),
-    "psg_kl_workspace_bytes": (c_int64, []),
-    "psg_clip_prep_fwd": (c_int, [c_void_p, c_void_p, c_int64] + [c_int] * 5 + [c_float, c_float, c_int, c_void_p]),
-    "psg_clip_prep_bwd": (c_int, [c_void_p, c_int64, c_void_p] + [c_int] * 5 + [c_float, c_int, c_void_p]),
-    "psg_attn_fwd_causal": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]
-                            + [c_int] * 5 + [c_float, c_float, c_uint64, c_int, c_void_p]),
-    "psg_cosine_loss": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "psg_layernorm": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_float,
-                              c_int, c_int, c_void_p]),
-    "psg_layernorm_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
-                                  c_int, c_int64, c_int, c_float, c_int, c_int, c_void_p, c_int64, c_void_p]),
-    "psg_layernorm_bwd_workspace_bytes": (c_int64, [c_int64, c_int]),
-    "psg_bert_embed_ln": (c_int, [c_void_p] * 8 + [c_int64] + [c_int] * 6 + [c_float, c_int, c_void_p]),
-    "psg_bert_embed_ln_bwd": (c_int, [c_void_p] * 7 + [c_int64, c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_float, c_int, c_void_p, c_int64,
-                                                                                                              c_void_p]),
-    "psg_bert_embed_ln_bwd_workspace_bytes": (c_int64, [c_int64, c_int]),
-    "psg_embed_scatter": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_int, c_void_p, c_int64,
-                                  c_void_p]),
-    "psg_embed_scatter_workspace_bytes": (c_int64, [c_int64, c_int]),
-    "psg_embed_scatter_chunk_rows": (c_int, []),
-    "psg_sumsq_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
-    "psg_adamw_f32": (c_int, [c_void_p] * 4 + [c_int64] + [c_float] * 5 + [c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
-    "psg_adamw_dev_f32": (c_int, [c_void_p] * 4 + [c_int64, c_void_p, c_void_p, c_int] + [c_float] * 4 + [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
-    "psg_clip_scale_f32": (c_int, [c_void_p, c_int64, c_void_p, c_float, c_void_p]),
-    "psg_sprite_contrast_mean": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "psg_sprite_augment": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "psg_set_available_cus": (c_int, [c_int]),
-    "psg_set_reserve_rounds": (c_int, [c_int]),
-    "psg_stream_create_cu_mask": (c_int, [c_int, c_void_p]),
-    "psg_stream_destroy": (c_int, [c_void_p]),
-    "psg_profile_begin": (c_int, []),
-    "psg_profile_end": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
-    "psg_profile_bytes": (c_int, [c_void_p, c_int]),
-}
-
-_lib = None
-_inited = set()
+HEADER_PATH = os.path.join(_HERE, "..", "include", "psg_hip.h")
 
 
 class PsgError(RuntimeError):
     pass
+
+
+# ---------------------------------------------------------------------------
+# The header is the one declaration of the ABI: prototypes, descriptor structs and constants are read from its text at
+# import.  It is plain C (one prototype / field line / enum member per statement, /* */ comments), which the regular
+# expressions below read exactly; anything they cannot place raises - nothing is skipped and no type is guessed.
+# ---------------------------------------------------------------------------
+BY_VALUE = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float,
+            "psg_stream_t": C.c_void_p}
+STRUCT_CLASS_NAMES = {"psg_conv_desc": "ConvDesc", "psg_wgrad_desc": "WgradDesc"}
+
+
+class Abi:
+    """functions: name -> (restype, [(ctypes type, C type text, parameter name)]); structs: C name -> ctypes.Structure
+    class, whose _fields_ is the ordered [(field name, ctypes type)]; constants: enum members and integer #defines."""
+
+    def __init__(self):
+        self.functions, self.structs, self.constants = {}, {}, {}
+
+
+def _oneline(decl):
+    return " ".join(decl.split())
+
+
+def _declarator(decl):
+    """`const float *x` -> ("const float*", "x")"""
+    m = re.fullmatch(r"(.*[\s*])(\w+)", _oneline(decl))
+    ctext = re.sub(r"\s*\*\s*", "*", m.group(1)).strip() if m else ""
+    if not re.fullmatch(r"(const )?\w+\**", ctext):
+        raise PsgError(f"psg_hip.h: cannot split the declaration `{_oneline(decl)}`")
+    return ctext, m.group(2)
+
+
+def _ctype(ctext, structs, decl, is_return=False):
+    const = ctext.startswith("const ")
+    base = ctext[len("const "):] if const else ctext
+    if base.endswith("*"):
+        if is_return and ctext == "const char*":
+            return C.c_char_p
+        return C.POINTER(structs[base[:-1]]) if const and base[:-1] in structs else C.c_void_p
+    if base not in BY_VALUE:
+        raise PsgError(f"psg_hip.h: no ctypes mapping for the by-value type `{ctext}` in `{_oneline(decl)}`")
+    return BY_VALUE[base]
+
+
+def parse_header(text):
+    abi = Abi()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(PSG_\w+)[ \t]+(-?\d+)[ \t]*$", text, flags=re.M):
+        abi.constants[name] = int(value)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+
+    def enum(m):
+        for member in filter(None, (s.strip() for s in m.group(1).split(","))):
+            mm = re.fullmatch(r"(\w+)\s*=\s*(-?\d+)", member)
+            if not mm:
+                raise PsgError(f"psg_hip.h: enum member `{member}` is not written `NAME = <decimal integer>`")
+            abi.constants[mm.group(1)] = int(mm.group(2))
+        return ""
+    text = re.sub(r"\benum\s+\w+\s*\{([^{}]*)\}\s*;", enum, text)
+
+    def struct(m):
+        fields = []
+        for decl in filter(None, (s.strip() for s in m.group(1).split(";"))):       # `int32_t B, Hi, Wi, Cin`
+            first, *more = decl.split(",")
+            ctext, name = _declarator(first)
+            if not all(re.fullmatch(r"\s*\w+\s*", n) for n in more):
+                raise PsgError(f"psg_hip.h: cannot split the declaration `{_oneline(decl)}`")
+            fields += [(n.strip(), _ctype(ctext, abi.structs, decl)) for n in [name] + more]
+        abi.structs[m.group(2)] = type(STRUCT_CLASS_NAMES.get(m.group(2), m.group(2)), (C.Structure,),
+                                       {"_fields_": fields, "__doc__": f"struct {m.group(2)} (include/psg_hip.h)."})
+        return ""
+    text = re.sub(r"\btypedef\s+struct\s+\w+\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, text)
+    text = re.sub(r"\btypedef\s+[^;{}]*;", "", text)                     # plain typedefs (psg_stream_t): BY_VALUE names them
+    text = re.sub(r'\bextern\s+"C"\s*\{(.*)\}', r"\1", text, flags=re.S)
+    for decl in filter(None, (s.strip() for s in text.split(";"))):      # what is left must all be prototypes
+        m = re.fullmatch(r"([^()]*)\(([^()]*)\)", decl)
+        if not m:
+            raise PsgError(f"psg_hip.h: cannot split the declaration `{_oneline(decl)}`")
+        rtext, name = _declarator(m.group(1))
+        params = [] if m.group(2).strip() == "void" else [_declarator(p) for p in m.group(2).split(",")]
+        abi.functions[name] = (_ctype(rtext, abi.structs, decl, is_return=True),
+                               [(_ctype(t, abi.structs, decl), t, n) for t, n in params])
+    return abi
+
+
+def read_header(path=HEADER_PATH):
+    try:
+        with open(path, encoding="utf-8") as f:
+            text = f.read()
+    except OSError as e:
+        raise PsgError(f"cannot read the ABI header {path}: {e}") from None
+    return parse_header(text)
+
+
+ABI = read_header()
+SIGNATURES = {name: (res, [p[0] for p in params]) for name, (res, params) in ABI.functions.items()}   # name -> (restype, argtypes)
+ConvDesc, WgradDesc = ABI.structs["psg_conv_desc"], ABI.structs["psg_wgrad_desc"]
+
+
+def _k(names):
+    return [ABI.constants["PSG_" + n] for n in names.split()]
+
+
+PSG_F32, PSG_BF16 = _k("F32 BF16")
+OK, ERR_SHAPE, ERR_DTYPE, ERR_ALIGN, ERR_WORKSPACE, ERR_HIP, ERR_ARG = _k("OK ERR_SHAPE ERR_DTYPE ERR_ALIGN ERR_WORKSPACE ERR_HIP ERR_ARG")
+ACT_NONE, ACT_SILU, ACT_GELU, ACT_RELU, ACT_TANH, ACT_QUICK_GELU = _k("ACT_NONE ACT_SILU ACT_GELU ACT_RELU ACT_TANH ACT_QUICK_GELU")
+CONV_SAVE_DACT, CONV_DACT_MUL, CONV_GENERIC_EPILOGUE = _k("CONV_SAVE_DACT CONV_DACT_MUL CONV_GENERIC_EPILOGUE")
+# enum psg_flag: bits of the per-step NaN/Inf flag word
+FLAG_NOISY_BAD, FLAG_T_RANGE, FLAG_PRED_BAD, FLAG_LOSS_BAD, FLAG_FALLBACK, FLAG_INPUT_BAD, FLAG_SKIP_MASK = _k(
+    "FLAG_NOISY_BAD FLAG_T_RANGE FLAG_PRED_BAD FLAG_LOSS_BAD FLAG_FALLBACK FLAG_INPUT_BAD FLAG_SKIP_MASK")
+
+_lib = None
+_inited = set()
 
 
 def load():

@@ -27,7 +27,7 @@ import torch
 
 from . import _lib
 
-NUM_PARAMS = 16                     # PSG_SPRITE_PARAMS; the row layout is described in include/psg_hip.h
+NUM_PARAMS = _lib.ABI.constants["PSG_SPRITE_PARAMS"]     # the row layout is described in include/psg_hip.h
 # what pandas.read_csv reads as a missing value (the reference drops rows whose description is missing)
 _NA = frozenset(["", "#N/A", "#N/A N/A", "#NA", "-1.#IND", "-1.#QNAN", "-NaN", "-nan", "1.#IND", "1.#QNAN", "<NA>", "N/A", "NA",
                  "NULL", "NaN", "None", "n/a", "nan", "null"])

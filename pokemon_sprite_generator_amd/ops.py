@@ -67,7 +67,7 @@ def _rows(t):
 # ---------------------------------------------------------------------------
 # prepared-weight cache
 # ---------------------------------------------------------------------------
-W_OIHW, W_OHWI = 0, 1
+W_OIHW, W_OHWI = _lib.ABI.constants["PSG_W_OIHW"], _lib.ABI.constants["PSG_W_OHWI"]
 
 
 def weight_layout(t):
@@ -247,8 +247,21 @@ class GradSink:
 
 # The two descriptors are packed with struct.pack_into into per-thread buffers (backward runs on autograd's thread) and
 # handed over as a pointer: one C call instead of ~30 ctypes field stores (8 us a launch, ~600 launches per train step).
-_CONV_FMT = struct.Struct("<13i2fiQ7q8QQq")     # struct psg_conv_desc
-_WGRAD_FMT = struct.Struct("<14ifi2q5Qq")       # struct psg_wgrad_desc
+_PACK_CODE = {C.c_int: "i", C.c_float: "f", C.c_int64: "q", C.c_uint64: "Q", C.c_void_p: "Q"}
+
+
+def _desc_format(desc):
+    return struct.Struct("<" + "".join(_PACK_CODE[t] for _, t in desc._fields_))
+
+
+def _check_pack_order(desc, order):
+    """The pack_into calls below are positional: `order` names what they pass, in their order, and must be the header's."""
+    fields = tuple(n for n, _ in desc._fields_)
+    if fields != tuple(order):
+        raise _lib.PsgError(f"{desc.__name__}: the header declares the fields {fields} but ops.py packs {tuple(order)}")
+
+
+_CONV_FMT, _WGRAD_FMT = _desc_format(ConvDesc), _desc_format(WgradDesc)
 assert _CONV_FMT.size == C.sizeof(ConvDesc) and _WGRAD_FMT.size == C.sizeof(WgradDesc)
 _tls = threading.local()
 
@@ -276,10 +289,18 @@ class SplitKStats:
 _splitk_need = {}
 
 
+_CONV_PACK_ORDER = ("dtype", "B", "Hi", "Wi", "Cin", "Ho", "Wo", "Cout", "ksize", "stride", "pad", "transposed", "act",
+                    "alpha", "drop_p", "flags", "drop_seed",
+                    "ldx", "ldy", "ld_rowadd", "ld_residual", "ld_preact", "ld_dact", "ldw",
+                    "x", "w", "y", "bias", "rowadd", "residual", "preact", "dact_u", "ws", "ws_bytes")    # ws, ws_bytes: also the "<Qq" tail
+_check_pack_order(ConvDesc, _CONV_PACK_ORDER)
+
+
 def _conv_launch(lib, dtype, x, ldx, w, ldw, y, ldy, geom, Cin, Cout, transposed=False, bias=None, rowadd=None,
                  residual=None, ld_res=0, preact=None, dact_u=None, ld_dact=0, act=ACT_NONE, alpha=1.0, drop_p=0.0, seed=0, flags=0):
     B, Hi, Wi, Ho, Wo, ks, stride, pad = geom
     cb, cp, _, _ = _desc_bufs()
+    # positional: edit _CONV_PACK_ORDER together with this argument list
     _CONV_FMT.pack_into(cb, 0, dtype_code(dtype), B, Hi, Wi, Cin, Ho, Wo, Cout, ks, stride, pad, int(transposed), act,
                         float(alpha), float(drop_p), int(flags), int(seed) & 0xFFFFFFFFFFFFFFFF,
                         ldx, ldy, rowadd.stride(0) if rowadd is not None else 0, ld_res if residual is not None else 0,
@@ -304,6 +325,11 @@ def _conv_launch(lib, dtype, x, ldx, w, ldw, y, ldy, geom, Cin, Cout, transposed
     check(lib.psg_conv_fwd(cp, stream_ptr()), "psg_conv_fwd")
 
 
+_WGRAD_PACK_ORDER = ("dtype", "B", "Hi", "Wi", "Cin", "Ho", "Wo", "Cout", "ksize", "stride", "pad", "accumulate", "dw_layout",
+                     "accumulate_bias", "scale", "reserved1", "ldx", "lddy", "x", "dy", "dw", "dbias", "ws", "ws_bytes")
+_check_pack_order(WgradDesc, _WGRAD_PACK_ORDER)
+
+
 def _wgrad_launch(lib, dtype, x, ldx, dy, lddy, dw, geom, Cin, Cout, accumulate=False, dbias=None, accumulate_bias=False, scale=1.0):
     """dw (+)= dy^T . gather(x); with `dbias` the same launch also produces the bias gradient (column sums of dy)."""
     B, Hi, Wi, Ho, Wo, ks, stride, pad = geom
@@ -318,6 +344,7 @@ def _wgrad_launch(lib, dtype, x, ldx, dy, lddy, dw, geom, Cin, Cout, accumulate=
     _, _, wb, wp = _desc_bufs()
 
     def pack(ws_ptr, ws_bytes):
+        # positional: edit _WGRAD_PACK_ORDER together with this argument list
         _WGRAD_FMT.pack_into(wb, 0, dtype_code(dtype), B, Hi, Wi, Cin, Ho, Wo, Cout, ks, stride, pad, int(accumulate), layout,
                              int(accumulate_bias) if dbias is not None else 0, float(scale), 0, ldx, lddy,
                              x.data_ptr(), dy.data_ptr(), out.data_ptr(), dbias.data_ptr() if dbias is not None else 0, ws_ptr, ws_bytes)

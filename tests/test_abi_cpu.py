@@ -35,6 +35,7 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
         assert n in _lib.SIGNATURES, f"{n} declared in the header but not bound in _lib.SIGNATURES"
     for n in _lib.SIGNATURES:
         assert n in names, f"{n} bound but not declared in include/psg_hip.h"
+    assert sorted(_lib.ABI.functions) == names, "the header reader of _lib.py skipped or invented a prototype"
     assert lib.psg_version() >= 100
 
 
@@ -57,6 +58,98 @@ def test_struct_layouts_match_header():
     want = [C.sizeof(ConvDesc)] + [getattr(ConvDesc, f).offset for f in fields_c]
     want += [C.sizeof(WgradDesc)] + [getattr(WgradDesc, f).offset for f in fields_w]
     assert vals == want
+
+
+def test_constants_match_header():
+    """Every enum member and integer #define the reader found has the value gcc gives it."""
+    import subprocess
+    import tempfile
+    from pokemon_sprite_generator_amd import _lib
+    consts = _lib.ABI.constants
+    assert len(consts) >= 32 and consts["PSG_ERR_ARG"] == -6 and consts["PSG_FLAG_SKIP_MASK"] == 47 and consts["PSG_SPRITE_PARAMS"] == 16
+    prog = '#include <stdio.h>\n#include "psg_hip.h"\nint main(void){\n'
+    prog += "".join(f'printf("%lld\\n", (long long){n});\n' for n in consts) + "return 0;}\n"
+    with tempfile.TemporaryDirectory() as td:
+        src, exe = os.path.join(td, "abi.c"), os.path.join(td, "abi")
+        open(src, "w").write(prog)
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
+        vals = [int(v) for v in subprocess.check_output([exe]).split()]
+    assert vals == list(consts.values())
+    # the names modules import are those constants
+    assert (_lib.OK, _lib.ERR_SHAPE, _lib.ERR_DTYPE, _lib.ERR_ALIGN, _lib.ERR_WORKSPACE, _lib.ERR_HIP, _lib.ERR_ARG) == (0, -1, -2, -3, -4, -5, -6)
+    assert (_lib.PSG_F32, _lib.PSG_BF16, _lib.ACT_QUICK_GELU, _lib.CONV_GENERIC_EPILOGUE, _lib.FLAG_INPUT_BAD) == (0, 1, 5, 4, 32)
+
+
+def test_header_reader_on_synthetic_headers(tmp_path):
+    from pokemon_sprite_generator_amd._lib import PsgError, parse_header, read_header
+    abi = parse_header("""
+        /* psg_fake(int x); is only prose (with parentheses) */
+        #define PSG_N 7
+        #define PSG_GUARD_H
+        typedef void* psg_stream_t; /* hipStream_t */
+        enum psg_e { PSG_A = 0, PSG_B = -3 };
+        typedef struct psg_conv_desc {
+            int32_t B, Hi, Wi;     /* several declarators */
+            float alpha;
+            uint64_t seed;
+            const void* x;
+            const float *bias;
+            float* dw;
+            int64_t ws_bytes;
+        } psg_conv_desc;
+        const char* psg_name(void);
+        int64_t psg_bytes(void);
+        int psg_run(const psg_conv_desc* d, const float* a,
+                    int64_t lda, float scale, uint64_t seed,
+                    void* ws, int64_t ws_bytes,
+                    psg_stream_t stream);
+        int psg_make(int n, psg_stream_t* stream);
+    """)
+    assert abi.constants == {"PSG_N": 7, "PSG_A": 0, "PSG_B": -3}
+    desc = abi.structs["psg_conv_desc"]
+    assert issubclass(desc, C.Structure) and desc.__name__ == "ConvDesc"
+    assert desc._fields_ == [("B", C.c_int), ("Hi", C.c_int), ("Wi", C.c_int), ("alpha", C.c_float), ("seed", C.c_uint64),
+                             ("x", C.c_void_p), ("bias", C.c_void_p), ("dw", C.c_void_p), ("ws_bytes", C.c_int64)]
+    assert sorted(abi.functions) == ["psg_bytes", "psg_make", "psg_name", "psg_run"]          # and no psg_fake
+    assert abi.functions["psg_name"] == (C.c_char_p, []) and abi.functions["psg_bytes"] == (C.c_int64, [])
+    res, params = abi.functions["psg_run"]
+    assert res is C.c_int
+    assert params == [(C.POINTER(desc), "const psg_conv_desc*", "d"), (C.c_void_p, "const float*", "a"), (C.c_int64, "int64_t", "lda"),
+                      (C.c_float, "float", "scale"), (C.c_uint64, "uint64_t", "seed"), (C.c_void_p, "void*", "ws"),
+                      (C.c_int64, "int64_t", "ws_bytes"), (C.c_void_p, "psg_stream_t", "stream")]
+    assert abi.functions["psg_make"][1] == [(C.c_int, "int", "n"), (C.c_void_p, "psg_stream_t*", "stream")]
+
+    with pytest.raises(PsgError, match=r"size_t.*psg_f\(const float\* a, size_t n\)"):
+        parse_header("int psg_f(const float* a, size_t n);")                                  # never guessed as c_int
+    with pytest.raises(PsgError, match="size_t"):
+        parse_header("typedef struct s { int32_t a; size_t n; } s;")
+    with pytest.raises(PsgError, match="PSG_Y"):
+        parse_header("enum psg_e { PSG_X = 0, PSG_Y };")
+    for bad in ("int psg_f(int);", "int psg_f(int x[4]);", "int psg_f();", "unsigned int psg_f(void);", "int psg_f(void) { return 0; }",
+                "typedef struct s { float *a, *b; } s;", "int psg_g(void);\n}"):
+        with pytest.raises(PsgError, match="cannot split"):
+            parse_header(bad)
+    missing = str(tmp_path / "no_such_psg_hip.h")
+    with pytest.raises(PsgError, match="no_such_psg_hip.h"):
+        read_header(missing)
+
+
+def test_pack_order_guard_follows_the_header():
+    """ops.py packs the two descriptors positionally: a header whose fields change order (or number) must fail the import-time
+    guard on the CPU, before any launch, even though the ctypes mirrors follow the header by construction."""
+    from pokemon_sprite_generator_amd import ops
+    from pokemon_sprite_generator_amd._lib import HEADER_PATH, PsgError, parse_header
+    text = open(HEADER_PATH, encoding="utf-8").read()
+    for cname, order, old, new in (("psg_conv_desc", ops._CONV_PACK_ORDER, "int32_t Ho, Wo, Cout;", "int32_t Wo, Ho, Cout;"),
+                                   ("psg_wgrad_desc", ops._WGRAD_PACK_ORDER, "int64_t ldx, lddy;", "int64_t lddy, ldx;"),
+                                   ("psg_wgrad_desc", ops._WGRAD_PACK_ORDER, "int32_t reserved1;", "int32_t reserved1, reserved2;")):
+        assert text.count(old) == 1
+        ops._check_pack_order(parse_header(text).structs[cname], order)
+        swapped = parse_header(text.replace(old, new)).structs[cname]
+        if "reserved2" not in new:
+            assert C.sizeof(swapped) == C.sizeof(parse_header(text).structs[cname])          # nothing else would notice
+        with pytest.raises(PsgError, match="packs"):
+            ops._check_pack_order(swapped, order)
 
 
 def test_argument_validation_without_gpu(lib):

@@ -14,7 +14,8 @@ from tests import conv4s2_ref as R
 from tests import gemm_ref
 from tests.util import maxrel, rel_l2
 
-OK, ERR_SHAPE, ERR_DTYPE, ERR_ALIGN, ERR_WORKSPACE, ERR_ARG = 0, -1, -2, -3, -4, -6
+from pokemon_sprite_generator_amd._lib import OK, ERR_SHAPE, ERR_DTYPE, ERR_ALIGN, ERR_WORKSPACE, ERR_ARG
+
 P = 0x10000            # a 16-byte aligned non-null "pointer": validation never dereferences
 
 

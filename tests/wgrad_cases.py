@@ -16,6 +16,8 @@ import ctypes
 import json
 import os
 
+from pokemon_sprite_generator_amd._lib import ERR_ARG
+
 ROUTES_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wgrad_routes.json")
 ROUTE_FIELDS = ("family", "dtype", "geom", "bias", "BR", "BQ", "BKP", "lds", "wg_per_cu", "rtiles", "qtiles", "splits",
                 "steps_per_split", "grid", "finish", "bias_finish", "launches")
@@ -26,7 +28,6 @@ BIAS_FINISH = ("none", "direct", "folded", "bias_sum")
 DTYPE_CODE = {"f32": 0, "bf16": 1}
 LAYOUT_CODE = {"oihw": 0, "ohwi": 1}
 CUS = (256, 96)
-ERR_ARG = -6
 # the environment spot checks: (variable, value) -> routes of ENV_CASES at bf16 / 256 CUs
 ENV_SETTINGS = (("PSG_WGRAD_WIDE", "0"), ("PSG_WGRAD_PIPE", "0"), ("PSG_WGRAD_BR160", "0"), ("PSG_WGRAD_SPLITS", "3"))
 

@@ -3,7 +3,8 @@
     python tools/abi_trace.py --out TRACE tests/test_unet_gpu.py tests/test_vae_gpu.py ...     (from the tree's root)
     python tools/abi_trace.py --compare TRACE_A TRACE_B
 
-After `_lib.load()` every function named in `_lib.SIGNATURES` is replaced on the loaded library object by a recorder that
+After `_lib.load()` every function include/psg_hip.h declares (`_lib.ABI.functions`: the parsed parameter lists, which also say
+which argument is the stream and which a workspace byte count) is replaced on the loaded library object by a recorder that
 writes one line and then calls the function.  The given pytest node ids run in-process; at the start of every test the torch
 seed and the dropout seed stream's counter are reset, so a test's calls do not depend on the tests before it.  A line holds
 the entry name and, per argument: integers and floats in full (dropout seeds included); for a pointer whether it is null and
@@ -18,13 +19,6 @@ import os
 import sys
 
 sys.path.insert(0, os.getcwd())
-
-# The two lists below are kept by hand next to `_lib.SIGNATURES` and must follow it: an entry added there whose last pointer is
-# not a stream, or that takes a workspace byte count, has to be named here or its line is tagged wrongly (for both trees alike).
-NO_STREAM = {"psg_set_seed_source", "psg_attn_path_counts", "psg_profile_end", "psg_profile_bytes", "psg_stream_create_cu_mask",
-             "psg_stream_destroy", "psg_attn_route", "psg_groupnorm_route", "psg_conv_route", "psg_conv_wgrad_route"}
-# entries whose second-to-last argument is the byte count of the workspace before it
-WS_BYTES = {"psg_colsum", "psg_attn_bwd_longq", "psg_feat_l1", "psg_kl_f32", "psg_layernorm_bwd", "psg_bert_embed_ln_bwd", "psg_embed_scatter"}
 
 
 def _addr(v):
@@ -54,11 +48,12 @@ class Recorder:
     def __init__(self, out):
         self.out, self.streams, self.calls = out, [], 0
 
-    def wrap(self, name, fn, argtypes):
+    def wrap(self, name, fn, params):
+        """params: the header's parameter list, [(ctypes type, C type text, name)] (_lib.ABI.functions)."""
         def call(*args):
             parts = []
-            for i, (a, t) in enumerate(zip(args, argtypes)):
-                if t is C.c_void_p and i == len(argtypes) - 1 and name not in NO_STREAM:
+            for a, (t, ctext, pname) in zip(args, params):
+                if ctext == "psg_stream_t":
                     s = _addr(a)
                     if s not in self.streams:
                         self.streams.append(s)
@@ -67,7 +62,7 @@ class Recorder:
                     parts.append(_pointer(a))
                 elif hasattr(t, "contents"):
                     parts.append(_struct(a))
-                elif name in WS_BYTES and i == len(argtypes) - 2:
+                elif ctext == "int64_t" and pname == "ws_bytes":
                     parts.append("ws0" if int(a) == 0 else "ws+")
                 else:
                     parts.append(repr(float(a)) if t is C.c_float else repr(int(a)))
@@ -125,8 +120,8 @@ def main():
     lib = _lib.load()
     with open(args.out, "w") as out:
         rec = Recorder(out)
-        for name, (_, argtypes) in _lib.SIGNATURES.items():
-            setattr(lib, name, rec.wrap(name, getattr(lib, name), argtypes))
+        for name, (_, params) in _lib.ABI.functions.items():
+            setattr(lib, name, rec.wrap(name, getattr(lib, name), params))
         rc = pytest.main([*args.nodeids, "-q", "-m", "gpu", "-p", "no:cacheprovider"], plugins=[rec])
     print(f"{rec.calls} calls recorded, pytest exit code {int(rc)}")
     return int(rc)
