@@ -201,9 +201,12 @@ int psg_upsample_bilinear_fwd(const void* x, int64_t ldx, void* y, int64_t ldy, 
                               int Ho, int Wo, int C, int dtype, psg_stream_t stream);
 int psg_upsample_bilinear_bwd(const void* dy, int64_t lddy, void* dx, int64_t lddx, int B, int Hi,
                               int Wi, int Ho, int Wo, int C, int dtype, psg_stream_t stream);
-/* y = a + b (elementwise, strided rows); used for gradient fan-in of skip tensors. */
-int psg_add(const void* a, int64_t lda, const void* b, int64_t ldb, void* y, int64_t ldy, int64_t rows,
-            int cols, int dtype, psg_stream_t stream);
+/* Which kernel pair takes an upsample launch, from the launches' own predicate and with their argument checks and error
+ * codes; host only, no device is touched.  rd / ldrd: the operand a lane gathers from (forward x, backward dy), wr / ldwr:
+ * the one it writes (forward y, backward dx).  out[0] = 1: the 8-channel bf16 kernel (bf16, C and both row strides
+ * multiples of 8, both pointers 16-byte aligned, 32-bit offsets; backward also Wo <= 3 Wi), 0: the 4-channel kernel. */
+int psg_upsample_route(int backward, int dtype, const void* rd, int64_t ldrd, const void* wr, int64_t ldwr, int B, int Hi,
+                       int Wi, int Ho, int Wo, int C, int32_t* out);
 /* Dropout under hipGraph replay.  Every mask in this library is a stateless hash of (seed, element index); the seeds are
  * launch arguments, so a captured train step would replay the SAME masks forever.  After psg_set_seed_source(p) every launch
  * that draws a mask adds the 64-bit word at device address p to its seed when it RUNS (conv / Linear epilogues, attention,
@@ -401,8 +404,17 @@ int psg_conv_wgrad_route(const psg_wgrad_desc* d, int32_t* out);
 /* Master weight (w_dtype PSG_F32, or PSG_BF16 for the AdamW shadow copy; w_layout PSG_W_OIHW or PSG_W_OHWI memory
  * order; a bf16 source must be OHWI or 1x1) -> prepared forward weight wf [O][Kpad] with k=(kh,kw,ci) and prepared
  * data-gradient weight wd [I][Kpad'] with k=(kh,kw,co) (either may be NULL); zero K padding.  Kpad: psg_kpad(). */
+/* 4x4 weights (ksize 4) must be OHWI with O and I multiples of 4 and w, wf and wd 16-byte aligned (PSG_ERR_ARG otherwise). */
 int psg_prep_weight(const void* w, int w_dtype, int w_layout, void* wf, void* wd, int O, int I, int ksize, int dtype,
                     psg_stream_t stream);
+/* Which kernel a psg_prep_weight launch with these arguments runs, from the launcher's own decision and with its argument
+ * checks and error codes; host only, no device is touched.  out[0] = a psg_prep_kernel value: the generic kernel (fp32
+ * source, any layout and channel counts, LDS transpose), the OHWI kernel on an fp32 or on a bf16 source (OHWI or 1x1, O and
+ * I multiples of 4, all pointers 16-byte aligned), or the bf16 transposition that writes wd alone (no wf, O and I multiples
+ * of 8). */
+enum psg_prep_kernel { PSG_PREP_GENERIC = 0, PSG_PREP_OHWI_F32 = 1, PSG_PREP_OHWI_BF16 = 2, PSG_PREP_WD_BF16 = 3 };
+int psg_prep_weight_route(const void* w, int w_dtype, int w_layout, const void* wf, const void* wd, int O, int I, int ksize,
+                          int dtype, int32_t* out);
 int64_t psg_kpad(int64_t K, int dtype);
 
 /* ---------------------------------------------------------------------------

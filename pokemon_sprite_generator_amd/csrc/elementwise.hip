@@ -405,18 +405,6 @@ __global__ __launch_bounds__(256) void upsample_bwd8_kernel(const bf16_t* __rest
     *reinterpret_cast<bf16x8*>(dx + (int64_t)pix * lddx + c) = o;
 }
 
-template <typename T>
-__global__ void add_kernel(const T* __restrict__ a, int64_t lda, const T* __restrict__ b, int64_t ldb,
-                           T* __restrict__ y, int64_t ldy, int64_t rows, int cols) {
-    const int c4n = cols >> 2;
-    const int64_t n = rows * c4n;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % c4n) * 4;
-        const int64_t r = i / c4n;
-        store4<T>(y + r * ldy + c, load4<T>(a + r * lda + c) + load4<T>(b + r * ldb + c));
-    }
-}
-
 // y = a (+ b (+ c)): row-strided operands, 16-byte chunks, ONE rounding of the fp32 sum.  One source = a strided copy
 // (a skip tensor into its half of a concat buffer), three = the gradient fan-in of a skip tensor (next encoder stage +
 // the two decoder blocks that read it) in one pass instead of autograd's clone + add + add.
@@ -1025,8 +1013,8 @@ int psg_timestep_sinusoid(const int64_t* t, const float* coeff, void* out, int64
 
 // Whether the 8-channel form takes an upsample launch: bf16 with 16-byte channel chunks and 32-bit offsets.  A lane writes one
 // chunk of `wr` and gathers from `rd` (forward: input -> output; backward: dy -> dx).  Backward also needs Wo <= 3 * Wi:
-// upsample_bwd8_kernel keeps 6 contributing output columns per input column, enough up to 3x (checked for Wi <= 64) while
-// 7 -> 28 has 8, and its 32-bit b * Ho * Wo.  Launches it does not take go to the 4-channel kernels, which have neither limit.
+// upsample_bwd8_kernel keeps 6 contributing output columns per input column, enough up to 3x (tests/test_row_ref_cpu.py: every
+// Wi <= 256) while 7 -> 28 has 8, and its 32-bit b * Ho * Wo.  Launches it does not take go to the 4-channel kernels, which have neither limit.
 static bool upsample8_applies(bool backward, int dtype, const void* rd, int64_t ldrd, const void* wr, int64_t ldwr, int B, int Hi,
                               int Wi, int Ho, int Wo, int C) {
     const int64_t in_px = (int64_t)Hi * Wi, out_px = (int64_t)Ho * Wo, rd_px = backward ? out_px : in_px, wr_px = backward ? in_px : out_px;
@@ -1035,11 +1023,28 @@ static bool upsample8_applies(bool backward, int dtype, const void* rd, int64_t 
            (!backward || (Wo <= 3 * (int64_t)Wi && B * out_px < (1ll << 31)));
 }
 
+// the shape checks of both upsample launches
+static int upsample_check(const char* who, const void* rd, int64_t ldrd, const void* wr, int64_t ldwr, int B, int Hi, int Wi, int Ho, int Wo, int C) {
+    PSG_REQUIRE(rd && wr, PSG_ERR_ARG, "%s: null pointer", who);
+    PSG_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && Ho >= Hi && Wo >= Wi && C > 0 && (C & 3) == 0 && ldrd >= C && ldwr >= C &&
+                (ldrd & 3) == 0 && (ldwr & 3) == 0, PSG_ERR_SHAPE, "%s: bad shape (C, ld multiples of 4)", who);
+    return PSG_OK;
+}
+
+int psg_upsample_route(int backward, int dtype, const void* rd, int64_t ldrd, const void* wr, int64_t ldwr, int B, int Hi, int Wi,
+                       int Ho, int Wo, int C, int32_t* out) {
+    PSG_REQUIRE(out, PSG_ERR_ARG, "upsample_route: null pointer");
+    const int rc = upsample_check("upsample_route", rd, ldrd, wr, ldwr, B, Hi, Wi, Ho, Wo, C);
+    if (rc != PSG_OK) return rc;
+    if (dtype != PSG_F32 && dtype != PSG_BF16) return bad_dtype(dtype);
+    out[0] = upsample8_applies(backward != 0, dtype, rd, ldrd, wr, ldwr, B, Hi, Wi, Ho, Wo, C) ? 1 : 0;
+    return PSG_OK;
+}
+
 int psg_upsample_bilinear_fwd(const void* x, int64_t ldx, void* y, int64_t ldy, int B, int Hi, int Wi, int Ho, int Wo,
                               int C, int dtype, psg_stream_t stream) {
-    PSG_REQUIRE(x && y, PSG_ERR_ARG, "upsample_fwd: null pointer");
-    PSG_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && Ho >= Hi && Wo >= Wi && C > 0 && (C & 3) == 0 && ldx >= C && ldy >= C &&
-                (ldx & 3) == 0 && (ldy & 3) == 0, PSG_ERR_SHAPE, "upsample_fwd: bad shape (C, ld multiples of 4)");
+    const int rc = upsample_check("upsample_fwd", x, ldx, y, ldy, B, Hi, Wi, Ho, Wo, C);
+    if (rc != PSG_OK) return rc;
     if (upsample8_applies(false, dtype, x, ldx, y, ldy, B, Hi, Wi, Ho, Wo, C)) {
         const int64_t n8 = (int64_t)B * Ho * Wo * (C / 8);
         hipLaunchKernelGGL(upsample_fwd8_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (int)ldx,
@@ -1056,9 +1061,8 @@ int psg_upsample_bilinear_fwd(const void* x, int64_t ldx, void* y, int64_t ldy, 
 
 int psg_upsample_bilinear_bwd(const void* dy, int64_t lddy, void* dx, int64_t lddx, int B, int Hi, int Wi, int Ho,
                               int Wo, int C, int dtype, psg_stream_t stream) {
-    PSG_REQUIRE(dy && dx, PSG_ERR_ARG, "upsample_bwd: null pointer");
-    PSG_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && Ho >= Hi && Wo >= Wi && C > 0 && (C & 3) == 0 && lddy >= C && lddx >= C &&
-                (lddx & 3) == 0 && (lddy & 3) == 0, PSG_ERR_SHAPE, "upsample_bwd: bad shape (C, ld multiples of 4)");
+    const int rc = upsample_check("upsample_bwd", dy, lddy, dx, lddx, B, Hi, Wi, Ho, Wo, C);
+    if (rc != PSG_OK) return rc;
     if (upsample8_applies(true, dtype, dy, lddy, dx, lddx, B, Hi, Wi, Ho, Wo, C)) {
         const int64_t n8 = (int64_t)B * Hi * Wi * (C / 8);
         hipLaunchKernelGGL(upsample_bwd8_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (int)lddy,
@@ -1070,17 +1074,6 @@ int psg_upsample_bilinear_bwd(const void* dy, int64_t lddy, void* dx, int64_t ld
     return launch_dtype(dtype, "upsample_bwd", [&](auto elem) {
         using T = decltype(elem);
         hipLaunchKernelGGL(upsample_bwd_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const T*)dy, lddy, (T*)dx, lddx, B, Hi, Wi, Ho, Wo, C);
-    });
-}
-
-int psg_add(const void* a, int64_t lda, const void* b, int64_t ldb, void* y, int64_t ldy, int64_t rows, int cols,
-            int dtype, psg_stream_t stream) {
-    PSG_REQUIRE(a && b && y, PSG_ERR_ARG, "add: null pointer");
-    PSG_REQUIRE(rows > 0 && cols > 0 && (cols & 3) == 0 && ((lda | ldb | ldy) & 3) == 0, PSG_ERR_SHAPE, "add: cols/ld must be multiples of 4");
-    const int g = grid_for(rows * (cols / 4), 256, 8192);
-    return launch_dtype(dtype, "add", [&](auto elem) {
-        using T = decltype(elem);
-        hipLaunchKernelGGL(add_kernel<T>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const T*)a, lda, (const T*)b, ldb, (T*)y, ldy, rows, cols);
     });
 }
 
@@ -1136,34 +1129,66 @@ int64_t psg_kpad(int64_t K, int dtype) {
     return (K + bk - 1) / bk * bk;
 }
 
-int psg_prep_weight(const void* w, int w_dtype, int w_layout, void* wf, void* wd, int O, int I, int ksize, int dtype, psg_stream_t stream) {
+// Which kernel takes a psg_prep_weight launch (a PSG_PREP_* value), after the launcher's own argument checks: psg_prep_weight and
+// psg_prep_weight_route both call this and nothing else decides.  The 4x4 case admits the OHWI kernels only - prep_weight_kernel's
+// LDS tile holds 9 taps per input channel - so every pointer the OHWI kernels need aligned is required there, outputs included.
+static int prep_weight_pick(const void* w, int w_dtype, int w_layout, const void* wf, const void* wd, int O, int I, int ksize, int dtype,
+                            int& kernel) {
     PSG_REQUIRE(w && (wf || wd), PSG_ERR_ARG, "prep_weight: null pointer");
     PSG_REQUIRE(O > 0 && I > 0 && (ksize == 1 || ksize == 3 || ksize == 4), PSG_ERR_SHAPE, "prep_weight: O=%d I=%d k=%d", O, I, ksize);
     PSG_REQUIRE(ksize != 4 || (w_layout == PSG_W_OHWI && O % 4 == 0 && I % 4 == 0 && aligned16(w)), PSG_ERR_ARG,
                 "prep_weight: 4x4 weights (VAE encoder) must be OHWI, 16-byte aligned, O and I multiples of 4");
+    PSG_REQUIRE(ksize != 4 || ((!wf || aligned16(wf)) && (!wd || aligned16(wd))), PSG_ERR_ARG,
+                "prep_weight: 4x4 weights (VAE encoder) need 16-byte aligned wf and wd");
     PSG_REQUIRE(w_layout == PSG_W_OIHW || w_layout == PSG_W_OHWI, PSG_ERR_ARG, "prep_weight: w_layout %d", w_layout);
     PSG_REQUIRE(w_dtype == PSG_F32 || w_dtype == PSG_BF16, PSG_ERR_DTYPE, "prep_weight: w_dtype %d", w_dtype);
+    if (dtype != PSG_F32 && dtype != PSG_BF16) return bad_dtype(dtype);
+    PSG_REQUIRE((O + 31) / 32 <= 65535, PSG_ERR_SHAPE, "prep_weight: O=%d too large", O);
+    const int taps = ksize * ksize;
+    if ((w_layout == PSG_W_OHWI || taps == 1) && O % 4 == 0 && I % 4 == 0 && aligned16(w) && (!wf || aligned16(wf)) && (!wd || aligned16(wd))) {
+        if (w_dtype == PSG_BF16) {
+            PSG_REQUIRE(dtype == PSG_BF16, PSG_ERR_DTYPE, "prep_weight: a bf16 source prepares bf16 weights only");
+            kernel = !wf && O % 8 == 0 && I % 8 == 0 ? PSG_PREP_WD_BF16 : PSG_PREP_OHWI_BF16;
+        } else {
+            kernel = PSG_PREP_OHWI_F32;
+        }
+        return PSG_OK;
+    }
+    PSG_REQUIRE(w_dtype == PSG_F32, PSG_ERR_ARG, "prep_weight: a bf16 source must be OHWI (or 1x1), 16-byte aligned, O and I multiples of 4");
+    kernel = PSG_PREP_GENERIC;
+    return PSG_OK;
+}
+
+int psg_prep_weight_route(const void* w, int w_dtype, int w_layout, const void* wf, const void* wd, int O, int I, int ksize, int dtype,
+                          int32_t* out) {
+    PSG_REQUIRE(out, PSG_ERR_ARG, "prep_weight_route: null pointer");
+    int kernel = 0;
+    const int rc = prep_weight_pick(w, w_dtype, w_layout, wf, wd, O, I, ksize, dtype, kernel);
+    if (rc == PSG_OK) out[0] = kernel;
+    return rc;
+}
+
+int psg_prep_weight(const void* w, int w_dtype, int w_layout, void* wf, void* wd, int O, int I, int ksize, int dtype, psg_stream_t stream) {
+    int kernel = 0;
+    const int rc = prep_weight_pick(w, w_dtype, w_layout, wf, wd, O, I, ksize, dtype, kernel);
+    if (rc != PSG_OK) return rc;
     const int ohwi = w_layout == PSG_W_OHWI;
     const int taps = ksize * ksize;
     const int64_t kpf = psg_kpad((int64_t)taps * I, dtype), kpd = psg_kpad((int64_t)taps * O, dtype);
-    PSG_REQUIRE((O + 31) / 32 <= 65535, PSG_ERR_SHAPE, "prep_weight: O=%d too large", O);
     hipStream_t s = (hipStream_t)stream;
-    if ((ohwi || taps == 1) && O % 4 == 0 && I % 4 == 0 && aligned16(w) && (!wf || aligned16(wf)) && (!wd || aligned16(wd))) {
+    if (kernel != PSG_PREP_GENERIC) {
         const dim3 g((I + 63) / 64, (O + 63) / 64, taps);
-        if (w_dtype == PSG_BF16) {
-            PSG_REQUIRE(dtype == PSG_BF16, PSG_ERR_DTYPE, "prep_weight: a bf16 source prepares bf16 weights only");
-            if (!wf && O % 8 == 0 && I % 8 == 0)
-                hipLaunchKernelGGL(prep_wd_bf16_kernel, g, dim3(256), 0, s, (const bf16_t*)w, (bf16_t*)wd, O, I, taps, kpd);
-            else
-                hipLaunchKernelGGL((prep_weight_ohwi_kernel<bf16_t, bf16_t>), g, dim3(256), 0, s, (const bf16_t*)w, (bf16_t*)wf, (bf16_t*)wd, O, I, taps, kpf, kpd);
-        } else if (!with_dtype(dtype, [&](auto elem) {
+        if (kernel == PSG_PREP_WD_BF16)
+            hipLaunchKernelGGL(prep_wd_bf16_kernel, g, dim3(256), 0, s, (const bf16_t*)w, (bf16_t*)wd, O, I, taps, kpd);
+        else if (kernel == PSG_PREP_OHWI_BF16)
+            hipLaunchKernelGGL((prep_weight_ohwi_kernel<bf16_t, bf16_t>), g, dim3(256), 0, s, (const bf16_t*)w, (bf16_t*)wf, (bf16_t*)wd, O, I, taps, kpf, kpd);
+        else if (!with_dtype(dtype, [&](auto elem) {
             using T = decltype(elem);
             hipLaunchKernelGGL((prep_weight_ohwi_kernel<float, T>), g, dim3(256), 0, s, (const float*)w, (T*)wf, (T*)wd, O, I, taps, kpf, kpd);
         })) return bad_dtype(dtype);
         PSG_LAUNCH_CHECK("prep_weight");
         return PSG_OK;
     }
-    PSG_REQUIRE(w_dtype == PSG_F32, PSG_ERR_ARG, "prep_weight: a bf16 source must be OHWI (or 1x1), 16-byte aligned, O and I multiples of 4");
     const dim3 g((I + 31) / 32, (O + 31) / 32);
     return launch_dtype(dtype, "prep_weight", [&](auto elem) {
         using T = decltype(elem);
