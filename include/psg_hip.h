@@ -383,6 +383,23 @@ int psg_conv_wgrad_set_variant(int v);
 /* Split pin: n > 0 makes every launch ask for n K splits (the environment variable PSG_WGRAD_SPLITS is the initial value; the
  * launch gets ceil(steps / ceil(steps / n)) of them); 0 returns the choice to the makespan model. */
 int psg_conv_wgrad_set_splits(int n);
+
+/* Slim weight gradient: the VAE decoder's high-resolution layers under stage 1 (src/training/vae_trainer.py) - blocks 4 and 5
+ * of src/models/vae_decoder.py:163-175 (108 x 108 x 64 and 215 x 215 x 32 channels) and the 32 -> 3 image convolution - where
+ * psg_conv_wgrad's 128-row tiles are three quarters padding.  Same descriptor, same result as psg_conv_wgrad, under a narrower
+ * contract: dtype PSG_BF16 (PSG_ERR_DTYPE otherwise: fp32 keeps going to psg_conv_wgrad); ksize 1 (pad 0) or 3 (pad 1), stride
+ * 1, Ho = Hi, Wo = Wi; Cout one of 8, 16, 32, 64; Cin a multiple of 8, at most 128; ldx >= Cin, lddy >= Cout, both multiples of
+ * 8 (PSG_ERR_SHAPE); x, dy and ws 16-byte aligned (PSG_ERR_ALIGN); dw_layout, null pointers (PSG_ERR_ARG).  Everything is
+ * checked on the host before any launch.  One workgroup owns all Cout rows, a 32-channel column block with all its taps and a
+ * slab of 8 x 16-pixel tiles (the nine taps share one LDS image of the input tile with its halo); the slabs - their count
+ * follows the pixel count and the CUs - are fp32 partials in ws (>= psg_conv_wgrad_slim_workspace_bytes, -1 for a descriptor
+ * outside the contract) that a second kernel adds in a fixed order: no atomics, the same bits every run.  dbias, accumulate,
+ * accumulate_bias and scale as in psg_conv_wgrad. */
+int psg_conv_wgrad_slim(const psg_wgrad_desc* d, psg_stream_t stream);
+int64_t psg_conv_wgrad_slim_workspace_bytes(const psg_wgrad_desc* d);
+/* Split pin of psg_conv_wgrad_slim (a test hook like psg_conv4s2_wgrad_set_splits): n > 0 asks for n slabs of whole tiles (the
+ * launch gets ceil(tiles / ceil(tiles / n)) of them, at most one per tile); 0 returns the choice to the plan. */
+int psg_conv_wgrad_slim_set_splits(int n);
 /* Host-only: which kernels psg_conv_wgrad(d) would launch, and how.  Runs the descriptor checks of
  * psg_conv_wgrad_workspace_bytes and the same plan - honouring psg_conv_wgrad_set_variant / _set_splits, the PSG_WGRAD_*
  * environment, psg_set_available_cus and psg_set_reserve_rounds - but reads no operand, initialises no device and launches

@@ -330,8 +330,39 @@ _WGRAD_PACK_ORDER = ("dtype", "B", "Hi", "Wi", "Cin", "Ho", "Wo", "Cout", "ksize
 _check_pack_order(WgradDesc, _WGRAD_PACK_ORDER)
 
 
+_WGRAD_SLIM = os.environ.get("PSG_WGRAD_SLIM", "1") != "0"          # 0: every launch goes to psg_conv_wgrad (A/B)
+_WGRAD_SLIM_MIN_SIDE, _WGRAD_SLIM_MIN_M = 64, 11664
+
+
+class SlimStats:
+    """How many weight-gradient launches went to psg_conv_wgrad_slim (tests, tools)."""
+    launches = 0
+
+
+def _wgrad_slim_route(dtype, geom, Cin, Cout):
+    """Whether a weight-gradient launch goes to psg_conv_wgrad_slim (csrc/conv_wgrad_slim.hip) instead of psg_conv_wgrad:
+    inside the slim entry's contract AND inside the set where it was measured faster - the one place that decides.
+
+    Measured (tools/bench_wgrad_slim.py, MI355X, bf16, with dbias, interleaved A/B; DESIGN.md section 19, raw lines in
+    profiles/wgrad_slim_bench.jsonl): the VAE decoder's blocks 4 and 5 and its image convolution - 108 x 108 and 215 x 215
+    pixels, Cin in {32, 64, 128}, Cout in {8, 32, 64}, 3x3 and 1x1 - at batch 1, 2, 4 and 16 (M = 11 664 ... 739 600): on
+    every one of the 36 shapes the slim kernel takes 0.22 - 0.69 of psg_conv_wgrad's time, more than that shape's
+    round-to-round spread of either entry.  Adopted for exactly those channel counts on images of at least 64 x 64 pixels
+    (the 8 x 16-pixel tiles of a smaller image are mostly border; nothing smaller was measured) from the smallest M measured
+    up; everything else keeps psg_conv_wgrad, which is also the only fp32 path.
+
+    No launch of the U-Net train step comes near: its convolutions run at 27 x 27 pixels and below (side < 64), and the two
+    layers with a small channel count, the 8 -> 320 input and the 320 -> 8 output convolution, have Cout = 320 and Cin = 320;
+    its Linears are 1 x 1 "images".  tests/test_gemm_b256_gpu.py and the step's launch count are unchanged."""
+    B, Hi, Wi, Ho, Wo, ks, stride, pad = geom
+    return (_WGRAD_SLIM and dtype == torch.bfloat16 and stride == 1 and ks in (1, 3) and Ho == Hi and Wo == Wi
+            and Cout in (8, 32, 64) and Cin in (32, 64, 128)
+            and Hi >= _WGRAD_SLIM_MIN_SIDE and Wi >= _WGRAD_SLIM_MIN_SIDE and B * Hi * Wi >= _WGRAD_SLIM_MIN_M)
+
+
 def _wgrad_launch(lib, dtype, x, ldx, dy, lddy, dw, geom, Cin, Cout, accumulate=False, dbias=None, accumulate_bias=False, scale=1.0):
-    """dw (+)= dy^T . gather(x); with `dbias` the same launch also produces the bias gradient (column sums of dy)."""
+    """dw (+)= dy^T . gather(x); with `dbias` the same launch also produces the bias gradient (column sums of dy).  The
+    descriptor is packed once for either entry: psg_conv_wgrad, or psg_conv_wgrad_slim where `_wgrad_slim_route` says so."""
     B, Hi, Wi, Ho, Wo, ks, stride, pad = geom
     layout = weight_layout(dw)
     out = dw
@@ -349,13 +380,18 @@ def _wgrad_launch(lib, dtype, x, ldx, dy, lddy, dw, geom, Cin, Cout, accumulate=
                              int(accumulate_bias) if dbias is not None else 0, float(scale), 0, ldx, lddy,
                              x.data_ptr(), dy.data_ptr(), out.data_ptr(), dbias.data_ptr() if dbias is not None else 0, ws_ptr, ws_bytes)
     pack(0, 0)
-    need = lib.psg_conv_wgrad_workspace_bytes(wp)
+    if _wgrad_slim_route(dtype, geom, Cin, Cout):
+        query, entry, name = lib.psg_conv_wgrad_slim_workspace_bytes, lib.psg_conv_wgrad_slim, "psg_conv_wgrad_slim"
+        SlimStats.launches += 1
+    else:
+        query, entry, name = lib.psg_conv_wgrad_workspace_bytes, lib.psg_conv_wgrad, "psg_conv_wgrad"
+    need = query(wp)
     if need < 0:
-        check(-1, "psg_conv_wgrad_workspace_bytes")
+        check(-1, name + "_workspace_bytes")
     if need > 0:
         ws = _lib.workspace(need, x.device)
         pack(ws.data_ptr(), ws.numel())
-    check(lib.psg_conv_wgrad(wp, stream_ptr()), "psg_conv_wgrad")
+    check(entry(wp, stream_ptr()), name)
     if out is not dw:
         dw.copy_(out)
 
@@ -1892,6 +1928,36 @@ class _ImageOutFn(torch.autograd.Function):
 
 def image_out(y, cout):
     return _ImageOutFn.apply(y.contiguous(), cout)
+
+
+class _PadRowsFn(torch.autograd.Function):
+    """param [n, ...] fp32 -> [n + extra, ...] with zero rows appended (the decoder's trainable 3-channel image conv computed
+    in 8 output columns, vae_decoder.py:175).  Backward takes the first n rows of the padded gradient: the padding rows
+    contribute nothing to the output and receive nothing.  The weight-gradient kernel writes the PADDED shape, which a sink
+    entry of the parameter's own shape cannot take, so a registered parameter is delivered through one small copy (a few
+    hundred values) into its GradSink view - written on first use in a step, accumulated afterwards, as the kernels do."""
+
+    @staticmethod
+    def forward(ctx, param, extra):
+        ctx.param, ctx.n = param, param.shape[0]
+        out = torch.zeros((param.shape[0] + extra,) + tuple(param.shape[1:]), dtype=torch.float32, device=param.device)
+        out[:ctx.n].copy_(param.detach())
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        own = g[:ctx.n]
+        e = GradSink.get(ctx.param)
+        if e is None:
+            return own.clone(), None
+        e.view.add_(own) if e.written else e.view.copy_(own)
+        GradSink.done(e)
+        return None, None
+
+
+def pad_rows(param, extra):
+    """`param` with `extra` zero rows appended along dim 0, differentiable with respect to `param` (see `_PadRowsFn`)."""
+    return _PadRowsFn.apply(param, extra)
 
 
 def text_pool(text, dtype):

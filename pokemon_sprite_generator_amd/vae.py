@@ -9,14 +9,19 @@ shapes, so `load_state_dict` takes a stage-1 checkpoint's 'vae_state_dict' halve
 What is trainable: the ENCODER, opt-in.  `VAEEncoder(..., trainable=True)` has parameters that require grad and, with grad mode
 on, runs the autograd nodes of `ops`: `ops.conv4s2_relu` for the three 4x4 stride-2 convolutions (psg_conv4s2_dgrad /
 psg_conv4s2_wgrad, csrc/conv4s2.hip), `ResNetBlock.nhwc_grad`, `ops.conv2d` for the mu / logvar projections and `ops.reparam`
-for the sample - gradients reach all 70 of its parameters (stage 1, src/training/vae_trainer.py).  What is still missing:
-the DECODER's weight gradients (a decoder with a trainable parameter raises, `_require_frozen`), the stage-1 stepper (two
-learning rates, two clip norms, KL annealing) and the joint phase of stage 3.
+for the sample - gradients reach all 70 of its parameters (stage 1, src/training/vae_trainer.py).  The DECODER, opt-in as
+well: `VAEDecoder(..., trainable=True)` runs the same nodes with grad mode on and every one of its 144 parameters receives a
+gradient - the convolutions' and the k / v Linears' through psg_conv_wgrad or, for the high-resolution layers of blocks 4 and 5
+in bf16, psg_conv_wgrad_slim (`ops._deliver_gemm_grads`, `ops._wgrad_slim_route`), the GroupNorms' from psg_groupnorm_bwd_res; the 3-channel image convolution is computed in 8 output columns and its gradients come back at the
+parameter's own [3,32,3,3] / [3] shapes (`ops.pad_rows`).  `PokemonVAE(..., trainable=True)` builds both halves trainable and
+its `forward` carries the graph encoder -> latent -> decoder.  What is still missing: the stage-1 stepper (two learning
+rates, two clip norms, KL annealing, the arena / FusedAdamW wiring for the VAE) and the joint phase of stage 3
+(`FinalPokemonGenerator.unfreeze_vae_decoder` keeps raising).
 
-The DECODER is differentiable with respect to its inputs: stage 3 trains the text encoder through it
-(final_trainer.py:215-236), so when grad mode is on and `text_emb` or `latent` requires grad, `VAEDecoder.forward` runs the
-autograd nodes of `ops` (data gradients only; the cross-attention backward is psg_attn_bwd_longq).  Every other call runs the
-inference launches, unchanged.
+A default DECODER is frozen (a parameter switched to requires_grad by hand raises, `_require_frozen`) but differentiable with
+respect to its inputs: stage 3 trains the text encoder through it (final_trainer.py:215-236), so when grad mode is on and
+`text_emb` or `latent` requires grad, `VAEDecoder.forward` runs the autograd nodes of `ops` (data gradients only; the
+cross-attention backward is psg_attn_bwd_longq).  Every other call runs the inference launches, unchanged.
 
 Same classes / constructor and forward signatures as the reference: `ResNetBlock`, `CrossAttentionBlock`, `VAEEncoder`,
 `VAEDecoder`, `PokemonVAE`.  Everything runs channels-last in `compute_dtype` on the kernels of the U-Net path:
@@ -76,7 +81,7 @@ class ResNetBlock(nn.Module):
         return _conv(h, w2, self.conv2.bias, cout, cout, 3, 1, 1, residual=skip)
 
     def nhwc_grad(self, x):
-        """`nhwc` on the autograd nodes of `ops` (frozen weights: data gradients only)."""
+        """`nhwc` on the autograd nodes of `ops`: data gradients, and the gradient of every parameter that requires one."""
         h, xs = ops.group_norm_split(x, self.norm1.weight, self.norm1.bias, self.norm1.num_groups, self.norm1.eps, silu=True)
         h = ops.conv2d(h, self.conv1.weight, self.conv1.bias)
         h = ops.group_norm(h, self.norm2.weight, self.norm2.bias, self.norm2.num_groups, self.norm2.eps, silu=True)
@@ -243,9 +248,11 @@ class VAEEncoder(nn.Module):
 class VAEDecoder(nn.Module):
     """vae_decoder.py:128-222: 27 -> 54 -> 108 -> 215 with a text cross-attention in every block."""
 
-    def __init__(self, latent_dim: int = 8, text_dim: int = 256, output_channels: int = 3, compute_dtype: torch.dtype = torch.float32):
+    def __init__(self, latent_dim: int = 8, text_dim: int = 256, output_channels: int = 3, compute_dtype: torch.dtype = torch.float32,
+                 trainable: bool = False):
         super().__init__()
         self.latent_dim, self.text_dim = latent_dim, text_dim
+        self.trainable = bool(trainable)
         self.latent_proj = nn.Conv2d(latent_dim, 512, kernel_size=3, padding=1)
         chans = [(512, 512), (512, 256), (256, 128), (128, 64), (64, 32)]
         for i, (cin, cout) in enumerate(chans, start=1):
@@ -259,18 +266,29 @@ class VAEDecoder(nn.Module):
         self.final_conv = nn.Sequential(nn.GroupNorm(8, 32), nn.SiLU(), nn.Conv2d(32, output_channels, kernel_size=3, padding=1), nn.Tanh())
         self.compute_dtype = compute_dtype
         self._cache = {}
+        self._epoch = ops.WeightCache.epoch
+        self._fc_padded = None
+        for p in self.parameters():                  # frozen unless asked: weight gradients exist only on the trainable path
+            p.requires_grad_(self.trainable)
 
     def forward(self, latent: torch.Tensor, text_emb: torch.Tensor) -> torch.Tensor:
+        """latent [B,latent_dim,h,w], text_emb [B,S,text_dim] -> image [B,3,215,215] fp32.  A `trainable` decoder called with
+        grad mode on runs the autograd nodes of `ops` and its output carries gradients to all its parameters (and to `latent`
+        / `text_emb` when they ask); a frozen one runs them when an input requires grad; every other call runs the inference
+        launches."""
         if not latent.is_cuda:
             raise _lib.PsgError("VAEDecoder (MI355X build) needs GPU tensors; there is no CPU fallback")
-        if _wants_grad(latent, text_emb):
+        if (self.trainable and torch.is_grad_enabled()) or _wants_grad(latent, text_emb):
             return self._forward_grad(latent, text_emb)
         with torch.no_grad():
             return self._forward_infer(latent, text_emb)
 
     def _forward_grad(self, latent, text_emb):
-        """The decoder on the autograd nodes of `ops`: gradients reach `text_emb` and `latent`, never a VAE parameter."""
-        _require_frozen(self)
+        """The decoder on the autograd nodes of `ops`: gradients reach `text_emb` and `latent`, and - `trainable` only - every
+        parameter (stage 1, vae_trainer.py).  The blocks' `nhwc_grad` are called directly: their own `forward`s guard the
+        frozen entry."""
+        if not self.trainable:
+            _require_frozen(self)
         dt = self.compute_dtype
         text = text_emb.to(device=latent.device, dtype=dt).contiguous()
         lat = ops.nchw_to_nhwc_grad(latent, dt) if latent.requires_grad else ops.nchw_to_nhwc(latent, dt)
@@ -287,13 +305,29 @@ class VAEDecoder(nn.Module):
         x = ops.group_norm(x, gn.weight, gn.bias, gn.num_groups, gn.eps, silu=True)
         cout = conv.out_channels
         opad = (-cout) % 8          # 3 image channels in 8 columns (zero rows of weight): the data gradient gathers 16-byte chunks of dY
-        w8, b8 = _prepared(self._cache, ("fc_grad",), [conv.weight, conv.bias],
-                           lambda: (torch.nn.functional.pad(conv.weight.detach().float(), (0, 0, 0, 0, 0, 0, 0, opad)).contiguous(),
-                                    torch.nn.functional.pad(conv.bias.detach().float(), (0, opad)).contiguous()))
+        if self.trainable:
+            # Padded from the live parameters on every call - so an update of either kind (version counter, or raw pointers +
+            # WeightCache.invalidate) is always seen - and differentiable: the [8,32,3,3] / [8] gradients of the node come
+            # back as [3,32,3,3] / [3].  The previous call's padded weight leaves the WeightCache with it.
+            if self._fc_padded is not None:
+                ops.WeightCache.drop([self._fc_padded])
+            w8, b8 = ops.pad_rows(conv.weight, opad), ops.pad_rows(conv.bias, opad)
+            self._fc_padded = w8
+        else:
+            w8, b8 = _prepared(self._cache, ("fc_grad",), [conv.weight, conv.bias],
+                               lambda: (torch.nn.functional.pad(conv.weight.detach().float(), (0, 0, 0, 0, 0, 0, 0, opad)).contiguous(),
+                                        torch.nn.functional.pad(conv.bias.detach().float(), (0, opad)).contiguous()))
         y = ops.conv2d(x, w8, b8, act=ACT_TANH)
         return ops.image_out(y, cout)               # d tanh rides the conv node's epilogue backward; the padding columns get zeros
 
     def _forward_infer(self, latent, text_emb):
+        if self.trainable and self._epoch != ops.WeightCache.epoch:
+            # an optimizer wrote the parameters through raw pointers (WeightCache.invalidate): version counters did not move
+            self._cache.clear()
+            for m in self.modules():
+                if isinstance(m, (ResNetBlock, CrossAttentionBlock)):
+                    m._cache.clear()
+            self._epoch = ops.WeightCache.epoch
         dt = self.compute_dtype
         text = text_emb.detach().to(device=latent.device, dtype=dt).contiguous()
         wl = _prepared(self._cache, ("lp", dt), [self.latent_proj.weight], lambda: _prep(self.latent_proj.weight, dt))
@@ -319,19 +353,29 @@ class VAEDecoder(nn.Module):
 class PokemonVAE(nn.Module):
     """vae_decoder.py:225-291."""
 
-    def __init__(self, latent_dim: int = 8, text_dim: int = 256, compute_dtype: torch.dtype = torch.float32):
+    def __init__(self, latent_dim: int = 8, text_dim: int = 256, compute_dtype: torch.dtype = torch.float32, trainable: bool = False):
         super().__init__()
         self.latent_dim, self.text_dim = latent_dim, text_dim
-        self.encoder = VAEEncoder(input_channels=3, latent_dim=latent_dim, compute_dtype=compute_dtype)
-        self.decoder = VAEDecoder(latent_dim=latent_dim, text_dim=text_dim, output_channels=3, compute_dtype=compute_dtype)
+        self.trainable = bool(trainable)
+        self.encoder = VAEEncoder(input_channels=3, latent_dim=latent_dim, compute_dtype=compute_dtype, trainable=self.trainable)
+        self.decoder = VAEDecoder(latent_dim=latent_dim, text_dim=text_dim, output_channels=3, compute_dtype=compute_dtype,
+                                  trainable=self.trainable)
 
-    @torch.no_grad()
-    def forward(self, images: torch.Tensor, text_emb: torch.Tensor, mode: str = "train") -> dict:
+    def forward(self, images: torch.Tensor, text_emb: torch.Tensor, mode: str = "train", eps: torch.Tensor = None) -> dict:
+        """vae_decoder.py:236-269.  A `trainable` VAE called with grad mode on (stage 1, vae_trainer.py) returns
+        `reconstructed`, `latent`, `mu`, `logvar` with a graph to the parameters of both halves; every other call runs under
+        no_grad, as the frozen VAE always did.  `eps`: the encoder's reparameterisation noise (default: drawn)."""
+        if self.trainable and torch.is_grad_enabled():
+            return self._forward(images, text_emb, mode, eps)
+        with torch.no_grad():
+            return self._forward(images, text_emb, mode, eps)
+
+    def _forward(self, images, text_emb, mode, eps):
         if mode == "sample" or images is None:
             latent = torch.randn(text_emb.size(0), self.latent_dim, 27, 27, device=text_emb.device)
             mu = logvar = None
         else:
-            latent, mu, logvar = self.encoder(images)
+            latent, mu, logvar = self.encoder(images, eps=eps)
             if mode == "generate":
                 latent = mu
         return {"reconstructed": self.decoder(latent, text_emb), "latent": latent, "mu": mu, "logvar": logvar}
