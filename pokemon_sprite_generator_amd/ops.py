@@ -132,14 +132,28 @@ class WeightCache:
 
     @classmethod
     def drop(cls, params):
-        """Release the prepared copies of these parameters only (their storage is about to move)."""
-        for p in params:
-            cls._entries.pop(id(p), None)
+        """Release the prepared copies of these parameters only (their storage is about to move, or their module is gone)."""
+        ids = {id(p) for p in params}
+        ids |= {id(e[1]) for k, e in cls._entries.items() if isinstance(k, tuple) and k[0] in ids}      # what was `derived` from them
+        for k in [k for k in cls._entries if k in ids or (isinstance(k, tuple) and k[0] in ids)]:
+            del cls._entries[k]
 
     @classmethod
-    def get(cls, w, dtype, need_wd):
+    def derived(cls, param, tag, build, fresh=False):
+        """`build()`, an fp32 tensor made from `param` (a zero-padded copy) that goes through `conv2d` like any weight: rebuilt, and
+        the predecessor's own entry dropped, when the parameter's stamp moves or on every call (`fresh`: a differentiable copy)."""
+        key = (id(param), tag)
+        stamp = (param.data_ptr(), param._version, cls.epoch, torch.float32, 0)
+        ent = cls._entries.get(key)
+        if ent is None or ent[0] != stamp or fresh:
+            cls._entries.pop(id(ent[1]) if ent else None, None)
+            ent = cls._entries[key] = (stamp, build(), None, param, None)
+        return ent[1]
+
+    @classmethod
+    def get(cls, w, dtype, need_wd, pad_in=0):
         key = id(w)
-        stamp = (w.data_ptr(), w._version, cls.epoch, dtype)
+        stamp = (w.data_ptr(), w._version, cls.epoch, dtype, pad_in)
         ent = cls._entries.get(key)
         if ent is not None and ent[0] == stamp and (ent[2] is not None or not need_wd):
             return ent[1], ent[2]
@@ -162,15 +176,17 @@ class WeightCache:
                     wd = None                      # (stale contents: dropped until a caller needs it again)
                 cls._entries[key] = (stamp, wf, wd, w, ent[4])
                 return wf, wd
-        O, I = w.shape[0], w.shape[1]
+        O, I = w.shape[0], w.shape[1] + pad_in
         ks = w.shape[2] if w.dim() == 4 else 1
         code = dtype_code(dtype)
         kpf = lib.psg_kpad(ks * ks * I, code)
         kpd = lib.psg_kpad(ks * ks * O, code)
         src = w.detach()
+        if ks == 4:                                # psg_prep_weight takes 4x4 as OHWI, O and I multiples of 4 (pad_in: the image's 3 in 8)
+            src = torch.nn.functional.pad(src.float(), (0, 0, 0, 0, 0, pad_in)).contiguous(memory_format=torch.channels_last)
         layout = weight_layout(src)
         shadow = None
-        if dtype == torch.bfloat16 and kpf == ks * ks * I and O % 4 == 0 and I % 4 == 0 and (layout == W_OHWI or ks == 1):
+        if dtype == torch.bfloat16 and kpf == ks * ks * I and O % 4 == 0 and I % 4 == 0 and (layout == W_OHWI or ks == 1) and not pad_in:
             shadow = ParamShadow.lookup(w)
         wd = torch.empty((I, kpd), dtype=dtype, device=w.device) if need_wd else None
         if shadow is not None:                     # the AdamW pass already wrote the forward operand
@@ -774,26 +790,30 @@ class _ConvFn(torch.autograd.Function):
         return dx, dw, db, dra, d_res, None, None, None, None, None, None
 
 
+class _NoNode:
+    """An autograd ctx's stand-in while grad mode is off: `_node` runs the node's forward body as it is, without the cost of
+    `Function.apply` per launch (a batch-1 VAE forward is host-bound); nothing is kept for a backward."""
+
+    def __init__(self, args):
+        self.needs_input_grad = [getattr(a, "requires_grad", False) for a in args]      # as apply would say
+
+    def save_for_backward(self, *tensors):
+        pass
+
+
+def _node(fn, *args):
+    return fn.apply(*args) if torch.is_grad_enabled() else fn.forward(_NoNode(args), *args)
+
+
 def conv2d(x, weight, bias=None, stride=1, rowadd=None, residual=None, act=ACT_NONE, alpha=1.0, drop_p=0.0, seed=0, out=None):
     """x: [B,H,W,Cin] channels-last; weight: fp32 OIHW parameter (3x3 pad 1, or 1x1).  nn.Conv2d of unet.py.
     `out`: a row-strided tensor of the output's shape to produce the result in (`OutSlot`, see `concat_slot`)."""
-    return _ConvFn.apply(x, weight, bias, rowadd, residual, stride, act, alpha, drop_p, seed, out)
+    return _node(_ConvFn, x, weight, bias, rowadd, residual, stride, act, alpha, drop_p, seed, out)
 
 
 def linear(x, weight, bias=None, residual=None, act=ACT_NONE, alpha=1.0, drop_p=0.0, seed=0, out=None):
     """x: [..., Cin]; weight: fp32 [Cout, Cin] parameter.  nn.Linear of unet.py, with the fused epilogue."""
-    return _ConvFn.apply(x, weight, bias, None, residual, 1, act, alpha, drop_p, seed, out)
-
-
-def _prepared_4s2(cache, key, weight, dtype, pad_in, need_wd):
-    """(wf, wd) of a trainable 4x4 stride-2 conv weight: `prep_weight`'s forward operand and, when asked, the data-gradient
-    operand [Cin][Kpad(16 Cout)]; kept in `cache` until the parameter's version counter or WeightCache.epoch moves."""
-    stamp = (weight.data_ptr(), weight._version, WeightCache.epoch)
-    ent = cache.get(key)
-    if ent is None or ent[0] != stamp or (need_wd and ent[2] is None):
-        ent = (stamp,) + prep_weight(weight, dtype, pad_in=pad_in, with_wd=bool(need_wd))
-        cache[key] = ent
-    return ent[1], ent[2]
+    return _node(_ConvFn, x, weight, bias, None, residual, 1, act, alpha, drop_p, seed, out)
 
 
 class _Conv4s2Fn(torch.autograd.Function):
@@ -804,7 +824,7 @@ class _Conv4s2Fn(torch.autograd.Function):
     carry more channels than the weight (the image's 3 in 8 columns): the extra ones are zero and get no weight gradient."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, pad, cache, key):
+    def forward(ctx, x, weight, bias, pad):
         lib = _lib_for(x)
         dtype = x.dtype
         Cout, cin_real = weight.shape[0], weight.shape[1]
@@ -813,7 +833,7 @@ class _Conv4s2Fn(torch.autograd.Function):
             raise _lib.PsgError(f"conv4s2_relu: weight {tuple(weight.shape)} on an input of {Cin} channels")
         xr, ldx = _rows(x)
         geom = _conv_geom(x, 4, 2, pad)
-        wf, wd = _prepared_4s2(cache, key, weight, dtype, Cin - cin_real, ctx.needs_input_grad[0])
+        wf, wd = WeightCache.get(weight, dtype, ctx.needs_input_grad[0], pad_in=Cin - cin_real)
         y = torch.empty((geom[0], geom[3], geom[4], Cout), dtype=dtype, device=x.device)
         _conv_launch(lib, dtype, xr, ldx, wf, 0, y, Cout, geom, Cin, Cout, bias=bias, act=ACT_RELU)
         ctx.save_for_backward(xr, y)
@@ -862,13 +882,13 @@ class _Conv4s2Fn(torch.autograd.Function):
             _colsum(lib, g, Cout, M, 1, Cout, dtype, torch.float32, out=bo, accumulate=bacc)
         if want_b:
             db = _param_ret(bo, be)
-        return dx, dw, db, None, None, None
+        return dx, dw, db, None
 
 
-def conv4s2_relu(x, weight, bias, pad, cache, key):
+def conv4s2_relu(x, weight, bias, pad):
     """relu(nn.Conv2d(kernel_size=4, stride=2, padding=pad)(x)) on channels-last x [B,H,W,Cin >= weight's]; weight: the fp32
-    OIHW parameter.  `cache` / `key`: where the caller keeps the prepared operands (see `_prepared_4s2`)."""
-    return _Conv4s2Fn.apply(x, weight, bias, pad, cache, key)
+    OIHW parameter."""
+    return _Conv4s2Fn.apply(x, weight, bias, pad)
 
 
 class _ReparamFn(torch.autograd.Function):
@@ -1609,24 +1629,19 @@ def conv_infer(x, wf, bias, Cin, Cout, ks=1, stride=1, pad=0, act=ACT_NONE, resi
     return y
 
 
-def prep_weight(w, dtype, pad_in=0, pad_out=0, with_wd=None):
-    """fp32 OIHW parameter -> prepared forward weight [O'][Kpad] in `dtype`; optional zero padding of Cin / Cout.
-    `with_wd` given (True / False): returns (wf, wd), wd the data-gradient operand [I'][Kpad'] from the same launch or None."""
+def prep_weight(w, dtype, pad_in=0):
+    """fp32 OIHW parameter -> prepared forward weight [O][Kpad] in `dtype`; optional zero padding of Cin."""
     lib = _lib_for(w)
     O, I, kh, kw = w.shape
     src = w.detach().float()
-    if pad_in or pad_out:
-        src = torch.nn.functional.pad(src, (0, 0, 0, 0, 0, pad_in, 0, pad_out))
-        O, I = O + pad_out, I + pad_in
+    if pad_in:
+        src, I = torch.nn.functional.pad(src, (0, 0, 0, 0, 0, pad_in)), I + pad_in
     src = src.contiguous(memory_format=torch.channels_last)           # OHWI memory: the layout every kernel-side path takes
     code = dtype_code(dtype)
     kp = lib.psg_kpad(kh * kw * I, code)
     wf = torch.empty((O, kp), dtype=dtype, device=w.device)
-    wd = torch.empty((I, lib.psg_kpad(kh * kw * O, code)), dtype=dtype, device=w.device) if with_wd else None
-    check(lib.psg_prep_weight(ptr(src), dtype_code(torch.float32), W_OHWI, ptr(wf), ptr(wd), O, I, kh, code, stream_ptr()),
-          "psg_prep_weight")
-    return wf if with_wd is None else (wf, wd)
-
+    check(lib.psg_prep_weight(ptr(src), dtype_code(torch.float32), W_OHWI, ptr(wf), None, O, I, kh, code, stream_ptr()), "psg_prep_weight")
+    return wf
 
 
 # ---------------------------------------------------------------------------

@@ -43,7 +43,7 @@ import torch.nn as nn
 from . import _lib, ops
 from ._lib import ACT_GELU
 from .unet import _SeedStream
-from .vae import _prep, _prepared
+from .ops import prep_weight as _prep, prepared as _prepared
 
 # keys of a `bert_config` dict (transformers.BertConfig attribute names)
 CONFIG_KEYS = ("hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size", "vocab_size",

@@ -6,22 +6,30 @@ demo decode with it.  By default its parameters are never trained here (they are
 shapes, so `load_state_dict` takes a stage-1 checkpoint's 'vae_state_dict' halves unchanged), and the encoder runs under
 `torch.no_grad()`.
 
-What is trainable: the ENCODER, opt-in.  `VAEEncoder(..., trainable=True)` has parameters that require grad and, with grad mode
-on, runs the autograd nodes of `ops`: `ops.conv4s2_relu` for the three 4x4 stride-2 convolutions (psg_conv4s2_dgrad /
-psg_conv4s2_wgrad, csrc/conv4s2.hip), `ResNetBlock.nhwc_grad`, `ops.conv2d` for the mu / logvar projections and `ops.reparam`
-for the sample - gradients reach all 70 of its parameters (stage 1, src/training/vae_trainer.py).  The DECODER, opt-in as
-well: `VAEDecoder(..., trainable=True)` runs the same nodes with grad mode on and every one of its 144 parameters receives a
-gradient - the convolutions' and the k / v Linears' through psg_conv_wgrad or, for the high-resolution layers of blocks 4 and 5
-in bf16, psg_conv_wgrad_slim (`ops._deliver_gemm_grads`, `ops._wgrad_slim_route`), the GroupNorms' from psg_groupnorm_bwd_res; the 3-channel image convolution is computed in 8 output columns and its gradients come back at the
-parameter's own [3,32,3,3] / [3] shapes (`ops.pad_rows`).  `PokemonVAE(..., trainable=True)` builds both halves trainable and
-its `forward` carries the graph encoder -> latent -> decoder.  What is still missing: the stage-1 stepper (two learning
-rates, two clip norms, KL annealing, the arena / FusedAdamW wiring for the VAE) and the joint phase of stage 3
-(`FinalPokemonGenerator.unfreeze_vae_decoder` keeps raising).
+One forward per module.  Every module has ONE body, written on the autograd nodes of `ops` (`ops.conv2d`, `ops.linear`,
+`ops.conv4s2_relu` for the encoder's three 4x4 stride-2 convolutions, `ops.group_norm[_split]`, `ops.attention_cross_longq`,
+`ops.reparam`, `ops.image_out`); the public `forward`s only decide the grad mode.  Under no_grad a node issues its forward launch
+and keeps nothing, so inference and training run the same launches in the same order.  Every prepared weight comes from
+`ops.WeightCache` under its one stamp (storage pointer, version counter, the epoch that `WeightCache.invalidate()` bumps for
+optimizers writing through raw pointers, dtype): a block called through its own `forward` sees an update of either kind, as
+the whole encoder / decoder does.  The padded operands enter the same cache: the first convolution's Cin 3 -> 8 as
+`WeightCache.get(..., pad_in=)`, the image convolution's Cout 3 -> 4 | 8 as `WeightCache.derived` copies
+(`VAEDecoder._image_conv`).  A module's entries are released when it is collected (`_release_on_collect`).
+
+What is trainable, opt-in: `VAEEncoder(..., trainable=True)` has parameters that require grad and, called with grad mode on,
+gradients reach all 70 of them (stage 1, src/training/vae_trainer.py; psg_conv4s2_dgrad / psg_conv4s2_wgrad, csrc/conv4s2.hip).
+`VAEDecoder(..., trainable=True)` likewise: every one of its 144 parameters receives a gradient - the convolutions' and the
+k / v Linears' through psg_conv_wgrad or, for the high-resolution layers of blocks 4 and 5 in bf16, psg_conv_wgrad_slim
+(`ops._deliver_gemm_grads`, `ops._wgrad_slim_route`), the GroupNorms' from psg_groupnorm_bwd_res; the 3-channel image
+convolution is computed in 8 output columns and its gradients come back at the parameter's own [3,32,3,3] / [3] shapes
+(`ops.pad_rows`).  `PokemonVAE(..., trainable=True)` builds both halves trainable and its `forward` carries the graph encoder
+-> latent -> decoder.  What is still missing: the stage-1 stepper (two learning rates, two clip norms, KL annealing, the arena /
+FusedAdamW wiring for the VAE) and the joint phase of stage 3 (`FinalPokemonGenerator.unfreeze_vae_decoder` keeps raising).
 
 A default DECODER is frozen (a parameter switched to requires_grad by hand raises, `_require_frozen`) but differentiable with
 respect to its inputs: stage 3 trains the text encoder through it (final_trainer.py:215-236), so when grad mode is on and
-`text_emb` or `latent` requires grad, `VAEDecoder.forward` runs the autograd nodes of `ops` (data gradients only; the
-cross-attention backward is psg_attn_bwd_longq).  Every other call runs the inference launches, unchanged.
+`text_emb` or `latent` requires grad, `VAEDecoder.forward` keeps grad mode on (data gradients only; the cross-attention
+backward is psg_attn_bwd_longq).  Every other call runs under no_grad.
 
 Same classes / constructor and forward signatures as the reference: `ResNetBlock`, `CrossAttentionBlock`, `VAEEncoder`,
 `VAEDecoder`, `PokemonVAE`.  Everything runs channels-last in `compute_dtype` on the kernels of the U-Net path:
@@ -30,18 +38,22 @@ GroupNorm+SiLU, bilinear upsampling and the attention core.  Reference quirks ke
 cross-attention reshapes the [B, S, C] key / value projections straight to [B, heads, head_dim, S]
 (vae_decoder.py:56-57 - a reinterpretation of memory, not a transpose), and the encoder returns a SAMPLED latent.
 """
-import math
+import weakref
 
 import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from ._lib import ACT_NONE, ACT_RELU, ACT_SILU, ACT_TANH, check, ptr, stream_ptr
-from .ops import conv_infer as _conv, prep_weight as _prep, prepared as _prepared
+from ._lib import ACT_TANH
 
 
 def _wants_grad(*tensors):
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _release_on_collect(module):
+    """`ops.WeightCache` entries keep their parameter alive: a module's are dropped when the module is collected."""
+    weakref.finalize(module, ops.WeightCache.drop, list(module.parameters()))
 
 
 def _require_frozen(module):
@@ -63,25 +75,11 @@ class ResNetBlock(nn.Module):
         self.conv2 = nn.Conv2d(out_channels, out_channels, kernel_size=3, padding=1)
         self.dropout = nn.Dropout(dropout)
         self.shortcut = nn.Conv2d(in_channels, out_channels, kernel_size=1) if in_channels != out_channels else nn.Identity()
-        self._cache = {}
+        _release_on_collect(self)
 
     def nhwc(self, x):
-        dt = x.dtype
-        cin, cout = self.conv1.in_channels, self.conv1.out_channels
-        w1 = _prepared(self._cache, ("c1", dt), [self.conv1.weight], lambda: _prep(self.conv1.weight, dt))
-        w2 = _prepared(self._cache, ("c2", dt), [self.conv2.weight], lambda: _prep(self.conv2.weight, dt))
-        h = ops.group_norm(x, self.norm1.weight, self.norm1.bias, self.norm1.num_groups, self.norm1.eps, silu=True)
-        h = _conv(h, w1, self.conv1.bias, cin, cout, 3, 1, 1)
-        h = ops.group_norm(h, self.norm2.weight, self.norm2.bias, self.norm2.num_groups, self.norm2.eps, silu=True)
-        if isinstance(self.shortcut, nn.Conv2d):
-            ws = _prepared(self._cache, ("sc", dt), [self.shortcut.weight], lambda: _prep(self.shortcut.weight, dt))
-            skip = _conv(x, ws, self.shortcut.bias, cin, cout, 1, 1, 0)
-        else:
-            skip = x
-        return _conv(h, w2, self.conv2.bias, cout, cout, 3, 1, 1, residual=skip)
-
-    def nhwc_grad(self, x):
-        """`nhwc` on the autograd nodes of `ops`: data gradients, and the gradient of every parameter that requires one."""
+        """x [B,H,W,C] in the compute dtype, on the nodes of `ops`: with grad mode on, data gradients and the gradient of every
+        parameter that requires one."""
         h, xs = ops.group_norm_split(x, self.norm1.weight, self.norm1.bias, self.norm1.num_groups, self.norm1.eps, silu=True)
         h = ops.conv2d(h, self.conv1.weight, self.conv1.bias)
         h = ops.group_norm(h, self.norm2.weight, self.norm2.bias, self.norm2.num_groups, self.norm2.eps, silu=True)
@@ -92,7 +90,7 @@ class ResNetBlock(nn.Module):
         dt = getattr(self, "compute_dtype", torch.float32)
         if _wants_grad(x):
             _require_frozen(self)
-            return ops.nhwc_to_nchw(self.nhwc_grad(ops.nchw_to_nhwc_grad(x, dt)))
+            return ops.nhwc_to_nchw(self.nhwc(ops.nchw_to_nhwc_grad(x, dt)))
         with torch.no_grad():
             return ops.nhwc_to_nchw(self.nhwc(ops.nchw_to_nhwc(x, dt)))
 
@@ -109,38 +107,20 @@ class CrossAttentionBlock(nn.Module):
         self.k = nn.Linear(text_dim, channels)
         self.v = nn.Linear(text_dim, channels)
         self.proj = nn.Conv2d(channels, channels, kernel_size=1)
-        self._cache = {}
+        _release_on_collect(self)
 
     def nhwc(self, x, text):
-        """x [B,H,W,C], text [B,S,text_dim] in the compute dtype."""
-        dt = x.dtype
-        B, H, W, C = x.shape
-        S = text.shape[1]
-        wq = _prepared(self._cache, ("q", dt), [self.q.weight], lambda: _prep(self.q.weight, dt))
-        wp = _prepared(self._cache, ("p", dt), [self.proj.weight], lambda: _prep(self.proj.weight, dt))
-        wk = _prepared(self._cache, ("k", dt), [self.k.weight], lambda: _prep(self.k.weight[:, :, None, None], dt))
-        wv = _prepared(self._cache, ("v", dt), [self.v.weight], lambda: _prep(self.v.weight[:, :, None, None], dt))
-        xn = ops.group_norm(x, self.norm.weight, self.norm.bias, self.norm.num_groups, self.norm.eps)
-        q = _conv(xn, wq, self.q.bias, C, C, 1, 1, 0).reshape(B, H * W, C)
-        t4 = text.reshape(B, S, 1, self.text_dim)
-        k = _conv(t4, wk, self.k.bias, self.text_dim, C, 1, 1, 0).reshape(B, S, C)
-        v = _conv(t4, wv, self.v.bias, self.text_dim, C, 1, 1, 0).reshape(B, S, C)
-        # vae_decoder.py:56-57: `.reshape(b, heads, head_dim, -1)` of a [b, S, C] tensor reads its memory as [C][S]:
-        # key token s' of channel c is element c*S + s' of the projection's buffer.  The attention kernel wants [S][C] rows.
-        kv = torch.cat([k.reshape(B, C, S).transpose(1, 2), v.reshape(B, C, S).transpose(1, 2)], dim=-1).contiguous()
-        o = ops.attention_cross(q, kv, self.num_heads)             # softmax(q^T k / sqrt(head_dim)) v, per head
-        y = _conv(o.reshape(B, H, W, C), wp, self.proj.bias, C, C, 1, 1, 0, residual=x)
-        return y
-
-    def nhwc_grad(self, x, text):
-        """`nhwc` on the autograd nodes of `ops`.  The [B,S,C] -> [C][S] reinterpretation is a reshape + transpose of views,
-        differentiated by autograd as such; the attention core's backward is psg_attn_bwd_longq."""
+        """x [B,H,W,C], text [B,S,text_dim] in the compute dtype, on the nodes of `ops`; the attention core's backward is
+        psg_attn_bwd_longq."""
         B, H, W, C = x.shape
         S = text.shape[1]
         xn, xs = ops.group_norm_split(x, self.norm.weight, self.norm.bias, self.norm.num_groups, self.norm.eps)
         q = ops.conv2d(xn, self.q.weight, self.q.bias).reshape(B, H * W, C)
         k = ops.linear(text, self.k.weight, self.k.bias)
         v = ops.linear(text, self.v.weight, self.v.bias)
+        # vae_decoder.py:56-57: `.reshape(b, heads, head_dim, -1)` of a [b, S, C] tensor reads its memory as [C][S]:
+        # key token s' of channel c is element c*S + s' of the projection's buffer.  The attention kernel wants [S][C] rows:
+        # a reshape + transpose of views, differentiated by autograd as such.
         kv = torch.cat([k.reshape(B, C, S).transpose(1, 2), v.reshape(B, C, S).transpose(1, 2)], dim=-1).contiguous()
         o = ops.attention_cross_longq(q, kv, self.num_heads)
         return ops.conv2d(o.reshape(B, H, W, C), self.proj.weight, self.proj.bias, residual=xs)
@@ -150,9 +130,9 @@ class CrossAttentionBlock(nn.Module):
         if _wants_grad(x, text_emb):
             _require_frozen(self)
             xin = ops.nchw_to_nhwc_grad(x, dt) if x.requires_grad else ops.nchw_to_nhwc(x, dt)
-            return ops.nhwc_to_nchw(self.nhwc_grad(xin, text_emb.to(dt).contiguous()))
+            return ops.nhwc_to_nchw(self.nhwc(xin, text_emb.to(dt).contiguous()))
         with torch.no_grad():
-            return ops.nhwc_to_nchw(self.nhwc(ops.nchw_to_nhwc(x, dt), text_emb.to(dt)))
+            return ops.nhwc_to_nchw(self.nhwc(ops.nchw_to_nhwc(x, dt), text_emb.to(dt).contiguous()))
 
 
 class VAEEncoder(nn.Module):
@@ -172,77 +152,45 @@ class VAEEncoder(nn.Module):
         self.mu_proj = nn.Conv2d(512, latent_dim, kernel_size=3, padding=1)
         self.logvar_proj = nn.Conv2d(512, latent_dim, kernel_size=3, padding=1)
         self.compute_dtype = compute_dtype
-        self._cache = {}
-        self._epoch = ops.WeightCache.epoch
-        for p in self.parameters():                  # frozen unless asked: gradients exist only on the trainable path
+        for p in self.parameters():                  # frozen unless asked
             p.requires_grad_(self.trainable)
+        _release_on_collect(self)
 
     def forward(self, x: torch.Tensor, eps: torch.Tensor = None, generator: torch.Generator = None):
         """x [B,3,H,W] -> (latent, mu, logvar), each [B,latent_dim,h,w] fp32 (215 -> 27).  `eps` (default: randn of mu's
         shape, from `generator` when given - a data-parallel rank's own stream) is the reparameterisation noise the
-        reference draws with randn_like (:121).  A `trainable` encoder called with grad mode on runs the autograd nodes of
-        `ops` and its outputs carry gradients to all its parameters; every other call runs the inference launches."""
+        reference draws with randn_like (:121).  A `trainable` encoder called with grad mode on returns outputs that carry
+        gradients to all its parameters; every other call runs under no_grad."""
         if not x.is_cuda:
             raise _lib.PsgError("VAEEncoder (MI355X build) needs GPU tensors; there is no CPU fallback")
         if self.trainable and torch.is_grad_enabled():
-            return self._forward_train(x, eps, generator)
+            if x.requires_grad:
+                raise _lib.PsgError("VAEEncoder: the image has requires_grad=True, but nothing differentiates with respect to the image "
+                                    "(the first convolution's data gradient is never computed); detach it")
+            return self._forward(x, eps, generator)
         with torch.no_grad():
-            return self._forward_infer(x, eps, generator)
+            return self._forward(x, eps, generator)
 
     def _draw_eps(self, mu, eps, generator):
         if eps is None:
             eps = torch.randn_like(mu) if generator is None else torch.randn(mu.shape, dtype=mu.dtype, device=mu.device, generator=generator)
         return eps.detach().to(device=mu.device, dtype=torch.float32).contiguous()
 
-    def _forward_train(self, x, eps, generator):
-        """The encoder on the autograd nodes of `ops` (stage 1, vae_trainer.py): the three 4x4 stride-2 convolutions are
-        `ops.conv4s2_relu` (own gradient kernels), everything else the nodes the decoder and the U-Net already use."""
-        if x.requires_grad:
-            raise _lib.PsgError("VAEEncoder: the image has requires_grad=True, but nothing differentiates with respect to the image "
-                                "(the first convolution's data gradient is never computed); detach it")
+    def _forward(self, x, eps, generator):
+        """The three 4x4 stride-2 convolutions (+ the ReLU after each) are `ops.conv4s2_relu` (own gradient kernels, stage 1,
+        vae_trainer.py), everything else the nodes the decoder and the U-Net use."""
         dt = self.compute_dtype
         Cin = x.shape[1]
-        cpad = (-Cin) % 8
-        h = ops.nchw_to_nhwc(x, dt, width=Cin + cpad)
-        for i, m in enumerate(self.encoder):
+        # image -> channels-last with the channel count padded to one 16-byte chunk (zeros; conv4s2_relu pads the weight alike)
+        h = ops.nchw_to_nhwc(x, dt, width=Cin + (-Cin) % 8)
+        for m in self.encoder:
             if isinstance(m, nn.Conv2d):
-                h = ops.conv4s2_relu(h, m.weight, m.bias, m.padding[0], self._cache, (i, dt, "train"))
+                h = ops.conv4s2_relu(h, m.weight, m.bias, m.padding[0])
             elif isinstance(m, ResNetBlock):
-                h = m.nhwc_grad(h)               # (called directly: ResNetBlock.forward guards its own, frozen, entry)
+                h = m.nhwc(h)                    # (called directly: ResNetBlock.forward guards its own, frozen, entry)
         mu = ops.nhwc_to_nchw(ops.conv2d(h, self.mu_proj.weight, self.mu_proj.bias))
         logvar = ops.nhwc_to_nchw(ops.conv2d(h, self.logvar_proj.weight, self.logvar_proj.bias))
         return ops.reparam(mu, logvar, self._draw_eps(mu, eps, generator)), mu, logvar
-
-    def _forward_infer(self, x, eps, generator):
-        if self.trainable and self._epoch != ops.WeightCache.epoch:
-            # an optimizer wrote the parameters through raw pointers (WeightCache.invalidate): version counters did not move
-            self._cache.clear()
-            for m in self.encoder:
-                if isinstance(m, ResNetBlock):
-                    m._cache.clear()
-            self._epoch = ops.WeightCache.epoch
-        dt = self.compute_dtype
-        Cin = x.shape[1]
-        # image -> channels-last with the channel count padded to one 16-byte chunk (zeros; the weights are padded alike)
-        cpad = (-Cin) % 8
-        h = ops.nchw_to_nhwc(x, dt, width=Cin + cpad)
-        for i, m in enumerate(self.encoder):
-            if isinstance(m, nn.Conv2d):
-                pin = cpad if i == 0 else 0
-                wf = _prepared(self._cache, (i, dt), [m.weight], lambda m=m, pin=pin: _prep(m.weight, dt, pad_in=pin))
-                h = _conv(h, wf, m.bias, m.in_channels + pin, m.out_channels, 4, 2, m.padding[0], act=ACT_RELU)   # Conv2d + the ReLU after it
-            elif isinstance(m, ResNetBlock):
-                h = m.nhwc(h)
-        wm = _prepared(self._cache, ("mu", dt), [self.mu_proj.weight], lambda: _prep(self.mu_proj.weight, dt))
-        wl = _prepared(self._cache, ("lv", dt), [self.logvar_proj.weight], lambda: _prep(self.logvar_proj.weight, dt))
-        mu = ops.nhwc_to_nchw(_conv(h, wm, self.mu_proj.bias, 512, self.latent_dim, 3, 1, 1))
-        logvar = ops.nhwc_to_nchw(_conv(h, wl, self.logvar_proj.bias, 512, self.latent_dim, 3, 1, 1))
-        if eps is None:
-            eps = torch.randn_like(mu) if generator is None else torch.randn(mu.shape, dtype=mu.dtype, device=mu.device, generator=generator)
-        eps = eps.to(device=mu.device, dtype=torch.float32).contiguous()
-        latent = torch.empty_like(mu)
-        check(ops._lib_for(mu).psg_reparam_f32(ptr(mu), ptr(logvar), ptr(eps), ptr(latent), mu.numel(), stream_ptr()), "psg_reparam_f32")
-        return latent, mu, logvar
 
 
 class VAEDecoder(nn.Module):
@@ -265,73 +213,43 @@ class VAEDecoder(nn.Module):
                 setattr(self, f"block{i}_upsample", nn.Upsample(size=(215, 215), mode="bilinear", align_corners=False))
         self.final_conv = nn.Sequential(nn.GroupNorm(8, 32), nn.SiLU(), nn.Conv2d(32, output_channels, kernel_size=3, padding=1), nn.Tanh())
         self.compute_dtype = compute_dtype
-        self._cache = {}
-        self._epoch = ops.WeightCache.epoch
-        self._fc_padded = None
-        for p in self.parameters():                  # frozen unless asked: weight gradients exist only on the trainable path
+        for p in self.parameters():                  # frozen unless asked
             p.requires_grad_(self.trainable)
+        _release_on_collect(self)
 
     def forward(self, latent: torch.Tensor, text_emb: torch.Tensor) -> torch.Tensor:
         """latent [B,latent_dim,h,w], text_emb [B,S,text_dim] -> image [B,3,215,215] fp32.  A `trainable` decoder called with
-        grad mode on runs the autograd nodes of `ops` and its output carries gradients to all its parameters (and to `latent`
-        / `text_emb` when they ask); a frozen one runs them when an input requires grad; every other call runs the inference
-        launches."""
+        grad mode on returns an image that carries gradients to all its parameters (stage 1, vae_trainer.py) and to `latent` /
+        `text_emb` when they ask; a frozen one carries the inputs' gradients when an input requires grad (data gradients only:
+        `_require_frozen`); every other call runs under no_grad."""
         if not latent.is_cuda:
             raise _lib.PsgError("VAEDecoder (MI355X build) needs GPU tensors; there is no CPU fallback")
         if (self.trainable and torch.is_grad_enabled()) or _wants_grad(latent, text_emb):
-            return self._forward_grad(latent, text_emb)
+            if not self.trainable:
+                _require_frozen(self)
+            return self._forward(latent, text_emb)
         with torch.no_grad():
-            return self._forward_infer(latent, text_emb)
+            return self._forward(latent, text_emb)
 
-    def _forward_grad(self, latent, text_emb):
-        """The decoder on the autograd nodes of `ops`: gradients reach `text_emb` and `latent`, and - `trainable` only - every
-        parameter (stage 1, vae_trainer.py).  The blocks' `nhwc_grad` are called directly: their own `forward`s guard the
-        frozen entry."""
-        if not self.trainable:
-            _require_frozen(self)
+    def _image_conv(self, grad):
+        """(w, b) of the image convolution: its 3 channels computed in 4 output columns (zero rows of weight), or in 8 when a
+        gradient is wanted - the data gradient gathers 16-byte chunks of dY; `image_out` reads the width off the result.  The padded fp32 copies follow the
+        parameters' WeightCache stamp; a `trainable` decoder's are differentiable and made from the live parameters on every
+        call: the [8,32,3,3] / [8] gradients of the node come back as [3,32,3,3] / [3]."""
+        conv = self.final_conv[2]
+        width = 8 if grad else 4
+        extra = (-conv.out_channels) % width
+        live = grad and self.trainable
+        pad = (lambda p: ops.pad_rows(p, extra)) if live else (
+            lambda p: torch.nn.functional.pad(p.detach().float(), (0, 0) * (p.dim() - 1) + (0, extra)).contiguous())
+        return [ops.WeightCache.derived(p, width, lambda: pad(p), fresh=live) for p in (conv.weight, conv.bias)]
+
+    def _forward(self, latent, text_emb):
+        """The blocks' `nhwc` are called directly: their own `forward`s guard the frozen entry."""
         dt = self.compute_dtype
         text = text_emb.to(device=latent.device, dtype=dt).contiguous()
-        lat = ops.nchw_to_nhwc_grad(latent, dt) if latent.requires_grad else ops.nchw_to_nhwc(latent, dt)
+        lat = ops.nchw_to_nhwc_grad(latent, dt) if _wants_grad(latent) else ops.nchw_to_nhwc(latent, dt)
         x = ops.conv2d(lat, self.latent_proj.weight, self.latent_proj.bias)
-        for i in range(1, 6):
-            x = getattr(self, f"block{i}_resnet1").nhwc_grad(x)
-            x = getattr(self, f"block{i}_attn").nhwc_grad(x, text)
-            x = getattr(self, f"block{i}_resnet2").nhwc_grad(x)
-            up = getattr(self, f"block{i}_upsample", None)
-            if up is not None:
-                size = up.size if up.size is not None else (int(x.shape[1] * up.scale_factor), int(x.shape[2] * up.scale_factor))
-                x = ops.upsample_bilinear(x, size)
-        gn, conv = self.final_conv[0], self.final_conv[2]
-        x = ops.group_norm(x, gn.weight, gn.bias, gn.num_groups, gn.eps, silu=True)
-        cout = conv.out_channels
-        opad = (-cout) % 8          # 3 image channels in 8 columns (zero rows of weight): the data gradient gathers 16-byte chunks of dY
-        if self.trainable:
-            # Padded from the live parameters on every call - so an update of either kind (version counter, or raw pointers +
-            # WeightCache.invalidate) is always seen - and differentiable: the [8,32,3,3] / [8] gradients of the node come
-            # back as [3,32,3,3] / [3].  The previous call's padded weight leaves the WeightCache with it.
-            if self._fc_padded is not None:
-                ops.WeightCache.drop([self._fc_padded])
-            w8, b8 = ops.pad_rows(conv.weight, opad), ops.pad_rows(conv.bias, opad)
-            self._fc_padded = w8
-        else:
-            w8, b8 = _prepared(self._cache, ("fc_grad",), [conv.weight, conv.bias],
-                               lambda: (torch.nn.functional.pad(conv.weight.detach().float(), (0, 0, 0, 0, 0, 0, 0, opad)).contiguous(),
-                                        torch.nn.functional.pad(conv.bias.detach().float(), (0, opad)).contiguous()))
-        y = ops.conv2d(x, w8, b8, act=ACT_TANH)
-        return ops.image_out(y, cout)               # d tanh rides the conv node's epilogue backward; the padding columns get zeros
-
-    def _forward_infer(self, latent, text_emb):
-        if self.trainable and self._epoch != ops.WeightCache.epoch:
-            # an optimizer wrote the parameters through raw pointers (WeightCache.invalidate): version counters did not move
-            self._cache.clear()
-            for m in self.modules():
-                if isinstance(m, (ResNetBlock, CrossAttentionBlock)):
-                    m._cache.clear()
-            self._epoch = ops.WeightCache.epoch
-        dt = self.compute_dtype
-        text = text_emb.detach().to(device=latent.device, dtype=dt).contiguous()
-        wl = _prepared(self._cache, ("lp", dt), [self.latent_proj.weight], lambda: _prep(self.latent_proj.weight, dt))
-        x = _conv(ops.nchw_to_nhwc(latent, dt), wl, self.latent_proj.bias, self.latent_dim, 512, 3, 1, 1)
         for i in range(1, 6):
             x = getattr(self, f"block{i}_resnet1").nhwc(x)
             x = getattr(self, f"block{i}_attn").nhwc(x, text)
@@ -342,12 +260,9 @@ class VAEDecoder(nn.Module):
                 x = ops.upsample_bilinear(x, size)
         gn, conv = self.final_conv[0], self.final_conv[2]
         x = ops.group_norm(x, gn.weight, gn.bias, gn.num_groups, gn.eps, silu=True)
-        cout = conv.out_channels
-        opad = (-cout) % 4                                           # 3 image channels -> 4 output columns (zero rows of weight)
-        wf = _prepared(self._cache, ("fc", dt), [conv.weight, conv.bias],
-                       lambda: (_prep(conv.weight, dt, pad_out=opad), torch.nn.functional.pad(conv.bias.detach().float(), (0, opad)).contiguous()))
-        y = _conv(x, wf[0], wf[1], conv.in_channels, cout + opad, 3, 1, 1, act=ACT_TANH)
-        return ops.nhwc_rows_to_nchw(y, cout + opad, cout)
+        w, b = self._image_conv(torch.is_grad_enabled())
+        y = ops.conv2d(x, w, b, act=ACT_TANH)
+        return ops.image_out(y, conv.out_channels)  # d tanh rides the conv node's epilogue backward; the padding columns get zeros
 
 
 class PokemonVAE(nn.Module):

@@ -61,7 +61,7 @@ def main():
             x = (torch.rand(B, Hi, Hi, Cin, device="cuda") * 2 - 1).to(dt)
             g = (torch.rand(B, Ho, Ho, Cout, device="cuda") * 2 - 1).to(dt)
             w = torch.rand(Cout, cin_real, 4, 4, device="cuda") * 0.2 - 0.1
-            _, wd = ops.prep_weight(w, dt, pad_in=Cin - cin_real, with_wd=True)
+            _, wd = ops.WeightCache.get(w, dt, True, pad_in=Cin - cin_real)
             dx = torch.empty_like(x)
             dw, db = torch.empty_like(w), torch.empty(Cout, device="cuda")
             need = lib.psg_conv4s2_wgrad_workspace_bytes(B, Ho, Ho, Cin, Cout, code)
