@@ -685,6 +685,28 @@ int psg_adamw_dev_f32(float* p, const float* g, float* m, float* v, int64_t n, c
                       const float* beta1_table, int sched_len, float beta1, float beta2, float eps,
                       float weight_decay, int32_t* step_dev, const float* normsq, float max_norm,
                       const int32_t* skip_flag, void* shadow_bf16, psg_stream_t stream);
+/* Grouped forms (stage 1, src/training/vae_trainer.py:164-187,341-342: the VAE and the text encoder under one optimizer with
+ * their own learning rate, and one clip_grad_norm_ each).  One flat fp32 arena of n floats is split into G consecutive
+ * groups, 1 <= G <= PSG_OPT_MAX_GROUPS: group i covers the floats [bounds[i], bounds[i+1]).  bounds is a HOST array of G+1
+ * values with bounds[0] == 0, bounds[G] == n, non-decreasing (PSG_ERR_SHAPE otherwise, as for G out of range or n <= 0), each
+ * a multiple of 8 floats (PSG_ERR_ALIGN, as for a buffer that is not 16-byte aligned); null pointers are PSG_ERR_ARG.  All of
+ * it is checked on the host before anything is launched.  An empty group (bounds[i] == bounds[i+1]) is legal.  Whole
+ * workgroups are assigned to groups on the host, in proportion to the groups' sizes and at least one per non-empty group.
+ *
+ * psg_sumsq_groups_f32: out[i] (device, G floats) = sum(g^2) over group i (0 for an empty one), every group in one pass over
+ * the arena plus one finishing launch; fixed reduction order, no atomics - the same input gives the same bits.  ws: at least
+ * psg_reduce_workspace_bytes() bytes. */
+#define PSG_OPT_MAX_GROUPS 8
+int psg_sumsq_groups_f32(const float* g, int64_t n, const int64_t* bounds, int G, float* out, void* ws, psg_stream_t stream);
+/* psg_adamw_dev_f32's update (the same arithmetic per element; no bf16 shadow, constant beta1) in ONE launch over all
+ * groups, group i with lr[i], weight_decay[i] (HOST arrays of G floats) and
+ * coef_i = min(1, max_norm[i] / (sqrt(normsq[i]) + 1e-6)): normsq is a device array of G floats (psg_sumsq_groups_f32's
+ * out) or NULL = no clipping in any group (max_norm, a host array of G floats, may then be NULL too).  Bias correction from
+ * *step_dev + 1; *step_dev += 1 once per call unless (*skip_flag & PSG_FLAG_SKIP_MASK) != 0 (skip_flag may be NULL), in
+ * which case nothing is written at all. */
+int psg_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* bounds, int G,
+                         const float* lr, const float* weight_decay, const float* max_norm, float beta1, float beta2,
+                         float eps, int32_t* step_dev, const float* normsq, const int32_t* skip_flag, psg_stream_t stream);
 /* g *= min(1, max_norm/(sqrt(*normsq)+1e-6)) — plain clip for callers that keep torch.optim. */
 int psg_clip_scale_f32(float* g, int64_t n, const float* normsq, float max_norm, psg_stream_t stream);
 

@@ -9,7 +9,7 @@ any op without the built library raises (no CPU fallback).
 from ._lib import LIB_PATH, PsgError
 from .scheduler import NoiseScheduler
 from .unet import CrossAttentionBlock, ResBlock, TimestepEmbedding, UNet, UNetBlock
-from .optim import FusedAdamW, GradArena, ParamArena
+from .optim import FusedAdamW, GradArena, GroupedAdamW, ParamArena
 from .ddp import BucketedAllReduce
 from .trainer import DiffusionStepper, DiffusionTrainer, ImprovedDiffusionTrainer
 from .inference import LatentGenerator, LinearNoiseScheduler, gradio_ddpm_sample
@@ -18,10 +18,11 @@ from .text_encoder import TextEncoder
 from .losses import CombinedLoss, VGGPerceptualLoss
 from .clip_loss import CLIPLoss
 from .final import FinalPokemonGenerator, FinalStepper
+from .vae_stepper import VAEStepper
 from .data import SpriteDataset, SpriteLoader, create_data_loaders, draw_params
 
 __all__ = ["UNet", "UNetBlock", "ResBlock", "CrossAttentionBlock", "TimestepEmbedding", "NoiseScheduler",
            "ImprovedDiffusionTrainer", "DiffusionTrainer", "DiffusionStepper", "FusedAdamW", "GradArena", "ParamArena",
            "BucketedAllReduce", "LatentGenerator", "LinearNoiseScheduler", "gradio_ddpm_sample", "PokemonVAE", "VAEEncoder", "VAEDecoder", "TextEncoder", "VGGPerceptualLoss", "CombinedLoss", "CLIPLoss",
-           "FinalPokemonGenerator", "FinalStepper", "SpriteDataset", "SpriteLoader", "create_data_loaders", "draw_params", "PsgError", "LIB_PATH"]
+           "FinalPokemonGenerator", "FinalStepper", "GroupedAdamW", "VAEStepper", "SpriteDataset", "SpriteLoader", "create_data_loaders", "draw_params", "PsgError", "LIB_PATH"]
 __version__ = "0.1.0"

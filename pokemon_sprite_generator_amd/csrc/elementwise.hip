@@ -576,6 +576,92 @@ __global__ void clip_scale_kernel(float* __restrict__ g, int64_t n, const float*
 }
 
 // ---------------------------------------------------------------------------
+// grouped optimizer: one flat arena split into G consecutive groups (stage 1: the VAE and the text encoder under their own
+// learning rate, weight decay and clip norm - vae_trainer.py:164-187,341-342).  WHOLE WORKGROUPS belong to one group: the
+// host hands group i the workgroups [blk0[i], blk0[i+1]) (opt_partition), a workgroup finds its group with at most G
+// compares of its own index, and from then on lr / weight decay / clip coefficient are wave-uniform and no element looks
+// anything up.
+// ---------------------------------------------------------------------------
+struct OptGroups {
+    int64_t lo4[PSG_OPT_MAX_GROUPS];       // first float4 of group i
+    int64_t hi4[PSG_OPT_MAX_GROUPS];       // one past its last (== lo4 for an empty group, which owns no workgroup)
+    int blk0[PSG_OPT_MAX_GROUPS + 1];      // blk0[G] == gridDim.x
+    float lr[PSG_OPT_MAX_GROUPS], wd[PSG_OPT_MAX_GROUPS], max_norm[PSG_OPT_MAX_GROUPS];
+    int G;
+};
+__device__ __forceinline__ int opt_group_of_block(const OptGroups& og) {
+    int gi = 0;
+    while (gi + 1 < og.G && (int)blockIdx.x >= og.blk0[gi + 1]) ++gi;      // (the LAST group starting at or before us: skips empty ones)
+    return gi;
+}
+
+__global__ void sumsq_groups_kernel(const float* __restrict__ g, float* __restrict__ partial, const OptGroups og) {
+    __shared__ float red[16];
+    const int gi = opt_group_of_block(og);
+    const int64_t lb = (int)blockIdx.x - og.blk0[gi], nb = og.blk0[gi + 1] - og.blk0[gi];
+    const int64_t hi4 = og.hi4[gi];
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
+    float acc = 0.f;
+    for (int64_t i = og.lo4[gi] + lb * blockDim.x + threadIdx.x; i < hi4; i += nb * blockDim.x) {
+        f32x4 v = g4[i];
+        acc += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+    }
+    const float s = block_sum(acc, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// final stage, one workgroup per group: its partials [blk0[i], blk0[i+1]) summed in a fixed order (none: out[i] = 0)
+__global__ void sumsq_groups_finish_kernel(const float* __restrict__ partial, float* __restrict__ out, const OptGroups og) {
+    __shared__ float red[16];
+    const int gi = blockIdx.x;
+    float acc = 0.f;
+    for (int i = og.blk0[gi] + (int)threadIdx.x; i < og.blk0[gi + 1]; i += blockDim.x) acc += partial[i];
+    const float s = block_sum(acc, red);
+    if (threadIdx.x == 0) out[gi] = s;
+}
+
+// adamw_kernel4's body (same expressions, same order: G = 1 gives the bits of psg_adamw_dev_f32) over the workgroup's group
+__global__ void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                    float* __restrict__ v, float beta1, float beta2, float eps, const float* normsq,
+                                    const int32_t* skip_flag, const AdamSched sc, const OptGroups og) {
+    if (skip_flag && (*skip_flag & PSG_FLAG_SKIP_MASK)) return;
+    const int gi = opt_group_of_block(og);
+    float lr = og.lr[gi], bc1 = 1.f, bc2_sqrt = 1.f;
+    const float wd = og.wd[gi];
+    adam_sched(sc, beta1, beta2, lr, bc1, bc2_sqrt);
+    const float coef = clip_coef_dev(normsq ? normsq + gi : nullptr, og.max_norm[gi]);
+    const float step_size = lr / bc1;
+    const int64_t n4 = og.hi4[gi];
+    const int64_t stride = (int64_t)(og.blk0[gi + 1] - og.blk0[gi]) * blockDim.x;
+    for (int64_t i0 = og.lo4[gi] + (int64_t)((int)blockIdx.x - og.blk0[gi]) * blockDim.x + threadIdx.x; i0 < n4; i0 += 2 * stride) {
+        const int64_t i1 = i0 + stride;
+        const bool two = i1 < n4;
+        const int64_t j1 = two ? i1 : i0;
+        auto ld = [](const float* a, int64_t i) { return reinterpret_cast<const f32x4*>(a)[i]; };
+        auto stv = [](float* a, int64_t i, f32x4 x) { reinterpret_cast<f32x4*>(a)[i] = x; };
+        f32x4 G[2] = {ld(g, i0), ld(g, j1)};
+        f32x4 P[2] = {ld(p, i0), ld(p, j1)};
+        f32x4 M[2] = {ld(m, i0), ld(m, j1)};
+        f32x4 V[2] = {ld(v, i0), ld(v, j1)};
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float gi_ = G[u][e] * coef;
+                float pi = P[u][e] * (1.0f - lr * wd);
+                const float mi = beta1 * M[u][e] + (1.0f - beta1) * gi_;
+                const float vi = beta2 * V[u][e] + (1.0f - beta2) * gi_ * gi_;
+                const float denom = sqrtf(vi) / bc2_sqrt + eps;
+                pi -= step_size * (mi / denom);
+                P[u][e] = pi; M[u][e] = mi; V[u][e] = vi;
+            }
+        }
+        stv(p, i0, P[0]); stv(m, i0, M[0]); stv(v, i0, V[0]);
+        if (two) { stv(p, i1, P[1]); stv(m, i1, M[1]); stv(v, i1, V[1]); }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // weight preparation: fp32 OIHW -> [O][Kpad] (kh,kw,ci) and [I][Kpad'] (kh,kw,co)
 // ---------------------------------------------------------------------------
 template <typename T>
@@ -967,6 +1053,76 @@ int psg_clip_scale_f32(float* g, int64_t n, const float* normsq, float max_norm,
     hipLaunchKernelGGL(clip_scale_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, g, n, normsq,
                        max_norm);
     PSG_LAUNCH_CHECK("clip_scale");
+    return PSG_OK;
+}
+
+// Validate the group bounds and hand out the workgroups: group i gets min(ceil(n4_i / threads), 1 + its share of the
+// (max_blocks - G) left after one each) of them, none when it is empty - so their sum never exceeds max_blocks.
+static int opt_partition(const char* what, int64_t n, const int64_t* bounds, int G, int threads, int max_blocks, OptGroups& og) {
+    PSG_REQUIRE(bounds, PSG_ERR_ARG, "%s: null pointer", what);
+    PSG_REQUIRE(G >= 1 && G <= PSG_OPT_MAX_GROUPS, PSG_ERR_SHAPE, "%s: G=%d outside 1..%d", what, G, PSG_OPT_MAX_GROUPS);
+    PSG_REQUIRE(n > 0 && bounds[0] == 0 && bounds[G] == n, PSG_ERR_SHAPE, "%s: bounds must run from 0 to n=%ld (got %ld..%ld)", what,
+                (long)n, (long)bounds[0], (long)bounds[G]);
+    for (int i = 0; i < G; ++i)
+        PSG_REQUIRE(bounds[i] <= bounds[i + 1], PSG_ERR_SHAPE, "%s: bounds[%d]=%ld > bounds[%d]=%ld", what, i, (long)bounds[i], i + 1,
+                    (long)bounds[i + 1]);
+    for (int i = 0; i <= G; ++i)
+        PSG_REQUIRE(bounds[i] % 8 == 0, PSG_ERR_ALIGN, "%s: bounds[%d]=%ld is not a multiple of 8 floats", what, i, (long)bounds[i]);
+    og.G = G;
+    const int64_t total4 = n / 4, spare = max_blocks - G;
+    int blk = 0;
+    for (int i = 0; i < PSG_OPT_MAX_GROUPS; ++i) {
+        og.lo4[i] = og.hi4[i] = 0;
+        og.lr[i] = og.wd[i] = og.max_norm[i] = 0.f;
+        og.blk0[i] = blk;
+        if (i >= G) continue;
+        og.lo4[i] = bounds[i] / 4;
+        og.hi4[i] = bounds[i + 1] / 4;
+        const int64_t n4 = og.hi4[i] - og.lo4[i];
+        if (n4 == 0) continue;
+        const int64_t want = (n4 + threads - 1) / threads;
+        const int64_t share = 1 + (int64_t)((double)spare * (double)n4 / (double)total4);
+        blk += (int)(want < share ? want : share);
+    }
+    og.blk0[PSG_OPT_MAX_GROUPS] = blk;
+    for (int i = G; i < PSG_OPT_MAX_GROUPS; ++i) og.blk0[i] = blk;       // (blk0[G] == the grid, whatever G is)
+    return PSG_OK;
+}
+
+int psg_sumsq_groups_f32(const float* g, int64_t n, const int64_t* bounds, int G, float* out, void* ws, psg_stream_t stream) {
+    PSG_REQUIRE(g && bounds && out && ws, PSG_ERR_ARG, "sumsq_groups: null pointer");
+    OptGroups og;
+    const int rc = opt_partition("sumsq_groups", n, bounds, G, RED_THREADS, RED_BLOCKS, og);
+    if (rc) return rc;
+    PSG_REQUIRE(aligned16(g), PSG_ERR_ALIGN, "sumsq_groups: g must be 16-byte aligned");
+    hipLaunchKernelGGL(sumsq_groups_kernel, dim3(og.blk0[G]), dim3(RED_THREADS), 0, (hipStream_t)stream, g, (float*)ws, og);
+    PSG_LAUNCH_CHECK("sumsq_groups");
+    hipLaunchKernelGGL(sumsq_groups_finish_kernel, dim3(G), dim3(256), 0, (hipStream_t)stream, (const float*)ws, out, og);
+    PSG_LAUNCH_CHECK("sumsq_groups_finish");
+    return PSG_OK;
+}
+
+int psg_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* bounds, int G, const float* lr,
+                         const float* weight_decay, const float* max_norm, float beta1, float beta2, float eps, int32_t* step_dev,
+                         const float* normsq, const int32_t* skip_flag, psg_stream_t stream) {
+    PSG_REQUIRE(p && g && m && v && bounds && lr && weight_decay && step_dev && (max_norm || !normsq), PSG_ERR_ARG,
+                "adamw_groups: null pointer");
+    OptGroups og;
+    // 262144 workgroups at most, as adamw_launch (2-3 trips of the 2 x float4 loop on the largest arenas)
+    const int rc = opt_partition("adamw_groups", n, bounds, G, 256, 262144, og);
+    if (rc) return rc;
+    PSG_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), PSG_ERR_ALIGN, "adamw_groups: p, g, m, v must be 16-byte aligned");
+    for (int i = 0; i < G; ++i) {
+        og.lr[i] = lr[i];
+        og.wd[i] = weight_decay[i];
+        og.max_norm[i] = normsq ? max_norm[i] : 0.f;
+    }
+    const AdamSched sc = {step_dev, nullptr, nullptr, 1};
+    hipLaunchKernelGGL(adamw_groups_kernel, dim3(og.blk0[G]), dim3(256), 0, (hipStream_t)stream, p, g, m, v, beta1, beta2, eps, normsq,
+                       skip_flag, sc, og);
+    PSG_LAUNCH_CHECK("adamw_groups");
+    hipLaunchKernelGGL(adam_step_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_dev, skip_flag);
+    PSG_LAUNCH_CHECK("adam_step_advance");
     return PSG_OK;
 }
 

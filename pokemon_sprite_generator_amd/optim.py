@@ -10,13 +10,17 @@ each view as a GradSink: the wgrad / column-sum / GroupNorm-backward kernels
 write gradients straight into it.  The global L2 norm is then one deterministic
 reduction (psg_sumsq_f32) instead of 478 `.item()` syncs, clip + AdamW is ONE
 launch over the flat buffers (psg_adamw_dev_f32) and the data-parallel all-reduce
-runs on large flat slices.
+runs on large flat slices.  GroupedAdamW does the same for several param groups
+at once, each with its own learning rate, weight decay and clip norm (stage 1,
+vae_trainer.py:164-187,341-342): GradArena.group_norm_sq is one pass for every
+group's norm (psg_sumsq_groups_f32), the update one launch (psg_adamw_groups_f32).
 
 Ownership: a parameter belongs to at most one ParamArena and one GradArena at a
 time.  Building a second arena over a parameter DISPLACES the first one: the
 older arena (and the optimizer on it) raises from then on instead of silently
 training on stale views.  `release()` gives the registrations back explicitly.
 """
+import ctypes as C
 import weakref
 
 import torch
@@ -151,6 +155,7 @@ class GradArena:
         self.offsets, self.numel = _arena_offsets(self.params, layout)
         self.flat = torch.zeros(self.numel, dtype=torch.float32, device=dev)
         self.normsq = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._group_normsq = None          # float[G] of group_norm_sq
         self.on_ready = on_ready
         self.views = []
         self.entries = []
@@ -212,6 +217,32 @@ class GradArena:
         ws = _lib.workspace(lib.psg_reduce_workspace_bytes(), self.flat.device)
         check(lib.psg_sumsq_f32(ptr(self.flat), self.numel, ptr(self.normsq), 0, ptr(ws), stream_ptr()), "psg_sumsq_f32")
         return self.normsq
+
+    def group_bounds(self, group_sizes):
+        """Parameter counts of consecutive groups (in this arena's parameter order, which must be its memory order) -> the
+        G + 1 float offsets [0, ..., numel] that psg_sumsq_groups_f32 / psg_adamw_groups_f32 take; a group's trailing padding
+        belongs to it (zeros)."""
+        if sum(group_sizes) != len(self.params) or any(k < 0 for k in group_sizes):
+            raise ValueError(f"group sizes {list(group_sizes)} do not add up to the arena's {len(self.params)} parameters")
+        if self.offsets != sorted(self.offsets):
+            raise ValueError("parameter groups need an arena in parameter order (no `layout`)")
+        bounds, k = [], 0
+        for size in group_sizes:
+            bounds.append(self.offsets[k] if k < len(self.params) else self.numel)
+            k += size
+        return bounds + [self.numel]
+
+    def group_norm_sq(self, bounds):
+        """Device float[G]: sum(g^2) of every group [bounds[i], bounds[i+1]) in one deterministic pass (psg_sumsq_groups_f32)."""
+        SideStream.join(self.flat.device)
+        G = len(bounds) - 1
+        if self._group_normsq is None or self._group_normsq.numel() != G:
+            self._group_normsq = torch.zeros(max(G, 1), dtype=torch.float32, device=self.flat.device)
+        lib = _lib.init(self.flat.device.index)
+        ws = _lib.workspace(lib.psg_reduce_workspace_bytes(), self.flat.device)
+        check(lib.psg_sumsq_groups_f32(ptr(self.flat), self.numel, (C.c_int64 * (G + 1))(*bounds), G, ptr(self._group_normsq), ptr(ws),
+                                       stream_ptr()), "psg_sumsq_groups_f32")
+        return self._group_normsq
 
 
 class FusedAdamW(torch.optim.Optimizer):
@@ -353,4 +384,96 @@ class FusedAdamW(torch.optim.Optimizer):
                 check(lib.psg_adamw_f32(ptr(p), ptr(g), ptr(st["exp_avg"]), ptr(st["exp_avg_sq"]), p.numel(), float(group["lr"]),
                                         float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), int(st["step"]),
                                         nptr, float(max_norm), None, None, stream_ptr()), "psg_adamw_f32")
+        WeightCache.invalidate()     # parameters changed through raw pointers
+
+
+def _torch_adamw_defaults():
+    """The keys torch.optim.AdamW itself keeps in a param group (amsgrad, maximize, foreach, ... - they vary with the torch
+    version): a state dict that carries them loads into torch.optim.AdamW and steps there."""
+    return dict(torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))]).defaults)
+
+
+class GroupedAdamW(FusedAdamW):
+    """torch.optim.AdamW over several param groups, each with its own `lr`, `weight_decay` and clip norm, as ONE launch over
+    the flat arenas (psg_adamw_groups_f32) - stage 1's optimizer (vae_trainer.py:164-187): the VAE at `learning_rate`, the text
+    encoder at `text_encoder_lr`, clipped to 1.0 and 0.5 (:341-342).
+
+    `param_groups` are torch-style dicts (`params`, `lr`, optional `weight_decay`, `name`, ...); `param_arena` / `grad_arena`
+    cover the concatenation of the groups' parameters in order.  betas and eps are common to all groups (one kernel argument
+    each).  `param_groups[i]["lr"]` / `["weight_decay"]` are read on every step, so a host-side torch.optim.lr_scheduler
+    works unchanged.  state_dict / load_state_dict use torch.optim.AdamW's wire format with G groups, both ways."""
+
+    def __init__(self, param_groups, param_arena, grad_arena, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        groups = [dict(g, params=list(g["params"])) for g in param_groups]
+        if not groups or not all(isinstance(g, dict) for g in param_groups):
+            raise ValueError("GroupedAdamW: param_groups must be a non-empty list of dicts")
+        if len(groups) > _lib.ABI.constants["PSG_OPT_MAX_GROUPS"]:
+            raise ValueError(f"GroupedAdamW: at most {_lib.ABI.constants['PSG_OPT_MAX_GROUPS']} param groups")
+        defaults = _torch_adamw_defaults()
+        defaults.update(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        torch.optim.Optimizer.__init__(self, groups, defaults)
+        params = [p for g in self.param_groups for p in g["params"]]
+        same = (len(params) == len(param_arena.params) == len(grad_arena.params)
+                and all(a is b and a is c for a, b, c in zip(params, param_arena.params, grad_arena.params))
+                and param_arena.offsets == grad_arena.offsets)
+        if not same:
+            raise ValueError("GroupedAdamW: arenas do not cover the groups' parameters in order")
+        if any(tuple(g["betas"]) != tuple(self.param_groups[0]["betas"]) or g["eps"] != self.param_groups[0]["eps"] for g in self.param_groups):
+            raise ValueError("GroupedAdamW: betas and eps are common to all groups")
+        self._pa, self._ga = param_arena, grad_arena
+        self.bounds = grad_arena.group_bounds([len(g["params"]) for g in self.param_groups])
+        self._bounds_c = (C.c_int64 * len(self.bounds))(*self.bounds)
+        self._m = torch.zeros_like(param_arena.flat)
+        self._v = torch.zeros_like(param_arena.flat)
+        self.step_dev = torch.zeros(1, dtype=torch.int32, device=param_arena.flat.device)
+        for i, p in enumerate(params):
+            self.state[p] = {"step": torch.tensor(0.0), "exp_avg": param_arena.like(self._m, i), "exp_avg_sq": param_arena.like(self._v, i)}
+
+    def set_lr_table(self, values, beta1_values=None):
+        raise _lib.PsgError("GroupedAdamW reads param_groups[i]['lr'] on every step: drive it with a host-side lr scheduler")
+
+    def load_state_dict(self, state_dict):
+        torch.optim.Optimizer.load_state_dict(self, state_dict)
+        if any(tuple(g["betas"]) != tuple(self.param_groups[0]["betas"]) or g["eps"] != self.param_groups[0]["eps"] for g in self.param_groups):
+            raise ValueError("GroupedAdamW: betas and eps are common to all groups")
+        steps = set()
+        for i, p in enumerate(self._pa.params):           # re-bind the loaded moments to the flat buffers
+            st = self.state[p]
+            m, v = self._pa.like(self._m, i), self._pa.like(self._v, i)
+            if "exp_avg" in st:
+                m.copy_(st["exp_avg"]); v.copy_(st["exp_avg_sq"])
+                steps.add(int(st["step"]))
+            else:                                         # torch keeps no state for a parameter that never had a gradient
+                m.zero_(); v.zero_()
+            st["exp_avg"], st["exp_avg_sq"] = m, v
+        if len(steps) > 1:
+            raise ValueError(f"GroupedAdamW: the flat update needs one common step count, checkpoint has {sorted(steps)}")
+        n = steps.pop() if steps else 0
+        for p in self._pa.params:
+            self.state[p]["step"] = torch.tensor(float(n))
+        self.step_dev.fill_(n)
+
+    def group_norm_sq(self):
+        """Device float[G]: every group's sum(g^2), one pass (GradArena.group_norm_sq over this optimizer's bounds)."""
+        return self._ga.group_norm_sq(self.bounds)
+
+    @torch.no_grad()
+    def step(self, normsq=None, max_norms=None, skip_flag=None):
+        """One launch for all groups.  normsq: device float[G] (`group_norm_sq()`) with max_norms, G floats - or neither: no
+        clipping.  skip_flag: as FusedAdamW.step."""
+        self._pa.check_alive()
+        self._ga.check_alive()
+        G = len(self.param_groups)
+        if (normsq is None) != (max_norms is None):
+            raise ValueError("GroupedAdamW.step: pass normsq and max_norms together")
+        if normsq is not None and (normsq.numel() != G or len(max_norms) != G or normsq.dtype != torch.float32):
+            raise ValueError(f"GroupedAdamW.step: normsq and max_norms must hold one fp32 value per group ({G})")
+        F = C.c_float * G
+        b1, b2 = self.param_groups[0]["betas"]
+        lib = _lib.init(self._pa.flat.device.index)
+        check(lib.psg_adamw_groups_f32(ptr(self._pa.flat), ptr(self._ga.flat), ptr(self._m), ptr(self._v), self._pa.numel, self._bounds_c, G,
+                                       F(*[float(g["lr"]) for g in self.param_groups]), F(*[float(g["weight_decay"]) for g in self.param_groups]),
+                                       F(*[float(x) for x in max_norms]) if max_norms is not None else None, float(b1), float(b2),
+                                       float(self.param_groups[0]["eps"]), ptr(self.step_dev), ptr(normsq) if normsq is not None else None,
+                                       ptr(skip_flag) if skip_flag is not None else None, stream_ptr()), "psg_adamw_groups_f32")
         WeightCache.invalidate()     # parameters changed through raw pointers

@@ -261,6 +261,14 @@ class TextEncoder(nn.Module):
             _prepared(self._cache, ("f2", i, dt), [ou.weight], lambda: _prep(ou.weight[:, :, None, None], dt)),
         )
 
+    def drop_prepared(self):
+        """Forget the packed operands of the trainable layers and the projection.  `_prepared` stamps them with the parameters'
+        storage and version counters; an optimizer that writes through raw pointers (optim.GroupedAdamW) moves neither, so its
+        stepper calls this after every update.  The frozen prefix keeps its operands."""
+        first = self.first_trainable_layer()
+        for k in [k for k in self._cache if k[0] == "proj" or k[1] >= first]:
+            del self._cache[k]
+
     def launches_per_call(self):
         """Kernel launches of one encode_ids call."""
         return 1 + 7 * len(self.bert.encoder.layer) + (1 if isinstance(self.projection, nn.Linear) else 0) + 1
