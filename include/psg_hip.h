@@ -707,6 +707,18 @@ int psg_sumsq_groups_f32(const float* g, int64_t n, const int64_t* bounds, int G
 int psg_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* bounds, int G,
                          const float* lr, const float* weight_decay, const float* max_norm, float beta1, float beta2,
                          float eps, int32_t* step_dev, const float* normsq, const int32_t* skip_flag, psg_stream_t stream);
+/* psg_adamw_groups_f32 with CLIP SETS (stage 3's joint phase, src/training/final_trainer.py:480-483: ONE clip_grad_norm_ over
+ * groups that keep their own learning rates).  clip_set is a HOST array of G values in 0..G-1; groups with the same value are
+ * clipped together: coef_i = min(1, max_norm[i] / (sqrt(sum_{j ascending, clip_set[j] == clip_set[i]} normsq[j]) + 1e-6)).
+ * Every workgroup forms its set's sum itself, in ascending group order: no extra launch, no atomics, the same bits on every
+ * run.  clip_set == NULL = every group its own set, and that or the identity map gives psg_adamw_groups_f32's bits (which is
+ * this entry with NULL).  An empty group inside a set contributes 0.  Checked on the host before anything is launched:
+ * clip_set[i] outside 0..G-1, or two groups of one set with different max_norm (one clip_grad_norm_ call has one max norm):
+ * PSG_ERR_SHAPE; clip_set non-NULL while normsq or max_norm is NULL: PSG_ERR_ARG. */
+int psg_adamw_groups_sets_f32(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* bounds, int G,
+                              const float* lr, const float* weight_decay, const float* max_norm, const int32_t* clip_set,
+                              float beta1, float beta2, float eps, int32_t* step_dev, const float* normsq,
+                              const int32_t* skip_flag, psg_stream_t stream);
 /* g *= min(1, max_norm/(sqrt(*normsq)+1e-6)) — plain clip for callers that keep torch.optim. */
 int psg_clip_scale_f32(float* g, int64_t n, const float* normsq, float max_norm, psg_stream_t stream);
 

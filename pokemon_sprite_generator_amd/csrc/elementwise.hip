@@ -587,6 +587,7 @@ struct OptGroups {
     int64_t hi4[PSG_OPT_MAX_GROUPS];       // one past its last (== lo4 for an empty group, which owns no workgroup)
     int blk0[PSG_OPT_MAX_GROUPS + 1];      // blk0[G] == gridDim.x
     float lr[PSG_OPT_MAX_GROUPS], wd[PSG_OPT_MAX_GROUPS], max_norm[PSG_OPT_MAX_GROUPS];
+    int set[PSG_OPT_MAX_GROUPS];           // clip set of group i: groups with the same value share one clip_grad_norm_ call
     int G;
 };
 __device__ __forceinline__ int opt_group_of_block(const OptGroups& og) {
@@ -620,6 +621,17 @@ __global__ void sumsq_groups_finish_kernel(const float* __restrict__ partial, fl
     if (threadIdx.x == 0) out[gi] = s;
 }
 
+// The squared norm group gi is clipped by: the sum over its clip set, formed by every workgroup itself from at most
+// PSG_OPT_MAX_GROUPS floats in ascending group order (wave-uniform, the same bits on every run; a set of one is normsq[gi]
+// itself: 0 + x == x).  Stage 3's joint phase clips the text encoder and the decoder by ONE norm (final_trainer.py:480-483).
+__device__ __forceinline__ float opt_set_coef(const OptGroups& og, int gi, const float* normsq) {
+    if (!normsq) return 1.0f;
+    float s = 0.f;
+    for (int j = 0; j < og.G; ++j)
+        if (og.set[j] == og.set[gi]) s += normsq[j];
+    return clip_coef_dev(&s, og.max_norm[gi]);
+}
+
 // adamw_kernel4's body (same expressions, same order: G = 1 gives the bits of psg_adamw_dev_f32) over the workgroup's group
 __global__ void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                     float* __restrict__ v, float beta1, float beta2, float eps, const float* normsq,
@@ -629,7 +641,7 @@ __global__ void adamw_groups_kernel(float* __restrict__ p, const float* __restri
     float lr = og.lr[gi], bc1 = 1.f, bc2_sqrt = 1.f;
     const float wd = og.wd[gi];
     adam_sched(sc, beta1, beta2, lr, bc1, bc2_sqrt);
-    const float coef = clip_coef_dev(normsq ? normsq + gi : nullptr, og.max_norm[gi]);
+    const float coef = opt_set_coef(og, gi, normsq);
     const float step_size = lr / bc1;
     const int64_t n4 = og.hi4[gi];
     const int64_t stride = (int64_t)(og.blk0[gi + 1] - og.blk0[gi]) * blockDim.x;
@@ -1074,6 +1086,7 @@ static int opt_partition(const char* what, int64_t n, const int64_t* bounds, int
     for (int i = 0; i < PSG_OPT_MAX_GROUPS; ++i) {
         og.lo4[i] = og.hi4[i] = 0;
         og.lr[i] = og.wd[i] = og.max_norm[i] = 0.f;
+        og.set[i] = i;
         og.blk0[i] = blk;
         if (i >= G) continue;
         og.lo4[i] = bounds[i] / 4;
@@ -1102,20 +1115,32 @@ int psg_sumsq_groups_f32(const float* g, int64_t n, const int64_t* bounds, int G
     return PSG_OK;
 }
 
-int psg_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* bounds, int G, const float* lr,
-                         const float* weight_decay, const float* max_norm, float beta1, float beta2, float eps, int32_t* step_dev,
-                         const float* normsq, const int32_t* skip_flag, psg_stream_t stream) {
+int psg_adamw_groups_sets_f32(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* bounds, int G, const float* lr,
+                              const float* weight_decay, const float* max_norm, const int32_t* clip_set, float beta1, float beta2,
+                              float eps, int32_t* step_dev, const float* normsq, const int32_t* skip_flag, psg_stream_t stream) {
     PSG_REQUIRE(p && g && m && v && bounds && lr && weight_decay && step_dev && (max_norm || !normsq), PSG_ERR_ARG,
                 "adamw_groups: null pointer");
+    PSG_REQUIRE(!clip_set || (normsq && max_norm), PSG_ERR_ARG, "adamw_groups: clip_set needs normsq and max_norm");
     OptGroups og;
     // 262144 workgroups at most, as adamw_launch (2-3 trips of the 2 x float4 loop on the largest arenas)
     const int rc = opt_partition("adamw_groups", n, bounds, G, 256, 262144, og);
     if (rc) return rc;
     PSG_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), PSG_ERR_ALIGN, "adamw_groups: p, g, m, v must be 16-byte aligned");
+    if (clip_set) {
+        for (int i = 0; i < G; ++i)
+            PSG_REQUIRE(clip_set[i] >= 0 && clip_set[i] < G, PSG_ERR_SHAPE, "adamw_groups: clip_set[%d]=%d outside 0..%d", i, (int)clip_set[i],
+                        G - 1);
+        for (int i = 0; i < G; ++i)
+            for (int j = i + 1; j < G; ++j)
+                PSG_REQUIRE(clip_set[i] != clip_set[j] || max_norm[i] == max_norm[j], PSG_ERR_SHAPE,
+                            "adamw_groups: groups %d and %d share clip set %d but max_norm %g != %g", i, j, (int)clip_set[i],
+                            (double)max_norm[i], (double)max_norm[j]);
+    }
     for (int i = 0; i < G; ++i) {
         og.lr[i] = lr[i];
         og.wd[i] = weight_decay[i];
         og.max_norm[i] = normsq ? max_norm[i] : 0.f;
+        og.set[i] = clip_set ? clip_set[i] : i;
     }
     const AdamSched sc = {step_dev, nullptr, nullptr, 1};
     hipLaunchKernelGGL(adamw_groups_kernel, dim3(og.blk0[G]), dim3(256), 0, (hipStream_t)stream, p, g, m, v, beta1, beta2, eps, normsq,
@@ -1124,6 +1149,13 @@ int psg_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t n
     hipLaunchKernelGGL(adam_step_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_dev, skip_flag);
     PSG_LAUNCH_CHECK("adam_step_advance");
     return PSG_OK;
+}
+
+int psg_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* bounds, int G, const float* lr,
+                         const float* weight_decay, const float* max_norm, float beta1, float beta2, float eps, int32_t* step_dev,
+                         const float* normsq, const int32_t* skip_flag, psg_stream_t stream) {
+    return psg_adamw_groups_sets_f32(p, g, m, v, n, bounds, G, lr, weight_decay, max_norm, nullptr, beta1, beta2, eps, step_dev, normsq,
+                                     skip_flag, stream);
 }
 
 int psg_nchw_to_nhwc(const float* src, void* dst, int64_t ld_dst, int B, int C, int HW, int dtype, psg_stream_t stream) {

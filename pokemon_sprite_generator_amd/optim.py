@@ -13,7 +13,9 @@ launch over the flat buffers (psg_adamw_dev_f32) and the data-parallel all-reduc
 runs on large flat slices.  GroupedAdamW does the same for several param groups
 at once, each with its own learning rate, weight decay and clip norm (stage 1,
 vae_trainer.py:164-187,341-342): GradArena.group_norm_sq is one pass for every
-group's norm (psg_sumsq_groups_f32), the update one launch (psg_adamw_groups_f32).
+group's norm (psg_sumsq_groups_f32), the update one launch (psg_adamw_groups_f32).  Groups may share ONE clip norm and
+keep their own learning rates (`step(..., clip_sets=)`, psg_adamw_groups_sets_f32): stage 3's joint phase, one
+clip_grad_norm_ over the text encoder and the VAE decoder (final_trainer.py:480-483).
 
 Ownership: a parameter belongs to at most one ParamArena and one GradArena at a
 time.  Building a second arena over a parameter DISPLACES the first one: the
@@ -457,10 +459,34 @@ class GroupedAdamW(FusedAdamW):
         """Device float[G]: every group's sum(g^2), one pass (GradArena.group_norm_sq over this optimizer's bounds)."""
         return self._ga.group_norm_sq(self.bounds)
 
+    def _check_sets(self, clip_sets):
+        G = len(self.param_groups)
+        sets = [int(x) for x in clip_sets]
+        if len(sets) != G or any(x < 0 or x >= G for x in sets):
+            raise ValueError(f"GroupedAdamW: clip_sets must hold one set index in 0..{G - 1} per group ({G})")
+        return sets
+
+    def set_norms(self, clip_sets, normsq=None):
+        """Device float[number of sets]: the gradient norm of every clip set, in ascending order of the set indices - what
+        `step(..., clip_sets=)` clips by, for reporting (`group_norm_sq()` summed per set; no host read).  `normsq`: a
+        `group_norm_sq()` result to reuse."""
+        sets = self._check_sets(clip_sets)
+        normsq = self.group_norm_sq() if normsq is None else normsq
+        members = [[i for i, x in enumerate(sets) if x == k] for k in sorted(set(sets))]
+        total = []
+        for idx in members:
+            acc = normsq[idx[0]]
+            for i in idx[1:]:                            # ascending group order, as the kernel sums
+                acc = acc + normsq[i]
+            total.append(acc)
+        return torch.stack(total).sqrt()
+
     @torch.no_grad()
-    def step(self, normsq=None, max_norms=None, skip_flag=None):
+    def step(self, normsq=None, max_norms=None, skip_flag=None, clip_sets=None):
         """One launch for all groups.  normsq: device float[G] (`group_norm_sq()`) with max_norms, G floats - or neither: no
-        clipping.  skip_flag: as FusedAdamW.step."""
+        clipping.  clip_sets: G ints; groups with the same value are clipped by ONE norm, the root of the sum of their
+        normsq (one `clip_grad_norm_` call over several param groups, final_trainer.py:480-483: psg_adamw_groups_sets_f32);
+        None: every group by its own (psg_adamw_groups_f32).  skip_flag: as FusedAdamW.step."""
         self._pa.check_alive()
         self._ga.check_alive()
         G = len(self.param_groups)
@@ -468,12 +494,19 @@ class GroupedAdamW(FusedAdamW):
             raise ValueError("GroupedAdamW.step: pass normsq and max_norms together")
         if normsq is not None and (normsq.numel() != G or len(max_norms) != G or normsq.dtype != torch.float32):
             raise ValueError(f"GroupedAdamW.step: normsq and max_norms must hold one fp32 value per group ({G})")
+        if clip_sets is not None and normsq is None:
+            raise ValueError("GroupedAdamW.step: clip_sets need normsq and max_norms")
         F = C.c_float * G
         b1, b2 = self.param_groups[0]["betas"]
         lib = _lib.init(self._pa.flat.device.index)
-        check(lib.psg_adamw_groups_f32(ptr(self._pa.flat), ptr(self._ga.flat), ptr(self._m), ptr(self._v), self._pa.numel, self._bounds_c, G,
-                                       F(*[float(g["lr"]) for g in self.param_groups]), F(*[float(g["weight_decay"]) for g in self.param_groups]),
-                                       F(*[float(x) for x in max_norms]) if max_norms is not None else None, float(b1), float(b2),
-                                       float(self.param_groups[0]["eps"]), ptr(self.step_dev), ptr(normsq) if normsq is not None else None,
-                                       ptr(skip_flag) if skip_flag is not None else None, stream_ptr()), "psg_adamw_groups_f32")
+        head = (ptr(self._pa.flat), ptr(self._ga.flat), ptr(self._m), ptr(self._v), self._pa.numel, self._bounds_c, G,
+                F(*[float(g["lr"]) for g in self.param_groups]), F(*[float(g["weight_decay"]) for g in self.param_groups]),
+                F(*[float(x) for x in max_norms]) if max_norms is not None else None)
+        tail = (float(b1), float(b2), float(self.param_groups[0]["eps"]), ptr(self.step_dev), ptr(normsq) if normsq is not None else None,
+                ptr(skip_flag) if skip_flag is not None else None, stream_ptr())
+        if clip_sets is None:
+            check(lib.psg_adamw_groups_f32(*head, *tail), "psg_adamw_groups_f32")
+        else:
+            sets = (C.c_int32 * G)(*self._check_sets(clip_sets))
+            check(lib.psg_adamw_groups_sets_f32(*head, sets, *tail), "psg_adamw_groups_sets_f32")
         WeightCache.invalidate()     # parameters changed through raw pointers

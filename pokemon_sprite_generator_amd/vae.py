@@ -23,8 +23,8 @@ k / v Linears' through psg_conv_wgrad or, for the high-resolution layers of bloc
 (`ops._deliver_gemm_grads`, `ops._wgrad_slim_route`), the GroupNorms' from psg_groupnorm_bwd_res; the 3-channel image
 convolution is computed in 8 output columns and its gradients come back at the parameter's own [3,32,3,3] / [3] shapes
 (`ops.pad_rows`).  `PokemonVAE(..., trainable=True)` builds both halves trainable and its `forward` carries the graph encoder
--> latent -> decoder.  What is still missing: the stage-1 stepper (two learning rates, two clip norms, KL annealing, the arena /
-FusedAdamW wiring for the VAE) and the joint phase of stage 3 (`FinalPokemonGenerator.unfreeze_vae_decoder` keeps raising).
+-> latent -> decoder.  The steppers are `vae_stepper.VAEStepper` (stage 1) and `final.FinalStepper` (stage 3, whose joint
+phase unfreezes a `trainable=True` decoder: `VAEDecoder.live_weights`).
 
 A default DECODER is frozen (a parameter switched to requires_grad by hand raises, `_require_frozen`) but differentiable with
 respect to its inputs: stage 3 trains the text encoder through it (final_trainer.py:215-236), so when grad mode is on and
@@ -218,18 +218,25 @@ class VAEDecoder(nn.Module):
         _release_on_collect(self)
 
     def forward(self, latent: torch.Tensor, text_emb: torch.Tensor) -> torch.Tensor:
-        """latent [B,latent_dim,h,w], text_emb [B,S,text_dim] -> image [B,3,215,215] fp32.  A `trainable` decoder called with
-        grad mode on returns an image that carries gradients to all its parameters (stage 1, vae_trainer.py) and to `latent` /
-        `text_emb` when they ask; a frozen one carries the inputs' gradients when an input requires grad (data gradients only:
+        """latent [B,latent_dim,h,w], text_emb [B,S,text_dim] -> image [B,3,215,215] fp32.  A `trainable` decoder whose
+        parameters require grad (`live_weights`), called with grad mode on, returns an image that carries gradients to all its
+        parameters (stage 1, vae_trainer.py; stage 3's joint phase) and to `latent` / `text_emb` when they ask; a frozen one carries the inputs' gradients when an input requires grad (data gradients only:
         `_require_frozen`); every other call runs under no_grad."""
         if not latent.is_cuda:
             raise _lib.PsgError("VAEDecoder (MI355X build) needs GPU tensors; there is no CPU fallback")
-        if (self.trainable and torch.is_grad_enabled()) or _wants_grad(latent, text_emb):
+        if (self.live_weights() and torch.is_grad_enabled()) or _wants_grad(latent, text_emb):
             if not self.trainable:
                 _require_frozen(self)
             return self._forward(latent, text_emb)
         with torch.no_grad():
             return self._forward(latent, text_emb)
+
+    def live_weights(self) -> bool:
+        """Whether a call with grad mode on differentiates with respect to the parameters: a `trainable` decoder whose
+        parameters currently require grad.  Stage 3 freezes a trainable decoder for its text-encoder phase
+        (`FinalPokemonGenerator.freeze_vae_decoder`): it is then a default decoder launch for launch - data gradients only, no
+        weight-gradient launch, every prepared operand from `WeightCache` - until `unfreeze_vae_decoder` switches it back."""
+        return self.trainable and any(p.requires_grad for p in self.parameters())
 
     def _image_conv(self, grad):
         """(w, b) of the image convolution: its 3 channels computed in 4 output columns (zero rows of weight), or in 8 when a
@@ -239,7 +246,7 @@ class VAEDecoder(nn.Module):
         conv = self.final_conv[2]
         width = 8 if grad else 4
         extra = (-conv.out_channels) % width
-        live = grad and self.trainable
+        live = grad and self.live_weights()
         pad = (lambda p: ops.pad_rows(p, extra)) if live else (
             lambda p: torch.nn.functional.pad(p.detach().float(), (0, 0) * (p.dim() - 1) + (0, extra)).contiguous())
         return [ops.WeightCache.derived(p, width, lambda: pad(p), fresh=live) for p in (conv.weight, conv.bias)]
