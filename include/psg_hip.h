@@ -754,6 +754,44 @@ int psg_sprite_augment(const uint8_t* src, int64_t N, const int64_t* idx, const 
                        float* out, int B, int S, psg_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * The two ends of the demo's generation path (imaging.hip) - PokemonGradioGenerator, gradio_app.py:394-465: an uploaded
+ * image in (pil_to_tensor), the latent / noise blend, uint8 sprites out (tensor_to_pil).
+ * ------------------------------------------------------------------------- */
+/* gradio_app.py:443-452 - `image.resize((215, 215), Image.Resampling.LANCZOS)`, then ToTensor and `(t - 0.5) * 2`.  PIL's
+ * 8-bit separable resample (Resample.c) driven by integer coefficient tables, any filter, any sizes:
+ *   src  uint8 [B, Hin, Win, C], interleaved channels, C in 1..4, every channel on its own
+ *   per axis: bounds int32 [out, 2] = (first input index, tap count) and coef int32 [out, k] (22-bit fixed point, zero-padded
+ *        rows of the table width k).  k == 0: PIL skips the pass (then the sizes must be equal and the tables are not read);
+ *        both 0: a copy.  bounds is passed twice: *bounds_host is a HOST copy, checked here before anything is launched, and
+ *        *bounds the DEVICE copy the kernels read (they cut every row to the input as well, so even a device copy that
+ *        differs never reads outside src)
+ *   the horizontal pass runs first: acc = 1 << 21; acc += pixel * coef per tap (int32); (acc >> 22) clamped to 0..255 and
+ *        stored as uint8 [B, Hin, Wout, C] in ws (>= B * Hin * Wout * C bytes, when both passes run) before the vertical
+ *        pass reads it - PIL's arithmetic, so the bytes are PIL's
+ *   out_u8  uint8 [B, Hout, Wout, C], and / or
+ *   out_f32 fp32 NCHW [B, 3, Hout, Wout] = lut[byte] of the first three channels (needs C >= 3): lut is the caller's 256-entry
+ *        fp32 table of the reference's own expression, which fuses ToTensor + normalise into the last pass bit-exactly
+ * The kernels loop over taps (tap counts are unbounded) and touch pixels one byte at a time (any row alignment).  Checked on
+ * the host before any launch: null pointers (src, both outputs, a table of a pass that runs, lut with out_f32: PSG_ERR_ARG),
+ * non-positive sizes, C outside 1..4, a side above 131072 or B above 65535, k < 0, a skipped pass between different sizes, a
+ * bounds row with first < 0, taps > k or first + taps past the input (PSG_ERR_SHAPE), ws too small (PSG_ERR_WORKSPACE). */
+int psg_resample_u8(const uint8_t* src, uint8_t* out_u8, float* out_f32, const float* lut, int B, int Hin, int Win, int C,
+                    int Hout, int Wout, const int32_t* xbounds_host, const int32_t* xbounds, const int32_t* xcoef, int kx,
+                    const int32_t* ybounds_host, const int32_t* ybounds, const int32_t* ycoef, int ky, void* ws,
+                    int64_t ws_bytes, psg_stream_t stream);
+/* tensor_to_pil's arithmetic, gradio_app.py:456-465 (and improved_diffusion_trainer.py generate_samples): fp32 image
+ * [B, 3, H, W] addressed by element strides (a contiguous NCHW tensor and a channels_last one both go in as they are) ->
+ * uint8 [B, H, W, 3] contiguous; per element, in fp32 and in the reference's order: (t + 1.0) / 2.0, clamp to [0, 1], * 255,
+ * truncate toward zero.  NaN gives 0.  PSG_ERR_ARG: null pointer; PSG_ERR_SHAPE: non-positive size, B or H above 65535, W
+ * above 131072, a negative stride. */
+int psg_image_to_u8(const float* img, int64_t stride_b, int64_t stride_c, int64_t stride_h, int64_t stride_w, uint8_t* out,
+                    int B, int H, int W, psg_stream_t stream);
+/* gradio_app.py:426 - `latent * (1 - noise_strength) + noise * noise_strength`: out = fl(fl(a * c0) + fl(b * c1)) per
+ * element with c0 = fp32(1 - s), c1 = fp32(s), which is how torch applies a Python scalar to an fp32 tensor.  out may not
+ * alias a or b.  PSG_ERR_ARG: null pointer; PSG_ERR_SHAPE: n <= 0 or above 2^31. */
+int psg_latent_mix_f32(const float* a, const float* b, float c0, float c1, float* out, int64_t n, psg_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Measurement hooks (bench.py): between begin and end every launch of the matrix / attention /
  * GroupNorm kernel families is bracketed by hipEvents on its stream.  end() drains once and
  * returns, per family k < nkinds (0 conv fwd gather, 1 conv data-gradient gather, 2 wgrad,

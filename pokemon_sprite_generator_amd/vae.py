@@ -302,8 +302,8 @@ class PokemonVAE(nn.Module):
                 latent = mu
         return {"reconstructed": self.decoder(latent, text_emb), "latent": latent, "mu": mu, "logvar": logvar}
 
-    def encode(self, images):
-        return self.encoder(images)
+    def encode(self, images, eps: torch.Tensor = None):
+        return self.encoder(images, eps=eps)
 
     def decode(self, latent, text_emb):
         return self.decoder(latent, text_emb)
