@@ -752,6 +752,15 @@ int psg_sprite_contrast_mean(const uint8_t* src, int64_t N, const int64_t* idx, 
  * mean[b]), then combined and normalised. */
 int psg_sprite_augment(const uint8_t* src, int64_t N, const int64_t* idx, const float* params, const float* mean,
                        float* out, int B, int S, psg_stream_t stream);
+/* The text inputs of a batch from the resident token table (data.TokenTable): table int32 [N, L], the tokenizer's ids of
+ * every dataset row, right-padded; lens int32 [N], each row's token count; idx int64 [B] as above.  With
+ * n = min(lens[idx[b]], S):  ids[b, s] = s < n ? table[idx[b], s] : pad_id,  mask[b, s] = s < n  (both int64 [B, S], what
+ * the tokenizer's padding=True call returns when S is the longest row of the batch),  kv_len[b] = n (int32 [B]).  An idx[b]
+ * outside [0, N) yields a row of pad_id, a zero mask and kv_len 0, never an out-of-bounds read.  Asynchronous on `stream`,
+ * no allocation, any B and any S up to L.  PSG_ERR_ARG: null pointer; PSG_ERR_SHAPE: non-positive N, L, B or S, S > L, B above
+ * 65535. */
+int psg_token_batch(const int32_t* table, const int32_t* lens, int64_t N, int L, const int64_t* idx, int B, int S,
+                    int32_t pad_id, int64_t* ids, int64_t* mask, int32_t* kv_len, psg_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * The two ends of the demo's generation path (imaging.hip) - PokemonGradioGenerator, gradio_app.py:394-465: an uploaded

@@ -19,11 +19,13 @@ from .losses import CombinedLoss, VGGPerceptualLoss
 from .clip_loss import CLIPLoss
 from .final import FinalPokemonGenerator, FinalStepper
 from .vae_stepper import VAEStepper
-from .data import SpriteDataset, SpriteLoader, create_data_loaders, draw_params
+from .data import SpriteDataset, SpriteLoader, TokenTable, create_data_loaders, draw_params
+from .vae_trainer import VAETrainer
+from .final_trainer import FinalTrainer
 from .generate import SpriteGenerator
 
 __all__ = ["UNet", "UNetBlock", "ResBlock", "CrossAttentionBlock", "TimestepEmbedding", "NoiseScheduler",
            "ImprovedDiffusionTrainer", "DiffusionTrainer", "DiffusionStepper", "FusedAdamW", "GradArena", "ParamArena",
            "BucketedAllReduce", "LatentGenerator", "LinearNoiseScheduler", "gradio_ddpm_sample", "PokemonVAE", "VAEEncoder", "VAEDecoder", "TextEncoder", "VGGPerceptualLoss", "CombinedLoss", "CLIPLoss",
-           "FinalPokemonGenerator", "FinalStepper", "GroupedAdamW", "VAEStepper", "SpriteDataset", "SpriteLoader", "create_data_loaders", "draw_params", "SpriteGenerator", "PsgError", "LIB_PATH"]
+           "FinalPokemonGenerator", "FinalStepper", "GroupedAdamW", "VAEStepper", "SpriteDataset", "SpriteLoader", "create_data_loaders", "draw_params", "SpriteGenerator", "VAETrainer", "FinalTrainer", "TokenTable", "PsgError", "LIB_PATH"]
 __version__ = "0.1.0"

@@ -1,5 +1,6 @@
 // Sprite batches from the device-resident dataset: gather + augmentation + normalisation in one pass
-// (psg_sprite_contrast_mean, psg_sprite_augment; the parameter row is described in include/psg_hip.h).
+// (psg_sprite_contrast_mean, psg_sprite_augment; the parameter row is described in include/psg_hip.h), and the batch's
+// text inputs gathered from the resident token table (psg_token_batch).
 //
 // Every float expression below is written once, in the order tests/sprite_ref.py restates it, and the build has
 // contraction off: the fp32 evaluation of that restatement and these kernels then differ only where a sum is ordered
@@ -13,6 +14,7 @@ using namespace psg;
 constexpr int NP = PSG_SPRITE_PARAMS;
 constexpr int AUG_THREADS = 256;     // one output pixel per lane, consecutive lanes consecutive pixels of a row: the three plane stores coalesce
 constexpr int MEAN_THREADS = 1024;   // one block per image: 46225 pixels at S = 215, 45-46 per lane
+constexpr int TOK_THREADS = 256;     // one token per lane, consecutive lanes consecutive positions: both int64 stores coalesce
 
 // the 24 orders of (0 brightness, 1 contrast, 2 saturation, 3 hue), lexicographic; entry k of an order in bits 2k..2k+1
 __device__ const unsigned char kOrders[24] = {
@@ -168,6 +170,23 @@ __global__ __launch_bounds__(AUG_THREADS) void sprite_augment_kernel(const uint3
     }
 }
 
+// grid (ceil(S / TOK_THREADS), B): lane s of row b.  A row index outside [0, N) reads nothing and yields an empty row.
+__global__ __launch_bounds__(TOK_THREADS) void token_batch_kernel(const int32_t* __restrict__ table, const int32_t* __restrict__ lens,
+                                                                  int64_t N, int L, const int64_t* __restrict__ idx, int S,
+                                                                  int32_t pad_id, int64_t* __restrict__ ids,
+                                                                  int64_t* __restrict__ mask, int32_t* __restrict__ kv_len) {
+    const int s = blockIdx.x * TOK_THREADS + threadIdx.x, b = blockIdx.y;
+    if (s >= S) return;
+    const int64_t row = idx[b];
+    int n = 0;
+    if (row >= 0 && row < N) n = min(max(lens[row], 0), S);       // (S <= L: a length past the table's width never reads past the row)
+    const bool real = s < n;
+    const size_t o = (size_t)b * S + s;
+    ids[o] = real ? (int64_t)table[(size_t)row * L + s] : (int64_t)pad_id;
+    mask[o] = real ? 1 : 0;
+    if (s == 0) kv_len[b] = n;
+}
+
 int check_args(const void* src, int64_t N, const void* idx, const void* params, const void* mean, const void* out, int B, int S,
                const char* what) {
     PSG_REQUIRE(src && idx && params && mean && out, PSG_ERR_ARG, "%s: null pointer", what);
@@ -196,6 +215,18 @@ int psg_sprite_augment(const uint8_t* src, int64_t N, const int64_t* idx, const 
     hipLaunchKernelGGL(sprite_augment_kernel, dim3((S * S + AUG_THREADS - 1) / AUG_THREADS, B), dim3(AUG_THREADS), 0,
                        (hipStream_t)stream, reinterpret_cast<const uint32_t*>(src), N, idx, params, mean, out, S);
     PSG_LAUNCH_CHECK("sprite_augment_kernel");
+    return PSG_OK;
+}
+
+int psg_token_batch(const int32_t* table, const int32_t* lens, int64_t N, int L, const int64_t* idx, int B, int S, int32_t pad_id,
+                    int64_t* ids, int64_t* mask, int32_t* kv_len, psg_stream_t stream) {
+    PSG_REQUIRE(table && lens && idx && ids && mask && kv_len, PSG_ERR_ARG, "psg_token_batch: null pointer");
+    PSG_REQUIRE(N > 0 && L > 0 && B > 0 && S > 0, PSG_ERR_SHAPE, "psg_token_batch: N=%lld L=%d B=%d S=%d must be positive", (long long)N,
+                L, B, S);
+    PSG_REQUIRE(S <= L && B <= 65535, PSG_ERR_SHAPE, "psg_token_batch: S=%d above L=%d, or B=%d above 65535", S, L, B);
+    hipLaunchKernelGGL(token_batch_kernel, dim3((S + TOK_THREADS - 1) / TOK_THREADS, B), dim3(TOK_THREADS), 0, (hipStream_t)stream, table,
+                       lens, N, L, idx, S, pad_id, ids, mask, kv_len);
+    PSG_LAUNCH_CHECK("token_batch_kernel");
     return PSG_OK;
 }
 

@@ -206,6 +206,78 @@ def augment(src, idx, params, mean=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# text inputs: the token ids of every description, resident like the images
+# ---------------------------------------------------------------------------------------------------------------------
+MAX_LENGTH = 256       # the reference TextEncoder's truncation
+
+
+def tokenize_rows(texts, tokenizer, max_length: int = MAX_LENGTH):
+    """[[id, ...]] - the reference's tokenizer call per text (truncation at max_length, special tokens as the tokenizer adds
+    them), no padding."""
+    return [list(tokenizer(t, truncation=True, max_length=max_length)["input_ids"]) for t in texts]
+
+
+def padded_batch(rows, pad_id: int, S: int = None):
+    """Host restatement of psg_token_batch over lists of ids: (input_ids, attention_mask) int64 [B, S], S = the longest row."""
+    S = max(len(r) for r in rows) if S is None else S
+    ids = torch.full((len(rows), S), int(pad_id), dtype=torch.int64)
+    mask = torch.zeros(len(rows), S, dtype=torch.int64)
+    for b, r in enumerate(rows):
+        n = min(len(r), S)
+        ids[b, :n] = torch.tensor(r[:n], dtype=torch.int64)
+        mask[b, :n] = 1
+    return ids, mask
+
+
+def token_batch(table, lens, idx, S: int, pad_id: int):
+    """psg_token_batch: (input_ids, attention_mask) int64 [B, S] and kv_len int32 [B] of the rows `idx` of `table`."""
+    if not (table.is_cuda and lens.is_cuda and idx.is_cuda):
+        raise _lib.PsgError("token batches need GPU tensors: the HIP kernel is the only implementation")
+    if table.dtype != torch.int32 or table.dim() != 2 or not table.is_contiguous():
+        raise _lib.PsgError(f"tokens: table must be a contiguous int32 [N, L] tensor, got {table.dtype} {tuple(table.shape)}")
+    N, L = table.shape
+    if lens.dtype != torch.int32 or tuple(lens.shape) != (N,) or not lens.is_contiguous():
+        raise _lib.PsgError(f"tokens: lens must be a contiguous int32 [{N}] tensor")
+    if idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous():
+        raise _lib.PsgError("tokens: idx must be a contiguous int64 [B] tensor")
+    B, S = idx.shape[0], int(S)
+    lib = _lib.init(table.device.index)
+    ids = torch.empty(B, S, dtype=torch.int64, device=table.device)
+    mask = torch.empty(B, S, dtype=torch.int64, device=table.device)
+    kv_len = torch.empty(B, dtype=torch.int32, device=table.device)
+    _lib.check(lib.psg_token_batch(_lib.ptr(table), _lib.ptr(lens), N, L, _lib.ptr(idx), B, S, int(pad_id), _lib.ptr(ids),
+                                   _lib.ptr(mask), _lib.ptr(kv_len), _lib.stream_ptr()), "psg_token_batch")
+    return ids, mask, kv_len
+
+
+class TokenTable:
+    """The tokenizer's ids of `dataset.meta(i)["full_description"]` for every row, made once on the host: `table` int32 [N, L]
+    on the dataset's device (right-padded with `pad_id`, L the longest row), `lens` int32 [N] there, `lens_host` a list.
+    `batch` then gives what `tokenizer(texts, padding=True, truncation=True, max_length=max_length)` returns for a batch's
+    texts, from one launch and no host work."""
+
+    def __init__(self, dataset, tokenizer, max_length: int = MAX_LENGTH):
+        pad = getattr(tokenizer, "pad_token_id", None)
+        self.pad_id = 0 if pad is None else int(pad)
+        self.max_length = int(max_length)
+        rows = tokenize_rows([dataset.meta(i)["full_description"] for i in range(len(dataset))], tokenizer, self.max_length)
+        self.lens_host = [len(r) for r in rows]
+        host, _ = padded_batch(rows, self.pad_id) if rows else (torch.zeros(0, 1, dtype=torch.int64), None)
+        self.table = host.to(torch.int32).to(dataset.device)
+        self.lens = torch.tensor(self.lens_host, dtype=torch.int32).to(dataset.device)
+
+    def __len__(self) -> int:
+        return len(self.lens_host)
+
+    def batch(self, idx_dev, rows_host):
+        """(input_ids, attention_mask) int64 [B, S] of the dataset rows `idx_dev` (int64, device); `rows_host` are the same
+        rows on the host, from which the padded length S = the longest of them comes without a device read."""
+        S = max(self.lens_host[int(r)] for r in rows_host)
+        ids, mask, _ = token_batch(self.table, self.lens, idx_dev, S, self.pad_id)
+        return ids, mask
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the draws (pure torch on the given device, no host sync)
 # ---------------------------------------------------------------------------------------------------------------------
 def identity_params(B: int, S: int, device="cpu"):
@@ -287,13 +359,15 @@ def split_indices(total: int, val_split: float, test_split: float, seed: int):
 
 class SpriteLoader:
     """Batches of the reference's dict - image (fp32 [B, 3, S, S] on the dataset's device), description, full_description,
-    national_number (int64 tensor), name - over `indices` of a SpriteDataset.
+    national_number (int64 tensor), name - over `indices` of a SpriteDataset.  With `tokens` (a TokenTable of the dataset) a
+    batch also carries input_ids, attention_mask (int64 [B, S], the tokenizer's padded batch of full_description) and index
+    (int64 [B], the dataset rows), all on the device.
 
     augment=True: shuffled and augmented from generators seeded `seed + epoch`, so every data-parallel rank sees the same
     global batches (ddp.ShardedLoader slices them).  The epoch advances by one per iteration; `set_epoch` pins it."""
 
-    def __init__(self, dataset, indices, batch_size: int, augment: bool, drop_last: bool, seed: int = 42):
-        self.dataset, self.indices, self.batch_size = dataset, list(indices), int(batch_size)
+    def __init__(self, dataset, indices, batch_size: int, augment: bool, drop_last: bool, seed: int = 42, tokens=None):
+        self.dataset, self.indices, self.batch_size, self.tokens = dataset, list(indices), int(batch_size), tokens
         self.augment, self.drop_last, self.seed, self.epoch = bool(augment), bool(drop_last), int(seed), 0
         if self.batch_size <= 0:
             raise ValueError("batch_size must be positive")
@@ -325,17 +399,22 @@ class SpriteLoader:
             batch = {key: [m[key] for m in meta] for key in ("description", "full_description", "name")}
             batch["national_number"] = torch.tensor([m["national_number"] for m in meta], dtype=torch.int64)
             batch["image"] = image
+            if self.tokens is not None:
+                batch["input_ids"], batch["attention_mask"] = self.tokens.batch(idx, order[lo:hi])
+                batch["index"] = idx
             yield batch
 
 
 def create_data_loaders(csv_path: str, image_dir: str, batch_size: int = 32, val_split: float = 0.1, test_split: float = 0.1,
                         image_size: int = 215, num_workers: int = 4, pin_memory: bool = True, seed: int = 42,
-                        background_color: Union[str, Tuple[int, int, int]] = "white", device=None):
+                        background_color: Union[str, Tuple[int, int, int]] = "white", device=None, tokenizer=None):
     """The reference's create_data_loaders (src/data/dataset_improved.py:228-317): (train, val, test).  The same split (seed),
     train shuffled + augmented with drop_last, val / test sequential and un-augmented.  num_workers and pin_memory are
-    accepted and ignored: there are no workers and nothing to pin."""
+    accepted and ignored: there are no workers and nothing to pin.  `tokenizer`: the three loaders share one TokenTable of
+    the dataset and their batches carry input_ids / attention_mask / index."""
     dataset = SpriteDataset(csv_path, image_dir, image_size=image_size, background_color=background_color, device=device)
     train, val, test = split_indices(len(dataset), val_split, test_split, seed)
-    return (SpriteLoader(dataset, train, batch_size, augment=True, drop_last=True, seed=seed),
-            SpriteLoader(dataset, val, batch_size, augment=False, drop_last=False, seed=seed),
-            SpriteLoader(dataset, test, batch_size, augment=False, drop_last=False, seed=seed))
+    tokens = None if tokenizer is None else TokenTable(dataset, tokenizer)
+    return (SpriteLoader(dataset, train, batch_size, augment=True, drop_last=True, seed=seed, tokens=tokens),
+            SpriteLoader(dataset, val, batch_size, augment=False, drop_last=False, seed=seed, tokens=tokens),
+            SpriteLoader(dataset, test, batch_size, augment=False, drop_last=False, seed=seed, tokens=tokens))

@@ -211,6 +211,26 @@ def tensor_to_pil(image):
     return Image.fromarray(image.cpu().numpy())
 
 
+def save_sheet(rows, path):
+    """Monitoring grid: `rows` is a list of [n, 3, H, W] tensors in [-1, 1] (one H x W for all); each goes through `to_uint8`
+    and becomes one row of the sheet, its n images side by side (a shorter row ends in white).  Laid out on the device,
+    written as a PNG with PIL.  Returns the uint8 [len(rows) * H, n_max * W, 3] sheet."""
+    from PIL import Image                      # lazy: importing the package needs neither PIL nor a GPU
+    if not rows:
+        raise _lib.PsgError("save_sheet: no rows")
+    u8 = [to_uint8(r) for r in rows]                                   # [n, H, W, 3] each
+    H, W = u8[0].shape[1:3]
+    if any(tuple(r.shape[1:3]) != (H, W) for r in u8):
+        raise _lib.PsgError(f"save_sheet: rows of different image sizes {[tuple(r.shape) for r in u8]}")
+    n = max(r.shape[0] for r in u8)
+    sheet = torch.full((len(u8), H, n, W, 3), 255, dtype=torch.uint8, device=u8[0].device)
+    for k, r in enumerate(u8):
+        sheet[k, :, :r.shape[0]] = r.to(sheet.device).permute(1, 0, 2, 3)
+    sheet = sheet.reshape(len(u8) * H, n * W, 3)
+    Image.fromarray(sheet.cpu().numpy()).save(str(path))
+    return sheet
+
+
 def mix_latent(latent, noise, strength: float):
     """gradio_app.py:426: latent * (1 - strength) + noise * strength in fp32, both scalars rounded to fp32 first (as torch
     applies a Python scalar to an fp32 tensor), every product and the sum rounded once.  `noise` is moved to the latent's device (an injected draw may come from the host)."""

@@ -45,6 +45,9 @@ class _NullWriter:
     def add_image(self, *a, **k):
         pass
 
+    def add_images(self, *a, **k):
+        pass
+
     def close(self):
         pass
 
@@ -450,13 +453,80 @@ def schedule_tables(make_scheduler, lr, betas, total):
     return lrs, b1s
 
 
-class ImprovedDiffusionTrainer:
+class TrainerBase:
+    """What the three stage trainers share: the experiment's directories, the log file (`LOG_FILE`, written by rank 0), the
+    TensorBoard writer (a null one when tensorboard is not installed) and `_component`, which resolves a collaborator from
+    `components=`, this package, or the reference tree.  A subclass sets config, experiment_name, _components and is_main first."""
+    LOG_FILE = "training.log"
+    is_main = True
+
+    def setup_directories(self):
+        self.experiment_dir = Path(self.config["experiment_dir"]) / self.experiment_name
+        self.checkpoint_dir, self.log_dir, self.sample_dir = (self.experiment_dir / d for d in ("checkpoints", "logs", "samples"))
+        for d in (self.experiment_dir, self.checkpoint_dir, self.log_dir, self.sample_dir):
+            d.mkdir(parents=True, exist_ok=True)
+
+    def setup_logging(self):
+        fmt = "%(asctime)s - %(levelname)s - %(message)s"
+        logging.basicConfig(level=logging.INFO if self.is_main else logging.WARNING, format=fmt, handlers=[logging.StreamHandler()])
+        self.logger = logging.getLogger(__name__)
+        if self.is_main:                                 # one log file, written by rank 0 (basicConfig is a no-op when the
+            path = str((self.log_dir / self.LOG_FILE).resolve())             # host application configured logging first)
+            root = logging.getLogger()
+            if not any(isinstance(h, logging.FileHandler) and h.baseFilename == path for h in root.handlers):
+                fh = logging.FileHandler(path)
+                fh.setFormatter(logging.Formatter(fmt))
+                root.addHandler(fh)
+            if root.level > logging.INFO or root.level == logging.NOTSET:
+                root.setLevel(logging.INFO)
+
+    def _component(self, name):
+        if name in self._components:
+            return self._components[name]
+        if name in ("VAEEncoder", "VAEDecoder"):          # the frozen VAE either side of the path runs on the kernels too
+            from . import vae
+            cls = getattr(vae, name)
+            return lambda *a, **k: cls(*a, compute_dtype=getattr(self, "vae_dtype", torch.float32), **k)
+        if name == "TextEncoder":                        # the frozen BERT text encoder as well (text_encoder.py)
+            from .text_encoder import TextEncoder
+            return lambda *a, **k: TextEncoder(*a, compute_dtype=getattr(self, "text_dtype", torch.float32), **k)
+        if name == "create_data_loaders":
+            # the reference tree's loader when this class is dropped into it (as before); anywhere else, or with
+            # `mi355x.gpu_data: true`, this package's device-resident loader (data.py)
+            if not getattr(self, "_gpu_data", False):
+                try:
+                    import importlib
+                    return getattr(importlib.import_module("src.data"), name)
+                except Exception:              # noqa: BLE001
+                    pass
+            from .data import create_data_loaders
+            return create_data_loaders
+        try:                                   # the reference package, when this class is dropped into its tree
+            import importlib
+            return getattr(importlib.import_module("src.models"), name)
+        except Exception as e:                 # noqa: BLE001
+            raise _lib.PsgError(f"component '{name}' is outside the accelerated hot path: provide it via components= "
+                                f"or run inside the reference tree ({e})")
+
+    def setup_monitoring(self):
+        self.writer = _NullWriter()
+        if not self.is_main:
+            return
+        try:
+            from torch.utils.tensorboard import SummaryWriter
+            self.writer = SummaryWriter(log_dir=self.log_dir)
+        except Exception:                      # tensorboard is optional here
+            pass
+
+
+class ImprovedDiffusionTrainer(TrainerBase):
     """Drop-in for the reference class of the same name (stage-2 diffusion trainer).
 
     Data parallel: when a default process group exists (`torchrun ... train_3stage.py` with
     `torch.distributed.init_process_group("nccl")` called before the trainer is built - see INTEGRATION.md) every
     rank builds the same trainer; gradients are averaged by the stepper, each rank trains on its own slice of every
     batch (`ddp.ShardedLoader`), and only rank 0 writes checkpoints, TensorBoard events, sample images and the log file."""
+    LOG_FILE = "diffusion_training.log"
 
     def __init__(self, config: Dict[str, Any], vae_checkpoint_path: str, experiment_name: str = "pokemon_diffusion",
                  components: Optional[Dict[str, Any]] = None, compute_dtype: Optional[torch.dtype] = None):
@@ -494,55 +564,7 @@ class ImprovedDiffusionTrainer:
         self.current_epoch, self.best_val_loss = 0, float("inf")
         self._gs_offset = 0
 
-    # -- setup (plain Python glue, same keys as the reference) -----------------------------------------
-    def setup_directories(self):
-        self.experiment_dir = Path(self.config["experiment_dir"]) / self.experiment_name
-        self.checkpoint_dir, self.log_dir, self.sample_dir = (self.experiment_dir / d for d in ("checkpoints", "logs", "samples"))
-        for d in (self.experiment_dir, self.checkpoint_dir, self.log_dir, self.sample_dir):
-            d.mkdir(parents=True, exist_ok=True)
-
-    def setup_logging(self):
-        fmt = "%(asctime)s - %(levelname)s - %(message)s"
-        logging.basicConfig(level=logging.INFO if self.is_main else logging.WARNING, format=fmt, handlers=[logging.StreamHandler()])
-        self.logger = logging.getLogger(__name__)
-        if self.is_main:                                 # one log file, written by rank 0 (basicConfig is a no-op when the
-            path = str((self.log_dir / "diffusion_training.log").resolve())   # host application configured logging first)
-            root = logging.getLogger()
-            if not any(isinstance(h, logging.FileHandler) and h.baseFilename == path for h in root.handlers):
-                fh = logging.FileHandler(path)
-                fh.setFormatter(logging.Formatter(fmt))
-                root.addHandler(fh)
-            if root.level > logging.INFO or root.level == logging.NOTSET:
-                root.setLevel(logging.INFO)
-
-    def _component(self, name):
-        if name in self._components:
-            return self._components[name]
-        if name in ("VAEEncoder", "VAEDecoder"):          # the frozen VAE either side of the path runs on the kernels too
-            from . import vae
-            cls = getattr(vae, name)
-            return lambda *a, **k: cls(*a, compute_dtype=self.vae_dtype, **k)
-        if name == "TextEncoder":                        # the frozen BERT text encoder as well (text_encoder.py)
-            from .text_encoder import TextEncoder
-            return lambda *a, **k: TextEncoder(*a, compute_dtype=self.text_dtype, **k)
-        if name == "create_data_loaders":
-            # the reference tree's loader when this class is dropped into it (as before); anywhere else, or with
-            # `mi355x.gpu_data: true`, this package's device-resident loader (data.py)
-            if not self._gpu_data:
-                try:
-                    import importlib
-                    return getattr(importlib.import_module("src.data"), name)
-                except Exception:              # noqa: BLE001
-                    pass
-            from .data import create_data_loaders
-            return create_data_loaders
-        try:                                   # the reference package, when this class is dropped into its tree
-            import importlib
-            return getattr(importlib.import_module("src.models"), name)
-        except Exception as e:                 # noqa: BLE001
-            raise _lib.PsgError(f"component '{name}' is outside the accelerated hot path: provide it via components= "
-                                f"or run inside the reference tree ({e})")
-
+    # -- setup (plain Python glue, same keys as the reference; directories, logging, monitoring and `_component` are TrainerBase's)
     def setup_models(self):
         mc = self.config["model"]
         latent_dim = mc.get("latent_dim", 8)
@@ -598,9 +620,19 @@ class ImprovedDiffusionTrainer:
         else:
             dc, uc = self.config["data"], self.config.get("unet_optimization", {}) or {}
             bs, nw = uc.get("batch_size", dc["batch_size"]), uc.get("num_workers", dc["num_workers"])
-            tr, va, te = self._component("create_data_loaders")(csv_path=dc["csv_path"], image_dir=dc["image_dir"], batch_size=bs,
-                                                                val_split=dc["val_split"], test_split=dc["test_split"],
-                                                                image_size=dc["image_size"], num_workers=nw, pin_memory=dc["pin_memory"])
+            make = self._component("create_data_loaders")
+            from . import data as own_data
+            from .text_encoder import TextEncoder as OwnTextEncoder
+            kw = {}
+            # this package's loader, this package's text encoder, one process: the batches carry their token ids from the
+            # resident table (data.TokenTable).  Data parallel keeps the string path: a rank's shard would otherwise be padded
+            # to the global batch's length, and the U-Net attends to the padding.
+            if (make is own_data.create_data_loaders and isinstance(self.text_encoder, OwnTextEncoder)
+                    and self.text_encoder.tokenizer is not None and self.world == 1):
+                self.text_encoder.tokenizer.padding_side = "right"
+                kw["tokenizer"] = self.text_encoder.tokenizer
+            tr, va, te = make(csv_path=dc["csv_path"], image_dir=dc["image_dir"], batch_size=bs, val_split=dc["val_split"],
+                              test_split=dc["test_split"], image_size=dc["image_size"], num_workers=nw, pin_memory=dc["pin_memory"], **kw)
             loaders = {"train": tr, "val": va, "test": te}
             self.logger.info(f"Data loaders created: train={len(tr)}, val={len(va)}, test={len(te)}")
         if self.world > 1:
@@ -640,16 +672,6 @@ class ImprovedDiffusionTrainer:
             lrs, b1s = schedule_tables(self._make_scheduler, self.scheduler_config["lr"], self._betas, n)
             self._lr_host, self._b1_host = lrs, b1s
             self.optimizer.set_lr_table(lrs, b1s)
-
-    def setup_monitoring(self):
-        self.writer = _NullWriter()
-        if not self.is_main:
-            return
-        try:
-            from torch.utils.tensorboard import SummaryWriter
-            self.writer = SummaryWriter(log_dir=self.log_dir)
-        except Exception:                      # tensorboard is optional here
-            pass
 
     # -- step counters: the truth is on the device ---------------------------------------------------------
     @property
@@ -694,7 +716,10 @@ class ImprovedDiffusionTrainer:
         """text embedding + frozen-VAE latent (:347-360) and the device-side form of their two NaN checks."""
         images = batch["image"].to(self.device)
         with torch.no_grad():
-            text_emb = self.text_encoder(batch["full_description"])
+            if "input_ids" in batch:               # the loader's resident token table: the same ids, the same padded length
+                text_emb = self.text_encoder.encode_ids(batch["input_ids"], batch["attention_mask"])
+            else:
+                text_emb = self.text_encoder(batch["full_description"])
             gen = self.stepper.generator
             from .vae import VAEEncoder as _OwnEncoder
             if gen is not None and isinstance(self.vae_encoder, _OwnEncoder):      # this rank's own reparameterisation noise
