@@ -77,19 +77,23 @@ int psg_init(int device);
  * out[b,i] = tabA[t[b]] * clamp?(x0[b,i]) + tabB[t[b]] * noise[b,i]; two rounded
  * multiplies and one rounded add, bit-identical to the CPU path.  *flag (int32,
  * device) is OR-ed with PSG_FLAG_FALLBACK if any output is NaN/Inf, with
- * PSG_FLAG_T_RANGE if any t[b] is outside [0,num_t).  Zero *flag before the call. */
+ * PSG_FLAG_T_RANGE if any t[b] is outside [0,num_t); such a t[b] reads the nearest entry of the
+ * tables (0 or num_t - 1).  Zero *flag before the call.  B == 0 is PSG_OK with nothing launched;
+ * B < 0, chw <= 0 or num_t <= 0 is PSG_ERR_SHAPE; a null pointer is PSG_ERR_ARG. */
 int psg_noise_add_f32(const float* x0, const float* noise, const int64_t* t, const float* tabA,
                       const float* tabB, float* out, int32_t* flag, int64_t B, int64_t chw,
                       int num_t, int do_clamp, psg_stream_t stream);
 /* The reference's fallback (:61-63): if (*flag & PSG_FLAG_FALLBACK) out = clamp?(x0) + 0.1*noise, and
  * *flag |= PSG_FLAG_NOISY_BAD if that is still non-finite (the trainer's re-check, :376).  Device-side
- * test of the flag; no host sync. */
+ * test of the flag; no host sync: with the bit clear neither out nor *flag is written.  n <= 0 is
+ * PSG_OK with nothing launched; a null pointer is PSG_ERR_ARG. */
 int psg_noise_fallback_f32(const float* x0, const float* noise, float* out, int32_t* flag,
                            int64_t n, int do_clamp, psg_stream_t stream);
 /* ddpm_sample update — improved_diffusion_trainer.py:543-567.  step tables hold the per-timestep
  * scalars c1=1/sqrt(alpha_t), c2=beta_t/sqrt(1-alphabar_t), sigma=sqrt(beta_t) (fp32, computed on
  * the host with the reference's torch ops); t_index selects the entry on the device so the launch
- * is graph-replayable: x <- c1*(x - c2*eps) [+ sigma*z if t>0].  t_dev: int32 device scalar. */
+ * is graph-replayable: x <- c1*(x - c2*eps) [+ sigma*z if t>0].  t_dev: int32 device scalar.
+ * n <= 0 is PSG_OK with nothing launched; a null pointer (z included, whatever t is) is PSG_ERR_ARG. */
 int psg_ddpm_update_f32(float* x, const float* eps, const float* z, const float* c1, const float* c2,
                         const float* sigma, const int32_t* t_dev, int64_t n, psg_stream_t stream);
 
@@ -102,21 +106,26 @@ int psg_ddpm_update_f32(float* x, const float* eps, const float* z, const float*
  *   mode 3 — PokemonGradioGenerator.ddpm_sample, gradio_app.py:343-358:
  *            x <- (x - c0 * eps) / c1  with c0 = (1 - alpha_t)/sqrt(1 - abar_t), c1 = sqrt(alpha_t); then, when z != NULL
  *            (not the last step and next_t > 0), x <- c2 * x + c3 * z with c2 = sqrt(alpha_next), c3 = sqrt(1 - alpha_next)
- * The scalars are computed by the host with the reference's own torch expressions. */
+ * The scalars are computed by the host with the reference's own torch expressions.  A mode outside 1..3 or a null x or eps
+ * is PSG_ERR_ARG; n <= 0 is PSG_OK with nothing launched. */
 int psg_sampler_update_f32(float* x, const float* eps, const float* z, int mode, float c0, float c1, float c2,
                            float c3, int64_t n, psg_stream_t stream);
 
-/* VAE reparameterisation, src/models/vae_decoder.py:120-123: out = mu + eps * exp(0.5 * logvar) (fp32, separately rounded). */
+/* VAE reparameterisation, src/models/vae_decoder.py:120-123: out = mu + eps * exp(0.5 * logvar) (fp32, separately rounded).
+ * n <= 0 is PSG_OK with nothing launched; a null pointer is PSG_ERR_ARG. */
 int psg_reparam_f32(const float* mu, const float* logvar, const float* eps, float* out, int64_t n, psg_stream_t stream);
 /* Its backward (stage 1 trains the encoder through the sample, vae_decoder.py:120-123): dmu = dlatent,
  * dlogvar = dlatent * eps * 0.5 * exp(0.5 * logvar); either output may be NULL; accumulate != 0 adds into what dmu / dlogvar
- * hold. */
+ * hold.  logvar and eps are read only for dlogvar and may be NULL without it.  A null dlatent, both outputs NULL, or dlogvar
+ * without logvar and eps is PSG_ERR_ARG; n <= 0 is PSG_OK with nothing launched. */
 int psg_reparam_bwd_f32(const float* dlatent, const float* logvar, const float* eps, float* dmu, float* dlogvar, int accumulate,
                         int64_t n, psg_stream_t stream);
 
 /* SmoothL1Loss(beta) mean + its gradient — improved_diffusion_trainer.py:300,388,396.
  * loss_out: fp32 device scalar; grad (may be NULL) = dL/dpred * grad_scale.  Deterministic
- * two-stage reduction.  ws: >= psg_reduce_workspace_bytes() bytes. */
+ * two-stage reduction.  ws: >= psg_reduce_workspace_bytes() bytes.  *nan_flag (may be NULL; never cleared here) is
+ * OR-ed with PSG_FLAG_PRED_BAD if any pred is NaN/Inf and with PSG_FLAG_LOSS_BAD if the loss is.  n <= 0 or
+ * beta <= 0 is PSG_ERR_SHAPE; a null pred, target, loss_out or ws is PSG_ERR_ARG. */
 int psg_smooth_l1_f32(const float* pred, const float* target, float* grad, float* loss_out,
                       int32_t* nan_flag, float beta, float grad_scale, int64_t n, void* ws,
                       psg_stream_t stream);
@@ -126,7 +135,9 @@ int64_t psg_reduce_workspace_bytes(void);
  * (F.l1_loss + 0.1 * F.mse_loss, both means over all n elements):
  *   out3 (3 fp32 device scalars) = { w_l1 * mean|d| + w_mse * mean d^2, mean|d|, mean d^2 },  d = pred - target
  *   grad (may be NULL) = (w_l1 * sign(d) + 2 * w_mse * d) / n
- * Deterministic two-stage reduction.  ws: >= psg_recon_loss_workspace_bytes() bytes. */
+ * with sign(0) = 0; the three scalars do not depend on whether grad is given.
+ * Deterministic two-stage reduction.  ws: >= psg_recon_loss_workspace_bytes() bytes.  n <= 0 is PSG_ERR_SHAPE; a null pred,
+ * target, out3 or ws is PSG_ERR_ARG. */
 int psg_recon_loss_f32(const float* pred, const float* target, float* grad, float* out3, int64_t n, float w_l1,
                        float w_mse, void* ws, psg_stream_t stream);
 int64_t psg_recon_loss_workspace_bytes(void);
@@ -183,17 +194,21 @@ int64_t psg_kl_workspace_bytes(void);
 /* ---------------------------------------------------------------------------
  * Layout / small ops at the boundary (NCHW fp32 <-> channels-last dtype)
  * ------------------------------------------------------------------------- */
-/* [B,C,HW] fp32 -> [B,HW,C] dtype (UNet.forward input, unet.py:448) and back (:507-509). */
+/* [B,C,HW] fp32 -> [B,HW,C] dtype (UNet.forward input, unet.py:448) and back (:507-509).  ld_dst / ld_src: the row stride of
+ * the channels-last side in elements, >= C; columns C..ld-1 are neither read nor written.  B, C or HW <= 0 or ld < C is
+ * PSG_ERR_SHAPE; a null pointer is PSG_ERR_ARG. */
 int psg_nchw_to_nhwc(const float* src, void* dst, int64_t ld_dst, int B, int C, int HW, int dtype,
                      psg_stream_t stream);
 int psg_nhwc_to_nchw(const void* src, int64_t ld_src, float* dst, int B, int C, int HW, int dtype,
                      psg_stream_t stream);
 /* AdaptiveAvgPool1d(1) over tokens — unet.py:322,445: text [B,S,D] fp32 -> out[B, :D] (dtype),
- * and the dtype copy of the token embeddings themselves (text_cast, may be NULL). */
+ * and the dtype copy of the token embeddings themselves (text_cast, may be NULL; contiguous [B,S,D]).  Columns D..ld_pooled-1
+ * are not written.  B, S or D <= 0 or ld_pooled < D is PSG_ERR_SHAPE; a null text or pooled is PSG_ERR_ARG. */
 int psg_text_pool(const float* text, void* pooled, int64_t ld_pooled, void* text_cast, int B, int S,
                   int D, int dtype, psg_stream_t stream);
 /* Sinusoidal features — unet.py:47-50: out[b, :half]=sin(t*coeff), out[b, half:]=cos(t*coeff),
- * accurate sinf/cosf (arguments reach 999 rad). */
+ * accurate sinf/cosf (arguments reach 999 rad).  Columns 2*half..ld_out-1 are not written.  B or half <= 0 or
+ * ld_out < 2*half is PSG_ERR_SHAPE; a null pointer is PSG_ERR_ARG. */
 int psg_timestep_sinusoid(const int64_t* t, const float* coeff, void* out, int64_t ld_out, int B,
                           int half, int dtype, psg_stream_t stream);
 /* nn.Upsample(size, bilinear, align_corners=False) — unet.py:365,375,385, channels-last. */
@@ -665,13 +680,18 @@ int psg_cosine_loss(const void* u, int64_t ldu, const void* v, int64_t ldv, void
 /* ---------------------------------------------------------------------------
  * Optimizer side — improved_diffusion_trainer.py:399-413
  * ------------------------------------------------------------------------- */
-/* out[0] (+)= sum(g^2) over n fp32 values; deterministic.  Replaces the 478 .item() syncs (:399-404). */
+/* out[0] (+)= sum(g^2) over n fp32 values; deterministic.  Replaces the 478 .item() syncs (:399-404).  Any n >= 1 (n need
+ * not be a multiple of 4); g must be 16-byte aligned (PSG_ERR_ALIGN otherwise); ws: >= psg_reduce_workspace_bytes() bytes.
+ * n <= 0 is PSG_ERR_SHAPE; a null pointer is PSG_ERR_ARG. */
 int psg_sumsq_f32(const float* g, int64_t n, float* out, int accumulate, void* ws, psg_stream_t stream);
 /* clip_grad_norm_ (:410) fused with AdamW (:277-283,412): coef = min(1, max_norm/(sqrt(*normsq)+1e-6))
  * read on the device (normsq may be NULL = no clipping); decoupled weight decay; step is 1-based.
  * skip_flag (may be NULL): when (*skip_flag & PSG_FLAG_SKIP_MASK) != 0 the update is skipped (NaN batch, :353-393).
  * shadow_bf16 (may be NULL): bf16 copy of the updated parameters written in the same pass, element i at
- * shadow_bf16[i] — with OHWI master weights this IS the prepared forward weight of the next step. */
+ * shadow_bf16[i] — with OHWI master weights this IS the prepared forward weight of the next step.
+ * n % 4 == 0 with p, g, m, v 16-byte aligned runs a float4 kernel, anything else a scalar one with the same bits per
+ * element.  The shadow exists on the float4 path only (and must itself be 8-byte aligned): PSG_ERR_ALIGN otherwise, with
+ * nothing written.  n <= 0 or step < 1 is PSG_ERR_SHAPE; a null p, g, m or v is PSG_ERR_ARG. */
 int psg_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
                   float beta2, float eps, float weight_decay, int step, const float* normsq,
                   float max_norm, const int32_t* skip_flag, void* shadow_bf16, psg_stream_t stream);
@@ -680,7 +700,8 @@ int psg_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n, float
  * :353-393,412-418) without a host read of the flag: step = *step_dev + 1 (1-based, bias correction computed in
  * the kernel), lr = lr_table[k], beta1 = beta1_table[k] with k = min(step - 1, sched_len - 1) (entry k = the values
  * the reference's scheduler holds after k scheduler.step() calls; OneCycleLR (:313-319) cycles Adam's beta1 along
- * with the lr; beta1_table may be NULL = constant beta1), and *step_dev += 1 after the update unless skipped. */
+ * with the lr; beta1_table may be NULL = constant beta1), and *step_dev += 1 after the update unless skipped.
+ * n <= 0 or sched_len < 1 is PSG_ERR_SHAPE; a null p, g, m, v, lr_table or step_dev is PSG_ERR_ARG; the shadow as above. */
 int psg_adamw_dev_f32(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_table,
                       const float* beta1_table, int sched_len, float beta1, float beta2, float eps,
                       float weight_decay, int32_t* step_dev, const float* normsq, float max_norm,
@@ -719,7 +740,8 @@ int psg_adamw_groups_sets_f32(float* p, const float* g, float* m, float* v, int6
                               const float* lr, const float* weight_decay, const float* max_norm, const int32_t* clip_set,
                               float beta1, float beta2, float eps, int32_t* step_dev, const float* normsq,
                               const int32_t* skip_flag, psg_stream_t stream);
-/* g *= min(1, max_norm/(sqrt(*normsq)+1e-6)) — plain clip for callers that keep torch.optim. */
+/* g *= min(1, max_norm/(sqrt(*normsq)+1e-6)) — plain clip for callers that keep torch.optim.  A coefficient >= 1 writes
+ * nothing.  n <= 0 is PSG_OK with nothing launched; a null g or normsq is PSG_ERR_ARG. */
 int psg_clip_scale_f32(float* g, int64_t n, const float* normsq, float max_norm, psg_stream_t stream);
 
 /* ---------------------------------------------------------------------------

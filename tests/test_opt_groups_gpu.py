@@ -61,29 +61,37 @@ def _sumsq_groups(lib, g, bounds):
     return out
 
 
-def _dev_vs_groups(lib, n, steps, seed):
-    """The same buffers through psg_adamw_dev_f32 and psg_adamw_groups_f32 (G = 1): (p, m, v) of both."""
+DEV_KW = dict(lr=3e-4, wd=0.01, max_norm=1.0, beta1=0.9, beta2=0.999, eps=1e-6)
+
+
+def _dev_vs_groups(lib, n, steps, seed, slices=None):
+    """The same buffers through psg_adamw_dev_f32 and psg_adamw_groups_f32 (G = 1): (p, m, v) of both.  slices: also return what
+    the last step started from on those slices - {"p", "g", "m", "v": one tensor per slice, "nsq": the squared norm it read}."""
     from pokemon_sprite_generator_amd import _lib
     gen = torch.Generator(device=DEV).manual_seed(seed)
     p0 = torch.randn(n, device=DEV, generator=gen)
     a, b = [p0.clone(), torch.zeros_like(p0), torch.zeros_like(p0)], [p0.clone(), torch.zeros_like(p0), torch.zeros_like(p0)]
     del p0
     step_a, step_b = torch.zeros(1, dtype=torch.int32, device=DEV), torch.zeros(1, dtype=torch.int32, device=DEV)
-    lr, wd, max_norm = 3e-4, 0.01, 1.0
+    lr, wd, max_norm = DEV_KW["lr"], DEV_KW["wd"], DEV_KW["max_norm"]
     table = torch.full((1,), lr, device=DEV)
+    kept = None
     g = torch.empty(n, device=DEV)
     for step in range(steps):
         g.normal_(generator=gen).mul_(SCALES[step % 2])
         nsq = _sumsq_groups(lib, g, [0, n])
         ref = float(g.double().pow(2).sum())
         assert abs(float(nsq[0]) - ref) / ref < NORM_BAR, (n, step, float(nsq[0]), ref)
+        if slices is not None and step == steps - 1:
+            kept = {k: [t[s].clone() for s in slices] for k, t in (("p", a[0]), ("g", g), ("m", a[1]), ("v", a[2]))}
+            kept["nsq"] = float(nsq[0])
         _lib.check(lib.psg_adamw_dev_f32(_ptr(a[0]), _ptr(g), _ptr(a[1]), _ptr(a[2]), n, _ptr(table), None, 1, 0.9, 0.999, 1e-6, wd,
                                          _ptr(step_a), _ptr(nsq), max_norm, None, None, _lib.stream_ptr()), "adamw_dev")
         _lib.check(lib.psg_adamw_groups_f32(_ptr(b[0]), _ptr(g), _ptr(b[1]), _ptr(b[2]), n, _i64([0, n]), 1, _f32([lr]), _f32([wd]),
                                             _f32([max_norm]), 0.9, 0.999, 1e-6, _ptr(step_b), _ptr(nsq), None, _lib.stream_ptr()),
                    "adamw_groups")
     assert int(step_a) == int(step_b) == steps
-    return a, b
+    return (a, b) if slices is None else (a, b, kept)
 
 
 @pytest.mark.parametrize("n", [8, 1032, 3 * 256 * 8 + 8])
@@ -97,13 +105,29 @@ def test_one_group_is_adamw_dev_bitwise(psg, n):
 
 def test_one_group_past_the_grid_cap_is_adamw_dev_bitwise(psg):
     """262144 * 256 float4s fill the capped grid once: 778 more make the second float4 of a trip exist for some lanes only.  The
-    norm reduction runs its 1024 workgroups over ~1000 trips each."""
+    norm reduction runs its 1024 workgroups over ~1000 trips each.
+
+    Both kernels share one loop body, so equal bits alone would let a mispaired second float4 pass: three slices of p, m and v
+    are also held to the fp64 restatement and bound of tests/step_ref.py (computed on the device) - the first 4096 float4s,
+    the float4s from index 262144 * 256 on (the first elements reached as the second float4 of a trip; 778 exist), and the
+    last 4096 float4s (the tail of the first trip, lanes whose second float4 does not exist, and those 778 again)."""
     from pokemon_sprite_generator_amd import _lib
-    n = (262144 * 256 + 778) * 4
-    a, b = _dev_vs_groups(_lib.load(), n, 1, 12)
+    from tests import step_ref
+    cap4, steps = 262144 * 256, 1
+    n4 = cap4 + 778
+    n = n4 * 4
+    slices = [slice(0, 4 * 4096), slice(4 * cap4, 4 * min(cap4 + 4096, n4)), slice(4 * (n4 - 4096), n)]
+    a, b, start = _dev_vs_groups(_lib.load(), n, steps, 12, slices)
     for x, y, name in zip(a, b, "pmv"):
         assert torch.equal(x, y), name
-    del a, b
+    for i, s in enumerate(slices):
+        ref = step_ref.adamw(start["p"][i], start["g"][i], start["m"][i], start["v"][i], steps, lr=DEV_KW["lr"], beta1=DEV_KW["beta1"],
+                             beta2=DEV_KW["beta2"], eps=DEV_KW["eps"], wd=DEV_KW["wd"], normsq=start["nsq"], max_norm=DEV_KW["max_norm"])
+        assert ref["p"][0].is_cuda and ref["p"][0].numel() == s.stop - s.start > 0
+        ratios = step_ref.check_adamw({"p": a[0][s], "m": a[1][s], "v": a[2][s]}, ref, f"past the cap, slice {i}")
+        print(f"RATIO adamw_dev past the cap, slice {i}: p {ratios['p']:.3g} m {ratios['m']:.3g} v {ratios['v']:.3g}")
+        assert not torch.equal(a[0][s], start["p"][i])
+    del a, b, start
     torch.cuda.empty_cache()
 
 
