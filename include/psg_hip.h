@@ -706,6 +706,28 @@ int psg_adamw_dev_f32(float* p, const float* g, float* m, float* v, int64_t n, c
                       const float* beta1_table, int sched_len, float beta1, float beta2, float eps,
                       float weight_decay, int32_t* step_dev, const float* normsq, float max_norm,
                       const int32_t* skip_flag, void* shadow_bf16, psg_stream_t stream);
+/* psg_adamw_dev_f32 with an exponential moving average of the parameters kept IN THE SAME PASS (the reference has none: an
+ * opt-in of this project).  p, m, v, the optional bf16 shadow and *step_dev get psg_adamw_dev_f32's bits; and with p' the
+ * parameter value just computed, still in registers,
+ *     ema[i] = fl( fl(d * ema[i]) + fl(fl(1 - d) * p'[i]) )
+ * - two products and one sum, each rounded to nearest on its own (__fmul_rn / __fadd_rn / __fsub_rn: no FMA).
+ * d = ema_decay when ema_warmup == 0, else d = min(ema_decay, fl(fl(1 + k) / fl(10 + k))) with k = (float)(*step_dev + 1), the
+ * 1-based step the bias correction uses: formed once per thread, in fp32, from the device's own step count, so that a
+ * captured graph warms up without host arithmetic.  A skipped step ((*skip_flag & PSG_FLAG_SKIP_MASK) != 0) writes nothing
+ * at all, ema included.  ema: n fp32 values, not overlapping the other operands; 16-byte aligned it keeps the float4
+ * kernel (10 x 16-byte loads in flight per lane, 38 instead of 30 bytes per parameter with the shadow), otherwise the
+ * scalar kernel runs with the same bits per element (and the shadow is refused as above).  Checked on the host before
+ * anything is launched: a null ema is PSG_ERR_ARG, ema_decay outside [0, 1) (NaN included) is PSG_ERR_SHAPE, everything else
+ * as psg_adamw_dev_f32. */
+int psg_adamw_dev_ema_f32(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_table,
+                          const float* beta1_table, int sched_len, float beta1, float beta2, float eps,
+                          float weight_decay, int32_t* step_dev, const float* normsq, float max_norm,
+                          const int32_t* skip_flag, void* shadow_bf16, float* ema, float ema_decay, int ema_warmup,
+                          psg_stream_t stream);
+/* a[i] <-> b[i] for n fp32 values, in place (the masters and their EMA change places: contents move, pointers do not).
+ * float4 where n % 4 == 0 and both are 16-byte aligned, scalar otherwise.  A null pointer is PSG_ERR_ARG; n <= 0 or a == b
+ * is PSG_OK with nothing launched; ranges that overlap without being equal are PSG_ERR_ARG. */
+int psg_swap_f32(float* a, float* b, int64_t n, psg_stream_t stream);
 /* Grouped forms (stage 1, src/training/vae_trainer.py:164-187,341-342: the VAE and the text encoder under one optimizer with
  * their own learning rate, and one clip_grad_norm_ each).  One flat fp32 arena of n floats is split into G consecutive
  * groups, 1 <= G <= PSG_OPT_MAX_GROUPS: group i covers the floats [bounds[i], bounds[i+1]).  bounds is a HOST array of G+1

@@ -12,7 +12,7 @@ from .unet import CrossAttentionBlock, ResBlock, TimestepEmbedding, UNet, UNetBl
 from .optim import FusedAdamW, GradArena, GroupedAdamW, ParamArena
 from .ddp import BucketedAllReduce
 from .trainer import DiffusionStepper, DiffusionTrainer, ImprovedDiffusionTrainer
-from .inference import LatentGenerator, LinearNoiseScheduler, gradio_ddpm_sample
+from .inference import LatentGenerator, LinearNoiseScheduler, gradio_ddpm_sample, load_unet_state
 from .vae import PokemonVAE, VAEDecoder, VAEEncoder
 from .text_encoder import TextEncoder
 from .losses import CombinedLoss, VGGPerceptualLoss
@@ -26,6 +26,6 @@ from .generate import SpriteGenerator
 
 __all__ = ["UNet", "UNetBlock", "ResBlock", "CrossAttentionBlock", "TimestepEmbedding", "NoiseScheduler",
            "ImprovedDiffusionTrainer", "DiffusionTrainer", "DiffusionStepper", "FusedAdamW", "GradArena", "ParamArena",
-           "BucketedAllReduce", "LatentGenerator", "LinearNoiseScheduler", "gradio_ddpm_sample", "PokemonVAE", "VAEEncoder", "VAEDecoder", "TextEncoder", "VGGPerceptualLoss", "CombinedLoss", "CLIPLoss",
+           "BucketedAllReduce", "LatentGenerator", "LinearNoiseScheduler", "gradio_ddpm_sample", "load_unet_state", "PokemonVAE", "VAEEncoder", "VAEDecoder", "TextEncoder", "VGGPerceptualLoss", "CombinedLoss", "CLIPLoss",
            "FinalPokemonGenerator", "FinalStepper", "GroupedAdamW", "VAEStepper", "SpriteDataset", "SpriteLoader", "create_data_loaders", "draw_params", "SpriteGenerator", "VAETrainer", "FinalTrainer", "TokenTable", "PsgError", "LIB_PATH"]
 __version__ = "0.1.0"

@@ -506,14 +506,35 @@ __global__ void adam_step_advance_kernel(int32_t* step_dev, const int32_t* skip_
     if (!(skip_flag && (*skip_flag & PSG_FLAG_SKIP_MASK))) *step_dev += 1;
 }
 
+// EMA of the parameters in the optimizer's own pass (psg_adamw_dev_ema_f32): d = ema_decay, or with the warm-up
+// min(ema_decay, (1 + k) / (10 + k)) for the 1-based step k = *step_dev + 1 that adam_sched forms too; once per thread, fp32,
+// every operation one rounding.  Returns d, and 1 - d through `omd`.
+__device__ __forceinline__ float ema_decay_dev(const AdamSched& sc, float ema_decay, int ema_warmup, float& omd) {
+    float d = ema_decay;
+    if (ema_warmup) {
+        const float k = (float)(*sc.step_dev + 1);
+        d = fminf(d, __fdiv_rn(__fadd_rn(1.0f, k), __fadd_rn(10.0f, k)));
+    }
+    omd = __fsub_rn(1.0f, d);
+    return d;
+}
+// ema' = fl(fl(d ema) + fl((1 - d) p')): two products and one sum, no FMA
+__device__ __forceinline__ float ema_next(float d, float omd, float ema, float p_new) {
+    return __fadd_rn(__fmul_rn(d, ema), __fmul_rn(omd, p_new));
+}
+
+template <bool EMA>
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, int64_t n, float lr, float beta1, float beta2, float eps,
                              float wd, float bc1, float bc2_sqrt, const float* normsq, float max_norm,
-                             const int32_t* skip_flag, const AdamSched sc) {
+                             const int32_t* skip_flag, const AdamSched sc, float* __restrict__ ema, float ema_decay,
+                             int ema_warmup) {
     if (skip_flag && (*skip_flag & PSG_FLAG_SKIP_MASK)) return;
     adam_sched(sc, beta1, beta2, lr, bc1, bc2_sqrt);
     const float coef = clip_coef_dev(normsq, max_norm);
     const float step_size = lr / bc1;
+    float d = 0.f, omd = 0.f;
+    if constexpr (EMA) d = ema_decay_dev(sc, ema_decay, ema_warmup, omd);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float gi = g[i] * coef;
         float pi = p[i] * (1.0f - lr * wd);
@@ -522,21 +543,28 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
         const float denom = sqrtf(vi) / bc2_sqrt + eps;
         pi -= step_size * (mi / denom);
         p[i] = pi; m[i] = mi; v[i] = vi;
+        if constexpr (EMA) ema[i] = ema_next(d, omd, ema[i], pi);
     }
 }
 
-// float4 form for the flat arenas (n % 4 == 0, 16-byte aligned): same arithmetic per element, optional bf16 shadow
+// float4 form for the flat arenas (n % 4 == 0, 16-byte aligned): same arithmetic per element, optional bf16 shadow.
+// EMA = false is the optimizer alone; EMA = true also reads and writes `ema` (8 more bytes per parameter instead of the 12
+// of a pass of its own, which would read the fresh p again).
+template <bool EMA>
 __global__ void adamw_kernel4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                               float* __restrict__ v, int64_t n4, float lr, float beta1, float beta2, float eps,
                               float wd, float bc1, float bc2_sqrt, const float* normsq, float max_norm,
-                              const int32_t* skip_flag, bf16_t* __restrict__ shadow, const AdamSched sc) {
+                              const int32_t* skip_flag, bf16_t* __restrict__ shadow, const AdamSched sc,
+                              float* __restrict__ ema, float ema_decay, int ema_warmup) {
     if (skip_flag && (*skip_flag & PSG_FLAG_SKIP_MASK)) return;
     adam_sched(sc, beta1, beta2, lr, bc1, bc2_sqrt);
     const float coef = clip_coef_dev(normsq, max_norm);
     const float step_size = lr / bc1;
+    float d = 0.f, omd = 0.f;
+    if constexpr (EMA) d = ema_decay_dev(sc, ema_decay, ema_warmup, omd);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n4; i0 += 2 * stride) {
-        // two independent float4 groups per trip: 8 x 16-byte loads in flight per lane before the first use
+        // two independent float4 groups per trip: 8 x 16-byte loads in flight per lane before the first use (10 with the EMA)
         const int64_t i1 = i0 + stride;
         const bool two = i1 < n4;
         const int64_t j1 = two ? i1 : i0;
@@ -547,6 +575,13 @@ __global__ void adamw_kernel4(float* __restrict__ p, const float* __restrict__ g
         f32x4 P[2] = {ld(p, i0), ld(p, j1)};
         f32x4 M[2] = {ld(m, i0), ld(m, j1)};
         f32x4 V[2] = {ld(v, i0), ld(v, j1)};
+        f32x4 E[2];
+        if constexpr (EMA) {
+            E[0] = ld(ema, i0); E[1] = ld(ema, j1);
+            // keep all 10 loads in front of the arithmetic: left alone, the scheduler issues 4, computes the first group and
+            // only then issues the other 6
+            __builtin_amdgcn_sched_barrier(0);
+        }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
 #pragma unroll
@@ -558,14 +593,26 @@ __global__ void adamw_kernel4(float* __restrict__ p, const float* __restrict__ g
                 const float denom = sqrtf(vi) / bc2_sqrt + eps;
                 pi -= step_size * (mi / denom);
                 P[u][e] = pi; M[u][e] = mi; V[u][e] = vi;
+                if constexpr (EMA) E[u][e] = ema_next(d, omd, E[u][e], pi);
             }
         }
         stv(p, i0, P[0]); stv(m, i0, M[0]); stv(v, i0, V[0]);
         if (shadow) store4<bf16_t>(shadow + 4 * i0, P[0]);
+        if constexpr (EMA) stv(ema, i0, E[0]);
         if (two) {
             stv(p, i1, P[1]); stv(m, i1, M[1]); stv(v, i1, V[1]);
             if (shadow) store4<bf16_t>(shadow + 4 * i1, P[1]);
+            if constexpr (EMA) stv(ema, i1, E[1]);
         }
+    }
+}
+
+// psg_swap_f32: a <-> b in place; T = f32x4 on the aligned path, float otherwise
+template <typename T>
+__global__ void swap_kernel(T* __restrict__ a, T* __restrict__ b, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const T x = a[i], y = b[i];
+        a[i] = y; b[i] = x;
     }
 }
 
@@ -1019,17 +1066,23 @@ int psg_sumsq_f32(const float* g, int64_t n, float* out, int accumulate, void* w
 
 static int adamw_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                         float weight_decay, float bc1, float bc2_sqrt, const float* normsq, float max_norm,
-                        const int32_t* skip_flag, void* shadow_bf16, const AdamSched& sc, psg_stream_t stream) {
-    const bool vec = n % 4 == 0 && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && (!shadow_bf16 || aligned8(shadow_bf16));
+                        const int32_t* skip_flag, void* shadow_bf16, const AdamSched& sc, psg_stream_t stream,
+                        float* ema = nullptr, float ema_decay = 0.f, int ema_warmup = 0) {
+    const bool vec = n % 4 == 0 && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && (!shadow_bf16 || aligned8(shadow_bf16)) &&
+                     aligned16(ema);
     PSG_REQUIRE(!shadow_bf16 || vec, PSG_ERR_ALIGN, "adamw: the bf16 shadow needs n %% 4 == 0 and 16-byte aligned buffers");
+    // grid (float4): 262144 workgroups at most (2-3 trips of the 2 x float4 loop on the 640 M-parameter arena): 3.15 ms against
+    // 3.35 ms with 8192 long-running ones (6.1 vs 5.7 TB/s)
+    const dim3 grid(vec ? grid_for(n / 4, 256, 262144) : grid_for(n, 256, 4096));
+    const int64_t count = vec ? n / 4 : n;
+    auto launch4 = ema ? adamw_kernel4<true> : adamw_kernel4<false>;
+    auto launch1 = ema ? adamw_kernel<true> : adamw_kernel<false>;
     if (vec) {
-        // grid: 262144 workgroups at most (2-3 trips of the 2 x float4 loop on the 640 M-parameter arena): 3.15 ms against
-        // 3.35 ms with 8192 long-running ones (6.1 vs 5.7 TB/s)
-        hipLaunchKernelGGL(adamw_kernel4, dim3(grid_for(n / 4, 256, 262144)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n / 4, lr,
-                           beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, normsq, max_norm, skip_flag, (bf16_t*)shadow_bf16, sc);
+        hipLaunchKernelGGL(launch4, grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, count, lr, beta1, beta2, eps, weight_decay, bc1,
+                           bc2_sqrt, normsq, max_norm, skip_flag, (bf16_t*)shadow_bf16, sc, ema, ema_decay, ema_warmup);
     } else {
-        hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr,
-                           beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, normsq, max_norm, skip_flag, sc);
+        hipLaunchKernelGGL(launch1, grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, count, lr, beta1, beta2, eps, weight_decay, bc1,
+                           bc2_sqrt, normsq, max_norm, skip_flag, sc, ema, ema_decay, ema_warmup);
     }
     PSG_LAUNCH_CHECK("adamw");
     return PSG_OK;
@@ -1046,16 +1099,50 @@ int psg_adamw_f32(float* p, const float* g, float* m, float* v, int64_t n, float
     return adamw_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2), normsq, max_norm, skip_flag, shadow_bf16, sc, stream);
 }
 
+static int adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_table, const float* beta1_table,
+                     int sched_len, float beta1, float beta2, float eps, float weight_decay, int32_t* step_dev, const float* normsq,
+                     float max_norm, const int32_t* skip_flag, void* shadow_bf16, float* ema, float ema_decay, int ema_warmup,
+                     psg_stream_t stream) {
+    const AdamSched sc = {step_dev, lr_table, beta1_table, sched_len};
+    const int rc = adamw_launch(p, g, m, v, n, 0.f, beta1, beta2, eps, weight_decay, 1.f, 1.f, normsq, max_norm, skip_flag, shadow_bf16, sc, stream,
+                                ema, ema_decay, ema_warmup);
+    if (rc) return rc;
+    hipLaunchKernelGGL(adam_step_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_dev, skip_flag);
+    PSG_LAUNCH_CHECK("adam_step_advance");
+    return PSG_OK;
+}
+
 int psg_adamw_dev_f32(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_table, const float* beta1_table,
                       int sched_len, float beta1, float beta2, float eps, float weight_decay, int32_t* step_dev, const float* normsq,
                       float max_norm, const int32_t* skip_flag, void* shadow_bf16, psg_stream_t stream) {
     PSG_REQUIRE(p && g && m && v && lr_table && step_dev, PSG_ERR_ARG, "adamw_dev: null pointer");
     PSG_REQUIRE(n > 0 && sched_len >= 1, PSG_ERR_SHAPE, "adamw_dev: n=%ld sched_len=%d", (long)n, sched_len);
-    const AdamSched sc = {step_dev, lr_table, beta1_table, sched_len};
-    const int rc = adamw_launch(p, g, m, v, n, 0.f, beta1, beta2, eps, weight_decay, 1.f, 1.f, normsq, max_norm, skip_flag, shadow_bf16, sc, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(adam_step_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_dev, skip_flag);
-    PSG_LAUNCH_CHECK("adam_step_advance");
+    return adamw_dev(p, g, m, v, n, lr_table, beta1_table, sched_len, beta1, beta2, eps, weight_decay, step_dev, normsq, max_norm, skip_flag,
+                     shadow_bf16, nullptr, 0.f, 0, stream);
+}
+
+int psg_adamw_dev_ema_f32(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_table, const float* beta1_table,
+                          int sched_len, float beta1, float beta2, float eps, float weight_decay, int32_t* step_dev, const float* normsq,
+                          float max_norm, const int32_t* skip_flag, void* shadow_bf16, float* ema, float ema_decay, int ema_warmup,
+                          psg_stream_t stream) {
+    PSG_REQUIRE(p && g && m && v && lr_table && step_dev && ema, PSG_ERR_ARG, "adamw_dev_ema: null pointer");
+    PSG_REQUIRE(n > 0 && sched_len >= 1, PSG_ERR_SHAPE, "adamw_dev_ema: n=%ld sched_len=%d", (long)n, sched_len);
+    PSG_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, PSG_ERR_SHAPE, "adamw_dev_ema: ema_decay=%g outside [0, 1)", (double)ema_decay);
+    return adamw_dev(p, g, m, v, n, lr_table, beta1_table, sched_len, beta1, beta2, eps, weight_decay, step_dev, normsq, max_norm, skip_flag,
+                     shadow_bf16, ema, ema_decay, ema_warmup != 0, stream);
+}
+
+int psg_swap_f32(float* a, float* b, int64_t n, psg_stream_t stream) {
+    PSG_REQUIRE(a && b, PSG_ERR_ARG, "swap: null pointer");
+    if (n <= 0 || a == b) return PSG_OK;
+    PSG_REQUIRE(a + n <= b || b + n <= a, PSG_ERR_ARG, "swap: the two ranges overlap");
+    if (n % 4 == 0 && aligned16(a) && aligned16(b)) {
+        hipLaunchKernelGGL(swap_kernel<f32x4>, dim3(grid_for(n / 4, 256, 262144)), dim3(256), 0, (hipStream_t)stream,
+                           reinterpret_cast<f32x4*>(a), reinterpret_cast<f32x4*>(b), n / 4);
+    } else {
+        hipLaunchKernelGGL(swap_kernel<float>, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, a, b, n);
+    }
+    PSG_LAUNCH_CHECK("swap");
     return PSG_OK;
 }
 

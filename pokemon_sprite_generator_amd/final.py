@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import PsgError
-from .inference import LatentGenerator, LinearNoiseScheduler
+from .inference import LatentGenerator, LinearNoiseScheduler, load_unet_state
 from .ops import WeightCache
 from .optim import GradArena, GroupedAdamW, ParamArena
 from .text_encoder import TextEncoder
@@ -57,12 +57,14 @@ class FinalPokemonGenerator(nn.Module):
 
     @classmethod
     def from_checkpoints(cls, vae_path: str, diffusion_path: str, text_encoder_config: Dict[str, Any],
-                         compute_dtype: torch.dtype = torch.float32, trainable_decoder: bool = False, **text_encoder_kw):
+                         compute_dtype: torch.dtype = torch.float32, trainable_decoder: bool = False, use_ema: bool = False, **text_encoder_kw):
         """:90-160 - 'vae_state_dict' split into its encoder. / decoder. halves, 'unet_state_dict', and the stage-1
         checkpoint's optional 'text_encoder_state_dict'.  `trainable_decoder`: build the decoder with `trainable=True`, which
-        the joint phase needs (it starts frozen either way)."""
+        the joint phase needs (it starts frozen either way).  `use_ema`: the U-Net takes the checkpoint's 'ema_unet_state_dict'
+        (inference.load_unet_state; an error if it has none)."""
         cfg = text_encoder_config
         latent_dim, text_dim = cfg.get("latent_dim", 8), cfg["text_embedding_dim"]
+        unet_state = load_unet_state(diffusion_path, use_ema=use_ema)        # (first: refused before anything is built)
         vae_ckpt = torch.load(vae_path, map_location="cpu")
         enc = VAEEncoder(input_channels=3, latent_dim=latent_dim, compute_dtype=compute_dtype)
         dec = VAEDecoder(latent_dim=latent_dim, text_dim=text_dim, output_channels=3, compute_dtype=compute_dtype,
@@ -72,7 +74,7 @@ class FinalPokemonGenerator(nn.Module):
         dec.load_state_dict({k[8:]: v for k, v in vsd.items() if k.startswith("decoder.")})
         unet = UNet(latent_dim=latent_dim, text_dim=text_dim, time_emb_dim=cfg.get("time_emb_dim", 128), num_heads=cfg.get("num_heads", 8),
                     compute_dtype=compute_dtype)
-        unet.load_state_dict(torch.load(diffusion_path, map_location="cpu")["unet_state_dict"])
+        unet.load_state_dict(unet_state)
         text_encoder_kw.setdefault("trainable", True)
         te = TextEncoder(model_name=cfg["bert_model"], hidden_dim=text_dim, compute_dtype=compute_dtype, **text_encoder_kw)
         if "text_encoder_state_dict" in vae_ckpt:

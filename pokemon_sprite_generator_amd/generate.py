@@ -15,7 +15,7 @@ import torch
 
 from . import imaging
 from ._lib import PsgError
-from .inference import gradio_ddpm_sample
+from .inference import gradio_ddpm_sample, load_unet_state
 from .text_encoder import TextEncoder
 from .unet import UNet
 from .vae import PokemonVAE
@@ -36,18 +36,20 @@ class SpriteGenerator:
 
     @classmethod
     def from_checkpoints(cls, vae_path: str, diffusion_path: str, config: Dict[str, Any], compute_dtype: torch.dtype = torch.float32,
-                         device=None, **text_encoder_kw):
+                         device=None, use_ema: bool = False, **text_encoder_kw):
         """:186-277 with the custom U-Net - `config` is the reference's config dict (its 'model' section is read; a flat dict
         of those keys is taken as that section).  'vae_state_dict', 'unet_state_dict' and the stage-1 checkpoint's optional
-        'text_encoder_state_dict', as `FinalPokemonGenerator.from_checkpoints` reads them.  device=None: the current GPU."""
+        'text_encoder_state_dict', as `FinalPokemonGenerator.from_checkpoints` reads them.  device=None: the current GPU.
+        `use_ema`: the U-Net takes the checkpoint's 'ema_unet_state_dict' (inference.load_unet_state; an error if it has none)."""
         cfg = config.get("model", config)
         latent_dim, text_dim = cfg.get("latent_dim", 8), cfg.get("text_embedding_dim", 768)
+        unet_state = load_unet_state(diffusion_path, use_ema=use_ema)        # (first: refused before anything is built)
         vae_ckpt = torch.load(vae_path, map_location="cpu")
         vae = PokemonVAE(latent_dim=latent_dim, text_dim=text_dim, compute_dtype=compute_dtype)
         vae.load_state_dict(vae_ckpt["vae_state_dict"])
         unet = UNet(latent_dim=latent_dim, text_dim=text_dim, time_emb_dim=cfg.get("time_emb_dim", 128), num_heads=cfg.get("num_heads", 8),
                     compute_dtype=compute_dtype)
-        unet.load_state_dict(torch.load(diffusion_path, map_location="cpu")["unet_state_dict"])
+        unet.load_state_dict(unet_state)
         te = TextEncoder(model_name=cfg.get("bert_model", "google-bert/bert-base-uncased"), hidden_dim=text_dim,
                          finetune_strategy=cfg.get("bert_finetune_strategy", "minimal"), compute_dtype=compute_dtype, **text_encoder_kw)
         if "text_encoder_state_dict" in vae_ckpt:

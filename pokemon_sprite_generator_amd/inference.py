@@ -30,6 +30,19 @@ def _lib_for(t):
     return _lib.init(t.device.index if t.device.index is not None else torch.cuda.current_device())
 
 
+def load_unet_state(checkpoint, use_ema: bool = False, map_location="cpu"):
+    """The U-Net weights of a stage-2 checkpoint (a path, or the loaded dict): 'unet_state_dict' - or, with `use_ema`, the
+    averaged weights 'ema_unet_state_dict' that a trainer with `training.ema_decay` writes next to it (same keys and shapes).
+    Asking for the EMA of a checkpoint that has none is an error, never a silent fall-back to the raw weights."""
+    ckpt = checkpoint if isinstance(checkpoint, dict) else torch.load(checkpoint, map_location=map_location)
+    if not use_ema:
+        return ckpt["unet_state_dict"]
+    if "ema_unet_state_dict" not in ckpt:
+        where = "the checkpoint" if isinstance(checkpoint, dict) else str(checkpoint)
+        raise _lib.PsgError(f"use_ema=True, but {where} has no 'ema_unet_state_dict' (it was trained without training.ema_decay)")
+    return ckpt["ema_unet_state_dict"]
+
+
 def _f32(v):
     return np.float32(float(v))
 

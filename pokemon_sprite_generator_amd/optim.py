@@ -257,12 +257,15 @@ class FusedAdamW(torch.optim.Optimizer):
     count lives ON THE DEVICE (`step_dev`): the kernel advances it only when the step was not skipped by the NaN
     flag, and reads the learning rate from a device table indexed by it (`set_lr_table`: entry k = the lr after k
     scheduler steps) - the reference's `continue` on a bad batch (no optimizer.step, no scheduler.step,
-    improved_diffusion_trainer.py:353-393) without a host read per step.  `steps_done()` reads the counter (one sync)."""
+    improved_diffusion_trainer.py:353-393) without a host read per step.  `steps_done()` reads the counter (one sync).
+    `enable_ema(decay)` (arena mode; not in the reference, off by default) makes the same launch keep an exponential moving
+    average of the masters: `ema_state()`, `swap_ema()`."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, param_arena=None, grad_arena=None):
         params = list(params)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._pa, self._ga = None, None
+        self._ema, self.ema_decay, self.ema_warmup = None, None, True      # enable_ema
         if param_arena is not None and grad_arena is not None:
             same = (len(params) == len(param_arena.params) == len(grad_arena.params)
                     and all(a is b and a is c for a, b, c in zip(params, param_arena.params, grad_arena.params))
@@ -318,6 +321,49 @@ class FusedAdamW(torch.optim.Optimizer):
                 self._lr_host = lr
         return self._lr_table
 
+    # ---- EMA of the masters, kept by the update pass itself ------------------------------------------------
+    def enable_ema(self, decay, warmup=True):
+        """Keep an exponential moving average of the flat masters: from now on `step()` is psg_adamw_dev_ema_f32, which
+        updates `_ema` in the pass that writes the parameters (ema' = d ema + (1 - d) p'; with `warmup`
+        d = min(decay, (1 + k) / (10 + k)) for the 1-based device step k).  A skipped step leaves it untouched, a captured
+        graph carries it along.  The average starts as a copy of the masters at this moment.  Not part of state_dict()
+        (torch.optim.AdamW's layout): `ema_state()` is what a checkpoint stores."""
+        if self._pa is None or type(self) is not FusedAdamW:
+            raise _lib.PsgError("enable_ema needs FusedAdamW over a ParamArena / GradArena pair (one flat update)")
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"enable_ema: decay {decay} outside [0, 1)")
+        self._pa.check_alive()
+        if self._ema is None:
+            self._ema = torch.zeros_like(self._pa.flat)
+        self._ema.copy_(self._pa.flat)
+        self.ema_decay, self.ema_warmup = decay, bool(warmup)
+
+    def _need_ema(self, what):
+        if self._ema is None:
+            raise _lib.PsgError(f"{what}: no EMA is kept (enable_ema)")
+
+    def ema_state(self):
+        """The EMA per parameter, in the model's logical shapes (views of the flat EMA buffer with the parameters' own offsets
+        and strides: conv weights are NCHW-shaped over OHWI memory, as the moments are)."""
+        self._need_ema("ema_state")
+        return [self._pa.like(self._ema, i) for i in range(len(self._pa.params))]
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange the masters and the EMA in place (psg_swap_f32): the model then runs on the averaged weights, and a second
+        call puts everything back bit for bit.  Contents move, pointers do not: parameter views, a captured graph and the
+        projection group's bf16 run stay valid.  The bf16 shadow is refreshed from the new masters."""
+        self._need_ema("swap_ema")
+        self._pa.check_alive()
+        lib = _lib.init(self._pa.flat.device.index)
+        check(lib.psg_swap_f32(ptr(self._pa.flat), ptr(self._ema), self._pa.numel, stream_ptr()), "psg_swap_f32")
+        if self._pa.shadow is not None:
+            self._pa.shadow.copy_(self._pa.flat)
+        WeightCache.invalidate()
+        if self._pa.shadow is not None:
+            self._pa.mark_shadow_current()
+
     def _sync_steps(self):
         if self._pa is not None:
             n = float(self.steps_done())
@@ -356,9 +402,16 @@ class FusedAdamW(torch.optim.Optimizer):
             lib = _lib.init(self._pa.flat.device.index)
             shadow = self._pa.shadow
             table = self._lr_ptr()
-            check(lib.psg_adamw_dev_f32(ptr(self._pa.flat), ptr(self._ga.flat), ptr(self._m), ptr(self._v), self._pa.numel,
-                                        ptr(table), ptr(self._b1_table) if self._lr_sched else None, table.numel(), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
-                                        ptr(self.step_dev), nptr, float(max_norm), fptr, ptr(shadow), stream_ptr()), "psg_adamw_dev_f32")
+            if self._ema is None:
+                check(lib.psg_adamw_dev_f32(ptr(self._pa.flat), ptr(self._ga.flat), ptr(self._m), ptr(self._v), self._pa.numel,
+                                            ptr(table), ptr(self._b1_table) if self._lr_sched else None, table.numel(), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                                            ptr(self.step_dev), nptr, float(max_norm), fptr, ptr(shadow), stream_ptr()), "psg_adamw_dev_f32")
+            else:
+                check(lib.psg_adamw_dev_ema_f32(ptr(self._pa.flat), ptr(self._ga.flat), ptr(self._m), ptr(self._v), self._pa.numel,
+                                                ptr(table), ptr(self._b1_table) if self._lr_sched else None, table.numel(), float(b1), float(b2),
+                                                float(group["eps"]), float(group["weight_decay"]), ptr(self.step_dev), nptr, float(max_norm), fptr,
+                                                ptr(shadow), ptr(self._ema), self.ema_decay, int(self.ema_warmup), stream_ptr()),
+                      "psg_adamw_dev_ema_f32")
             WeightCache.invalidate()
             if shadow is not None:
                 self._pa.mark_shadow_current()       # the kernel just rewrote it (a skipped NaN step leaves both untouched)

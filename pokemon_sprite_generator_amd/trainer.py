@@ -22,6 +22,8 @@ The decision is made ON THE DEVICE (flag word, `psg_flag` in include/psg_hip.h):
 the step counter and the lr / beta1 schedule live in device memory and advance only
 on steps that happened, so the loop never reads the flag on the host.
 """
+import collections
+import contextlib
 import logging
 import os
 from pathlib import Path
@@ -63,7 +65,7 @@ class DiffusionStepper:
 
     def __init__(self, unet: UNet, noise_scheduler: NoiseScheduler, lr=1e-4, betas=(0.9, 0.999), weight_decay=0.01,
                  eps=1e-6, max_grad_norm=1.0, optimizer_type="adamw", distributed=None, bucket_bytes=64 << 20,
-                 grad_bucket_dtype=torch.float32, ddp_cu_reserve=None):
+                 grad_bucket_dtype=torch.float32, ddp_cu_reserve=None, ema_decay=None, ema_warmup=True):
         self.unet, self.noise_scheduler = unet, noise_scheduler
         self.max_grad_norm = max_grad_norm
         self.device = next(unet.parameters()).device
@@ -93,7 +95,14 @@ class DiffusionStepper:
             self.optimizer = FusedAdamW(self.arena.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                         param_arena=self.params, grad_arena=self.arena)
         else:
+            if ema_decay:
+                raise _lib.PsgError("ema_decay needs the fused AdamW (optimizer_type='adamw'): the EMA is kept by its update pass")
             self.optimizer = torch.optim.Adam(self.arena.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        # EMA of the masters (opt-in; None or 0: none, and nothing about the stepper changes).  Enabled after the broadcast
+        # above, so every rank's average starts from rank 0's masters.
+        self._ema_scope = False
+        if ema_decay and optimizer_type == "adamw":
+            self.optimizer.enable_ema(ema_decay, warmup=ema_warmup)
         self.reducer = BucketedAllReduce(self.arena.flat, self.arena.params, self.arena.offsets, bucket_bytes,
                                          bucket_dtype=grad_bucket_dtype, force_single=force_single,
                                          cu_reserve=ddp_cu_reserve) if distributed else None
@@ -115,6 +124,58 @@ class DiffusionStepper:
             self.unet.bind_proj_group(None, None)
         self.arena.release()
         self.params.release()
+
+    # ---- EMA ------------------------------------------------------------------------------------------------
+    @property
+    def ema_enabled(self) -> bool:
+        return getattr(self.optimizer, "_ema", None) is not None
+
+    def ema_state(self):
+        """The EMA per trainable parameter, in `unet.parameters()` order and the model's logical shapes."""
+        return self.optimizer.ema_state()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run the model on the averaged weights: the masters and the EMA change places on entry and again on exit (also on an
+        exception), bit for bit.  Training inside the scope raises; scopes do not nest."""
+        if not self.ema_enabled:
+            raise _lib.PsgError("ema_weights: this stepper keeps no EMA (ema_decay)")
+        if self._ema_scope:
+            raise _lib.PsgError("ema_weights: already inside an ema_weights() scope")
+        self.optimizer.swap_ema()
+        self._ema_scope = True
+        try:
+            yield self
+        finally:
+            self._ema_scope = False
+            self.optimizer.swap_ema()
+
+    def _ema_views(self):
+        names = {id(p): n for n, p in self.unet.named_parameters()}
+        return {names[id(p)]: v for p, v in zip(self.params.params, self.ema_state())}
+
+    def ema_state_dict(self):
+        """One entry for every entry of `unet.state_dict()`, same keys and shapes: the EMA for the trained parameters, a copy of
+        the model's own tensor for everything else (buffers, frozen parameters).  Loads into a fresh UNet."""
+        views = self._ema_views()
+        return collections.OrderedDict((k, (views[k] if k in views else v).detach().clone()) for k, v in self.unet.state_dict().items())
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, state_dict=None):
+        """Set the EMA from `ema_state_dict()`'s layout; None: to the current masters."""
+        self._no_ema_scope("load_ema_state_dict")
+        if state_dict is None:
+            self.optimizer._need_ema("load_ema_state_dict")
+            self.optimizer._ema.copy_(self.params.flat)
+            return
+        for k, v in self._ema_views().items():
+            if k not in state_dict:
+                raise KeyError(f"load_ema_state_dict: no entry for parameter {k}")
+            v.copy_(state_dict[k])
+
+    def _no_ema_scope(self, what):
+        if self._ema_scope:
+            raise _lib.PsgError(f"{what} inside an ema_weights() scope: the masters hold the averaged weights")
 
     def randn_like(self, x):
         """randn_like from this rank's stream (:373)."""
@@ -153,6 +214,7 @@ class DiffusionStepper:
         (the caller's own input checks, :353,359).  Returns device tensors {'loss','grad_norm','nan_flag'} (no sync);
         a step whose flag has a bit of FLAG_SKIP_MASK leaves parameters, optimizer state, step count and schedule
         untouched."""
+        self._no_ema_scope("train_step")
         if not self.unet.training:             # (module.train() walks all ~390 submodules: 1.6 ms of host time per call)
             self.unet.train()
         if ops_mod.SeedSource.enabled():       # fixed per-site seeds + a device word that changes per step (graph replay)
@@ -199,6 +261,7 @@ class DiffusionStepper:
         for the whole process - eager steps of this and any other stepper draw their masks that way too from then on -
         until the LAST live graph is closed (`GraphedTrainStep.close()`, or this stepper's `close()`; the source is reference
         counted, one count per graph: the device word is baked into captured kernel arguments)."""
+        self._no_ema_scope("capture_train_step")
         if self.reducer is not None:
             raise NotImplementedError("capture_train_step: data-parallel steps are not captured")
         if not isinstance(self.optimizer, FusedAdamW):
@@ -209,12 +272,15 @@ class DiffusionStepper:
         """Data parallel: measure which gradient-exchange mode is fastest on THIS machine (ddp.BucketedAllReduce.autotune: real
         train steps on the given batch, every rank takes part) WITHOUT training - masters, moments, step count and the bf16
         shadow are snapshotted (10 GB at full width) and put back, so the model, the optimizer and the schedule are exactly
-        where they were; only the random streams have moved on.  Returns the record (None in a single process)."""
+        where they were; only the random streams have moved on.  The EMA, when one is kept, is snapshotted and put back with
+        them.  Returns the record (None in a single process)."""
+        self._no_ema_scope("autotune_exchange")
         if self.reducer is None or not self.reducer.active or not isinstance(self.optimizer, FusedAdamW):
             return None
         opt = self.optimizer
         snap = (self.params.flat.clone(), opt._m.clone(), opt._v.clone(), opt.step_dev.clone(),
-                None if self.params.shadow is None else self.params.shadow.clone())
+                None if self.params.shadow is None else self.params.shadow.clone(),
+                None if opt._ema is None else opt._ema.clone())
         try:
             rec = self.reducer.autotune(lambda: self.train_step(latents, text_emb, t), trials=trials)
         finally:
@@ -222,6 +288,8 @@ class DiffusionStepper:
                 self.params.flat.copy_(snap[0]); opt._m.copy_(snap[1]); opt._v.copy_(snap[2]); opt.step_dev.copy_(snap[3])
                 if snap[4] is not None:
                     self.params.shadow.copy_(snap[4])
+                if snap[5] is not None:
+                    opt._ema.copy_(snap[5])
             ops_mod.WeightCache.invalidate()
             if self.params.shadow is not None:
                 self.params.mark_shadow_current()
@@ -320,6 +388,7 @@ class GraphedTrainStep:
         from .ops import WeightCache
         if self._closed:
             raise _lib.PsgError("GraphedTrainStep.run after close()")
+        self.stepper._no_ema_scope("GraphedTrainStep.run")
         if latents is not None:
             self.lat.copy_(latents)
         if text_emb is not None:
@@ -645,13 +714,19 @@ class ImprovedDiffusionTrainer(TrainerBase):
         uc, oc = self.config.get("unet_optimization", {}) or {}, self.config["optimization"]
         get = lambda k, default=None: uc.get(k, oc.get(k, default))      # safe fallbacks (the reference KeyErrors on beta1/beta2)
         lr, self.max_grad_norm = get("learning_rate"), get("max_grad_norm")
+        # opt-in EMA of the U-Net weights (`training.ema_decay`; absent, None or 0: off, the reference's behaviour)
+        tc = self.config.get("training", {}) or {}
+        self.ema_decay = float(tc["ema_decay"]) if tc.get("ema_decay") else None
         self._betas = (get("beta1", 0.9), get("beta2", 0.999))
         self.stepper = DiffusionStepper(self.unet, self.noise_scheduler, lr=lr, betas=self._betas,
                                         weight_decay=get("weight_decay"), eps=1e-6, max_grad_norm=self.max_grad_norm,
-                                        optimizer_type=get("optimizer", "adamw"), grad_bucket_dtype=self._grad_bucket_dtype)
+                                        optimizer_type=get("optimizer", "adamw"), grad_bucket_dtype=self._grad_bucket_dtype,
+                                        ema_decay=self.ema_decay, ema_warmup=bool(tc.get("ema_warmup", True)))
         self.optimizer = self.stepper.optimizer
         self.scheduler_config = {"type": uc.get("scheduler", oc.get("scheduler", "cosine")), "lr": lr}
         self.logger.info(f"Using U-Net optimization: {get('optimizer', 'adamw')}, lr={lr}, wd={get('weight_decay')}, clip={self.max_grad_norm}")
+        if self.ema_decay:
+            self.logger.info(f"EMA of the U-Net weights: decay={self.ema_decay}, warmup={bool(tc.get('ema_warmup', True))}")
 
     def _make_scheduler(self, optimizer):
         if self.scheduler_config["type"] == "cosine":
@@ -705,11 +780,20 @@ class ImprovedDiffusionTrainer(TrainerBase):
             self.scheduler.step()                                                                    # :413
         return out
 
-    def sample(self, text_emb, num_samples, fast_sampling=True, noise_fn=None):
-        return self.stepper.sample(text_emb, num_samples, fast_sampling, noise_fn, latent_dim=self.config["model"].get("latent_dim", 8))
+    def _ema_ctx(self, use_ema=None):
+        """`ema_weights()` when the EMA is asked for (None: whenever one is kept, unless a scope is already open), else nothing."""
+        if use_ema is None:
+            use_ema = self.stepper.ema_enabled and not self.stepper._ema_scope
+        elif use_ema and not self.stepper.ema_enabled:
+            raise _lib.PsgError("use_ema=True, but this trainer keeps no EMA (training.ema_decay)")
+        return self.stepper.ema_weights() if use_ema else contextlib.nullcontext()
 
-    def ddpm_sample(self, text_emb: torch.Tensor, num_samples: int, fast_sampling: bool = True) -> torch.Tensor:
-        return self.sample(text_emb, num_samples, fast_sampling)
+    def sample(self, text_emb, num_samples, fast_sampling=True, noise_fn=None, use_ema=None):
+        with self._ema_ctx(use_ema):
+            return self.stepper.sample(text_emb, num_samples, fast_sampling, noise_fn, latent_dim=self.config["model"].get("latent_dim", 8))
+
+    def ddpm_sample(self, text_emb: torch.Tensor, num_samples: int, fast_sampling: bool = True, use_ema=None) -> torch.Tensor:
+        return self.sample(text_emb, num_samples, fast_sampling, use_ema=use_ema)
 
     # -- epochs ----------------------------------------------------------------------------------------
     def _encode(self, batch):
@@ -789,6 +873,10 @@ class ImprovedDiffusionTrainer(TrainerBase):
         return {"train_loss": avg}
 
     def validate_epoch(self, epoch: int) -> Dict[str, float]:
+        with self._ema_ctx():                    # (on the averaged weights when an EMA is kept)
+            return self._validate_epoch(epoch)
+
+    def _validate_epoch(self, epoch: int) -> Dict[str, float]:
         dev = self.device
         total, nb = torch.zeros(1, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
         for batch in self.data_loaders["val"]:
@@ -812,6 +900,10 @@ class ImprovedDiffusionTrainer(TrainerBase):
         """Monitoring only (:571-615): needs the (out-of-scope) VAE decoder; skipped when it is absent; rank 0 only."""
         if self.vae_decoder is None or not self.is_main:
             return
+        with self._ema_ctx():                    # (one swap for the whole sheet; ddpm_sample inside sees the open scope)
+            self._generate_samples(epoch, num_samples)
+
+    def _generate_samples(self, epoch: int, num_samples: int):
         batch = next(iter(self.data_loaders["val"]))
         desc = batch["full_description"][:num_samples]
         with torch.no_grad():
@@ -832,6 +924,8 @@ class ImprovedDiffusionTrainer(TrainerBase):
         ckpt = {"epoch": epoch, "global_step": self.global_step, "unet_state_dict": self.unet.state_dict(),
                 "optimizer_state_dict": self.optimizer.state_dict(), "scheduler_state_dict": self.scheduler.state_dict(),
                 "best_val_loss": self.best_val_loss, "config": self.config}
+        if self.stepper.ema_enabled:               # next to the reference's keys, none of which changes
+            ckpt["ema_unet_state_dict"], ckpt["ema_decay"] = self.stepper.ema_state_dict(), self.ema_decay
         if is_best:
             torch.save(ckpt, self.checkpoint_dir / "diffusion_best_model.pth")
             self.logger.info(f"New best model saved at epoch {epoch}")
@@ -841,6 +935,12 @@ class ImprovedDiffusionTrainer(TrainerBase):
         self.current_epoch, self.best_val_loss = ckpt["epoch"], ckpt["best_val_loss"]
         self.unet.load_state_dict(ckpt["unet_state_dict"])
         self.optimizer.load_state_dict(ckpt["optimizer_state_dict"])
+        if self.stepper.ema_enabled:
+            if "ema_unet_state_dict" in ckpt:
+                self.stepper.load_ema_state_dict(ckpt["ema_unet_state_dict"])
+            else:
+                self.stepper.load_ema_state_dict(None)
+                self.logger.info("Checkpoint has no 'ema_unet_state_dict': the EMA starts from the loaded weights")
         if self.scheduler and ckpt["scheduler_state_dict"]:
             self.scheduler.load_state_dict(ckpt["scheduler_state_dict"])
         if not self._fused:
