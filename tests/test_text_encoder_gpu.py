@@ -3,7 +3,8 @@
 psg_layernorm / psg_bert_embed_ln against torch's layer_norm and embedding sums; psg_attn_fwd_varlen against SDPA with
 transformers' finfo.min key mask on every kernel family (and bitwise equal to psg_attn_fwd at full key lengths); the
 whole TextEncoder against the reference module's outputs (tests/golden/text_encoder.npz, cases A and B, every position);
-padding invariance of a text's rows; the trainer building this class with `mi355x.text_dtype`."""
+padding invariance of a text's rows; the trainer building this class with `mi355x.text_dtype`.
+tests/test_ln_kernels_gpu.py holds psg_layernorm and psg_bert_embed_ln to element-wise fp64 bounds on every instantiation."""
 import ctypes as C
 
 import pytest

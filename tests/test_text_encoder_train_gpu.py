@@ -4,7 +4,8 @@ psg_layernorm_bwd against torch's layer_norm differentiated in fp64; the key-len
 (psg_attn_fwd_varlen_train / psg_attn_bwd_varlen) against SDPA with transformers' finfo.min key mask differentiated in fp64,
 on every kernel family, with and without dropout, and bitwise equal to psg_attn_fwd / psg_attn_bwd at full key lengths; the
 whole `TextEncoder(trainable=True)` forward + backward against the reference module's (tests/golden/text_encoder_grad.npz,
-cases N, M, P); train-mode determinism; and one AdamW + clip_grad_norm_ loop as the reference trainers run it."""
+cases N, M, P); train-mode determinism; and one AdamW + clip_grad_norm_ loop as the reference trainers run it.
+tests/test_ln_kernels_gpu.py holds psg_layernorm_bwd to element-wise fp64 bounds on every instantiation, dtype pair and stride."""
 import ctypes as C
 
 import numpy as np
