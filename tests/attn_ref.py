@@ -115,9 +115,10 @@ def stored(t, bf16):
     return (t.to(torch.bfloat16) if bf16 else t.to(torch.float32)).double()
 
 
-def reference(q, k, v, heads, scale, family, bf16, kv_len=None, drop_p=0.0, seed=0, dout=None):
+def reference(q, k, v, heads, scale, family, bf16, kv_len=None, drop_p=0.0, seed=0, dout=None, causal=False):
     """fp64 reference and magnitudes (module docstring).  q, dout: [B, L, heads d]; k, v: [B, S, heads d]; kv_len: a sequence of B
-    ints or None; family: MFMA_BF16 / VALU / MFMA_F32 of the launch (the bf16 MFMA extras).  Returns a namespace with, per
+    ints or None; family: MFMA_BF16 / VALU / MFMA_F32 of the launch (the bf16 MFMA extras); causal: key s takes part for query
+    l iff s <= l (psg_attn_fwd_causal) - the set of live keys then differs from row to row, nothing else changes.  Returns a namespace with, per
     output name n, n (fp64), n_mag (M) and n_extra; o / dq [B, L, heads d], dk / dv [B, S, heads d], lse / delta [B, heads, L].
     o_st and lse_st are o and lse as stored (what the backward launch is given).  Backward outputs only with dout."""
     H = heads
@@ -129,6 +130,8 @@ def reference(q, k, v, heads, scale, family, bf16, kv_len=None, drop_p=0.0, seed
     live = torch.zeros(B, 1, 1, S, dtype=torch.bool, device=q.device)
     for b, e in enumerate(ends):
         live[b, :, :, :e] = True
+    if causal:                                                                                   # [B, 1, L, S]
+        live = live & torch.ones(L, S, dtype=torch.bool, device=q.device).tril()
     keep = torch.from_numpy(keep_mask(seed, B * H, L, S, drop_p)).to(q.device).reshape(B, H, L, S)
     kp = keep.double() / (1.0 - float(np.float32(drop_p)) if drop_p > 0.0 else 1.0)
     RB = BF16_ROUND if family == MFMA_BF16 else 0.0

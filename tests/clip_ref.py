@@ -10,14 +10,20 @@ kernels four times that (`bar`), floored at 1e-6.  The state dicts carry transfo
 The resize is the image processor's float path, F.interpolate(mode='bicubic', align_corners=False, antialias=True), restated as
 one dense matrix per axis (`resize_matrix`); tests/test_clip_ref_cpu.py holds it against F.interpolate in float64.  The three
 keyword arguments `cubic_a`, `causal`, `act` exist so the CPU test can plant a defect and see the comparator reject it.
+
+The last section holds what the element-wise tests of the four kernels need (cases: tests/clip_cases.py): fp64 references with
+the magnitude each bound scales with, the constants of the bounds, and fp32 evaluations in the order the header describes.
 """
 import functools
 import math
+import types
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
 from oracle import hashgen
+from tests.gemm_ref import BF16_ROUND, F32_ROUND, c_acc
 
 SEED = 3207
 MEAN = (0.48145466, 0.4578275, 0.40821073)
@@ -492,3 +498,233 @@ def measure(key_with_prec, threads=4):
         return errors(_compute(tuple(key), PRECISIONS[prec]), tuple(key))
     finally:
         torch.set_num_threads(before)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# element-wise references and bounds of the kernels of csrc/clip.hip (cases: tests/clip_cases.py)
+# ---------------------------------------------------------------------------------------------------------------
+# Every bound below is per element and leaves out no element; `check_bound` is the one comparator.  The causal attention is
+# checked by tests/attn_ref.py (reference(causal=True), check) with the constant C_CAUSAL measured here.
+TWO24 = 2.0 ** -24
+A_FLOOR = 2.0 ** -126
+COS_EPS = 1e-12                      # F.normalize's eps
+
+# Constants of the bounds: measured on the CPU over every case of tests/clip_cases.py, never against a kernel
+# (tests/test_clip_ref_cpu.py re-measures each within 25 %; tests/golden/REPORT_clip_kernels.txt lists them per case class).
+#   C_CAUSAL_TORCH  smallest c (attn_ref.smallest_c, o and lse) at which torch's fp32 masked softmax + matmul passes
+#   C_CAUSAL_SEQ    the same for `causal_seq_f32`: the header's description of psg_attn_fwd_causal evaluated in numpy fp32 -
+#                   one query at a time, keys in ascending order, running maximum, exp(m - m_new) rescale, one division
+#   C_CAUSAL        4 x the larger: the project's margin for "a different but fixed order" (attn_ref.C_ATTN was measured on
+#                   tree-ordered kernels; this one adds up to 128 keys one after the other, rescaling at every new maximum)
+#   C_COS_TORCH     smallest c at which torch's fp32 evaluation of clip_loss.py:60-67 (autograd) passes cosine_ref's bounds
+#   C_COS           4 x that
+C_CAUSAL_TORCH = 0.0385               # f32.d64.L77.hot
+C_CAUSAL_SEQ = 0.0343                 # f32.d64.L77.hot
+C_CAUSAL = 4.0 * max(C_CAUSAL_TORCH, C_CAUSAL_SEQ)
+C_COS_TORCH = 0.0291                  # bf16.B9.D516.neg
+C_COS = 4.0 * C_COS_TORCH
+# psg_clip_prep_fwd: the fp32 roundings on the path of ONE term w_y w_x (a x + b) of an output, counted from the header's
+# description ("centre and weights in fp64, each weight rounded once, the taps combined in fp32, rows first") and the kernel:
+#    2  the two weights, each rounded once to fp32
+#    2  a * x, then + b
+#    1  w_x * (a x + b)
+#    4  the adds of a window row (at most 4 taps; the first, onto 0, is exact and is counted all the same)
+#    1  w_y * row
+#    4  the adds over the window's rows
+#    2  - mean, * inv_std
+#    1  the constant's own rounding: the kernel's mean is fp32(mean) where the reference takes the decimal value
+#       (inv_std is fp32(1 / std) on both sides, as the header states it)
+#   17  each at most 2^-24 of a partial result that the sum of the magnitudes bounds; the fp32 store is exact.
+K_PREP = 17
+
+
+def _f32(x):
+    return float(np.float32(x))
+
+
+def _inv_std():
+    return [float(np.float32(1.0) / np.float32(s)) for s in STD]
+
+
+def check_bound(got, ref, bound, what):
+    """Assert |got - ref| <= bound for every element (a NaN in got fails); returns the worst err / bound."""
+    g = got.detach().to(device=ref.device, dtype=torch.float64)
+    assert g.shape == ref.shape, f"{what}: shape {tuple(g.shape)} vs reference {tuple(ref.shape)}"
+    err = (g - ref).abs()
+    ratio = err / bound
+    ratio = torch.where(torch.isnan(ratio), torch.full_like(ratio, math.inf), ratio)
+    worst = float(ratio.max()) if ratio.numel() else 0.0
+    if not worst <= 1.0:
+        i = int(ratio.argmax())
+        idx = tuple(int(v) for v in torch.unravel_index(torch.tensor(i), ratio.shape))
+        raise AssertionError(f"{what}: {int((ratio > 1.0).sum())} of {ratio.numel()} elements out of bound; worst at {idx}: got "
+                             f"{float(g.reshape(-1)[i]):.9g}, ref {float(ref.reshape(-1)[i]):.9g}, |err| {float(err.reshape(-1)[i]):.3g} > bound "
+                             f"{float(bound.reshape(-1)[i]):.3g} (err/bound {worst:.3g})")
+    return worst
+
+
+def smallest_c(got, ref, mag, r_out):
+    """The smallest c at which |got - ref| <= r_out |ref| + c 2^-24 mag + A_FLOOR holds everywhere."""
+    err = (got.detach().double() - ref).abs()
+    over = (err - r_out * ref.abs() - A_FLOOR).clamp_min(0.0)
+    c = torch.where(over > 0, over / (TWO24 * mag), torch.zeros_like(over))
+    c = torch.where(torch.isnan(c), torch.full_like(c, math.inf), c)
+    return float(c.max())
+
+
+# ---- image processor ----------------------------------------------------------------------------------------------
+def _axis_matrix(Hi, S, cubic_a=-0.5):
+    return resize_matrix(Hi, S, cubic_a) if Hi != S else torch.eye(S, dtype=torch.float64)
+
+
+def rows_of(pixels, P):
+    """[B,3,S,S] -> [B (S/P)^2, 3 P P]."""
+    r = patch_rows(pixels, P)
+    return r.reshape(-1, r.shape[-1])
+
+
+def pixels_of(rows, B, S, P):
+    """The inverse of rows_of: [B (S/P)^2, 3 P P] -> [B,3,S,S]."""
+    G = S // P
+    return F.fold(rows.reshape(B, G * G, 3 * P * P).transpose(1, 2), (S, S), P, stride=P)
+
+
+def prep_fwd_ref(img, S, P, a, b, W=None):
+    """psg_clip_prep_fwd in fp64 on the fp32 image: y = (W (a img + b) W^T - mean) inv_std with W clip_ref.resize_matrix (fp64
+    weights; the identity when Hi == S), CLIP's mean and fp32(1 / std), a and b as the C floats the entry takes - as patch rows
+    [B (S/P)^2, 3 P P] - and the magnitude of the same shape,
+        Mag = (sum |Wy| |Wx| (|a x| + |b|) + mean_c) inv_std_c
+    (the cubic has negative lobes: the sum of the magnitudes is the scale of the roundings, not |ref|).  The bound is
+    K_PREP 2^-24 Mag + A_FLOOR (prep_fwd_bound).  `W` replaces the axis matrix (the CPU test plants defects with it)."""
+    a, b = _f32(a), _f32(b)
+    x = img.detach().double()
+    W = _axis_matrix(x.shape[-1], S) if W is None else W
+    Wy, Wx = W if isinstance(W, tuple) else (W, W)
+    mean = torch.tensor(MEAN, dtype=torch.float64).view(1, 3, 1, 1)
+    inv = torch.tensor(_inv_std(), dtype=torch.float64).view(1, 3, 1, 1)
+    v = torch.einsum("oh,bchw,pw->bcop", Wy, a * x + b, Wx)
+    m = torch.einsum("oh,bchw,pw->bcop", Wy.abs(), (a * x).abs() + abs(b), Wx.abs())
+    return rows_of((v - mean) * inv, P), rows_of((m + mean) * inv, P)
+
+
+def prep_fwd_bound(mag):
+    return K_PREP * TWO24 * mag + A_FLOOR
+
+
+def prep_bwd_ref(dy_rows, B, Hi, S, P, a, W=None):
+    """psg_clip_prep_bwd in fp64: dimg[b,c] = a inv_std_c W^T dy[b,c] W with dy the patch rows read back as [B,3,S,S], and M, the
+    same sum over |dy|, |a| and |W|.  Bound: 4 2^-24 M + A_FLOOR (prep_bwd_bound) - the kernel forms the sum in fp64 and rounds
+    once, with its two constant factors, exactly as psg_image_prep_bwd, which tests/test_imaging_gpu.py holds to this bound."""
+    a = _f32(a)
+    g = pixels_of(dy_rows.detach().double(), B, S, P)
+    W = _axis_matrix(Hi, S) if W is None else W
+    inv = torch.tensor(_inv_std(), dtype=torch.float64).view(1, 3, 1, 1)
+    ref = a * inv * torch.einsum("oh,bcop,pw->bchw", W, g, W)
+    M = abs(a) * inv * torch.einsum("oh,bcop,pw->bchw", W.abs(), g.abs(), W.abs())
+    return ref, M
+
+
+def prep_bwd_bound(M):
+    return 4.0 * TWO24 * M + A_FLOOR
+
+
+def prep_fwd_f32(img, S, P, a, b):
+    """The header's description of psg_clip_prep_fwd evaluated in numpy fp32: weights from fp64 rounded once, v = a x + b, the
+    taps of each window row first, then the rows, - mean, * inv_std.  Patch rows, fp32."""
+    x = img.detach().numpy().astype(np.float32)
+    B, _, Hi, _ = x.shape
+    a, b = np.float32(a), np.float32(b)
+    mean = np.array(MEAN, dtype=np.float32)
+    inv = np.float32(1.0) / np.array(STD, dtype=np.float32)
+    W = _axis_matrix(Hi, S).numpy()
+    out = np.zeros((B, 3, S, S), dtype=np.float32)
+    v = a * x + b
+    taps = [np.nonzero(W[o])[0] for o in range(S)]
+    for oy in range(S):
+        for ox in range(S):
+            acc = np.zeros((B, 3), dtype=np.float32)
+            for iy in taps[oy]:
+                row = np.zeros((B, 3), dtype=np.float32)
+                for ix in taps[ox]:
+                    row = row + np.float32(W[ox, ix]) * v[:, :, iy, ix]
+                acc = acc + np.float32(W[oy, iy]) * row
+            out[:, :, oy, ox] = (acc - mean) * inv
+    return rows_of(torch.from_numpy(out), P)
+
+
+# ---- cosine loss ------------------------------------------------------------------------------------------------------
+def cosine_ref(u, v):
+    """clip_loss.py:60-67 with F.normalize's clamp in fp64, its gradient, and the magnitudes of their bounds
+        |got - ref| <= r_out |ref| + C_COS 2^-24 M + A_FLOOR.
+    Per row r, nu = ||u_r||, nu' = max(nu, eps) (nv, nv' alike), cos_r = u_r . v_r / (nu' nv'), out = -mean_r cos_r,
+        du[r, c] = -(v_c / (nu' nv') - [nu > eps] cos_r u_c / nu^2) / B.
+    With sq(n) = gemm_ref.c_acc(n) / 2^-24 the factor of an fp32 reduction over n terms, in units of 2^-24:
+      e_r    = sum_c |u_c v_c| / (nu' nv')                 the dot product's error scale
+      Ecos_r = sq(D) (e_r + 2 |cos_r|) + 4                 u . v, the two norms (a square root halves a relative error: sq(D) / 2
+                                                           each, taken whole), the product, the division, the clamp
+      out    M = (1/B) sum_r Ecos_r + sq(B) (1/B) sum_r |cos_r|          the cosines, then their sum over the rows
+      du     M = (1/B) ((2 sq(D) + 4) |v_c| / (nu' nv') + (Ecos_r + |cos_r| (2 sq(D) + 4)) |u_c| / nu^2)
+             the first term's factor 1 / (nu' nv'), the second's cos_r / nu^2 (cos_r's own error plus the squared norm's), the
+             two products and the add; the second term is absent where nu <= eps.
+    Returns a namespace: loss, loss_mag (0-d), du, du_mag [B, D], cos [B], nu [B]."""
+    u, v = u.detach().double(), v.detach().double()
+    B, D = u.shape
+    sqD, sqB = c_acc(D) / TWO24, c_acc(B) / TWO24
+    nu, nv = u.norm(dim=-1, keepdim=True), v.norm(dim=-1, keepdim=True)
+    den = nu.clamp_min(COS_EPS) * nv.clamp_min(COS_EPS)
+    cos = (u * v).sum(-1, keepdim=True) / den
+    gate = nu > COS_EPS
+    nu2 = torch.where(gate, nu * nu, torch.ones_like(nu))
+    e = (u * v).abs().sum(-1, keepdim=True) / den
+    Ecos = sqD * (e + 2.0 * cos.abs()) + 4.0
+    r = types.SimpleNamespace(cos=cos.squeeze(-1), nu=nu.squeeze(-1))
+    r.loss = -cos.mean()
+    r.loss_mag = Ecos.mean() + sqB * cos.abs().mean()
+    r.du = -(v / den - torch.where(gate, cos * u / nu2, torch.zeros_like(u))) / B
+    r.du_mag = ((2.0 * sqD + 4.0) * v.abs() / den + torch.where(gate, (Ecos + cos.abs() * (2.0 * sqD + 4.0)) * u.abs() / nu2, torch.zeros_like(u))) / B
+    return r
+
+
+def cosine_bound(ref, mag, out_dtype, c=None):
+    c = C_COS if c is None else c
+    return (BF16_ROUND if out_dtype == torch.bfloat16 else F32_ROUND) * ref.abs() + c * TWO24 * mag + A_FLOOR
+
+
+# ---- causal attention -------------------------------------------------------------------------------------------------
+def causal_seq_f32(q, k, v, heads, scale):
+    """include/psg_hip.h's description of psg_attn_fwd_causal evaluated in numpy fp32: one query row at a time, its keys
+    s = 0..l in ascending order with a running maximum m - p = exp(s - m_new), sum and the output row rescaled by exp(m - m_new)
+    at every key - one division at the end, lse = m + log(sum).  q, k, v: [B, L, heads d] fp32.  Returns (o [B, L, heads d],
+    lse [B, heads, L]) as fp32 tensors."""
+    B, L, E = q.shape
+    d = E // heads
+    Q, K, V = (t.detach().reshape(B, L, heads, d).permute(0, 2, 1, 3).contiguous().numpy().astype(np.float32) for t in (q, k, v))
+    s = np.zeros((B, heads, L, L), dtype=np.float32)
+    for c in range(d):
+        s = s + Q[:, :, :, None, c] * K[:, :, None, :, c]
+    s = s * np.float32(scale)
+    m = np.full((B, heads, L), -np.inf, dtype=np.float32)
+    tot = np.zeros((B, heads, L), dtype=np.float32)
+    acc = np.zeros((B, heads, L, d), dtype=np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for j in range(L):                                   # key j, for the queries l >= j
+            sj = s[:, :, j:, j]
+            mn = np.maximum(m[:, :, j:], sj)
+            corr = np.exp(m[:, :, j:] - mn)
+            p = np.exp(sj - mn)
+            tot[:, :, j:] = tot[:, :, j:] * corr + p
+            acc[:, :, j:] = acc[:, :, j:] * corr[..., None] + V[:, :, j, None, :] * p[..., None]
+            m[:, :, j:] = mn
+    o = acc * (np.float32(1.0) / tot)[..., None]
+    lse = m + np.log(tot)
+    return torch.from_numpy(o).permute(0, 2, 1, 3).reshape(B, L, E), torch.from_numpy(lse)
+
+
+def causal_torch_f32(q, k, v, heads, scale):
+    """torch's own fp32 masked softmax and matmul: (o, lse)."""
+    B, L, E = q.shape
+    d = E // heads
+    Q, K, V = (t.detach().float().reshape(B, L, heads, d).permute(0, 2, 1, 3) for t in (q, k, v))
+    s = (Q @ K.transpose(2, 3)) * torch.tensor(scale, dtype=torch.float32)
+    s = s.masked_fill(torch.ones(L, L, dtype=torch.bool).triu(1), -math.inf)
+    return (torch.softmax(s, -1) @ V).permute(0, 2, 1, 3).reshape(B, L, E), torch.logsumexp(s, -1)

@@ -32,7 +32,7 @@ NF = len(ROUTE_FIELDS)
 TILES = ((128, 128), (128, 64), (64, 64), (128, 160), (64, 160))           # psg_conv_set_tile candidates 0..4
 DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16}
 DTYPE_CODE = {"f32": 0, "bf16": 1}
-ACT_CODE = {"none": 0, "silu": 1, "gelu": 2, "relu": 3, "tanh": 4}
+ACT_CODE = {"none": 0, "silu": 1, "gelu": 2, "relu": 3, "tanh": 4, "quick_gelu": 5}
 SAVE_DACT, DACT_MUL, GENERIC = 1, 2, 4
 NAN = float("nan")
 GUARD = 64                                                                  # guard elements before and after every buffer
@@ -61,6 +61,15 @@ RECIPES = {
     "dmul": dict(dact="mul", alpha=1.3),
     "all": dict(bias=True, rowadd=True, residual=True, act="silu", alpha=0.7, drop_p=0.05, preact=True),
 }
+# quick-GELU (both CLIP towers' MLP) in each form an epilogue evaluates an activation in: the value (act_f), value and saved
+# derivative (act_both), the value under dropout, the derivative of a saved pre-activation (act_grad).  Listed apart: the cases
+# of _build() take the fifteen recipes above by position, which must not move.
+QGELU_RECIPES = {
+    "qgelu": dict(bias=True, act="quick_gelu"),
+    "qgelu_save": dict(bias=True, act="quick_gelu", preact=True, save_dact=True),
+    "qgelu_drop_pre": dict(act="quick_gelu", drop_p=0.05, preact=True),
+    "dactu_qgelu": dict(dact="u", act="quick_gelu"),
+}
 # recipes whose bf16 staged epilogue has a per-kind copy (EK_*); the rest run EK_GENERIC
 EK_OF = {"plain": "PLAIN", "res": "PLAIN", "drop": "DROP", "drop_res": "DROP", "gelu_pre": "GELU", "gelu_drop_save": "GELU_DROP",
          "dmul": "DMUL"}
@@ -71,7 +80,7 @@ def _mk(name, recipe=None, **kw):
     c["name"] = name
     c["recipe"] = recipe
     if recipe:
-        c.update(RECIPES[recipe])
+        c.update(RECIPES[recipe] if recipe in RECIPES else QGELU_RECIPES[recipe])
     c.update(kw)
     if c["pad"] is None:
         c["pad"] = c["ks"] // 2
@@ -271,6 +280,18 @@ def _build():
     add("alias.f32", None, dtype="f32", B=130, Cin=64, Cout=72, bias=True, residual=True, alias=True, act="silu")
     add("alias.cls", None, B=21, H=3, W=5, Cin=64, Cout=72, ks=3, tapcls=2, residual=True, alias=True, tile=2)
     add("alias.mode3", None, B=3, H=5, W=8, Cin=64, Cout=24, ks=3, stride=2, tr=1, residual=True, alias=True)
+
+    # ---- (H) quick-GELU on every epilogue path (appended: the cases above keep their places) ---------------------------------
+    for r in QGELU_RECIPES:
+        add(f"epi.staged.{r}", r, B=3, H=3, W=5, Cin=64, Cout=72, ks=3, tapcls=0)
+        add(f"epi.direct.{r}", r, B=3, H=3, W=5, Cin=64, Cout=12, ks=3, tapcls=0)
+        add(f"epi.f32.{r}", r, dtype="f32", B=3, H=3, W=5, Cin=32, Cout=12, ks=3)
+    add("split.bf16.qgelu_save", "qgelu_save", ks=3, tapcls=0, ws="ok", **shapes[0])               # the finishing kernel
+    add("split.f32.dactu_qgelu", "dactu_qgelu", dtype="f32", ks=3, tr=1, ws="ok", **f32shapes[0])
+    add("g.bf16.3x3s2.dgrad.7x7.dactu_qgelu", "dactu_qgelu", B=3, H=7, W=7, Cin=64, Cout=24, ks=3, stride=2, tr=1)   # parity classes
+    # the CLIP MLP's shape class: whole 128x128 tiles of a pointwise launch, more of them than resident slots, nothing pinned -
+    # the stored route says which kernel takes it (the persistent pointwise kernel has no quick-GELU copy)
+    add("pw.qgelu.plan", "qgelu", B=768, Cin=192, Cout=640, cus=8)
     names = [c["name"] for c in cs]
     assert len(set(names)) == len(names), "duplicate case names"
     return cs
@@ -442,14 +463,15 @@ def operands(c):
     the weights and the bias are zero-mean, so that the pre-activation u straddles zero at any K and on border pixels alike
     (standard deviation ~0.5: about half the elements on either side of ReLU's kink, |u| mostly below 1.5 for tanh) - a ReLU
     that clamps nothing, a saved derivative of constant 1 or a saturated tanh would otherwise pass
-    (tests/test_conv_ref_cpu.py asserts the fractions)."""
+    (tests/test_conv_ref_cpu.py asserts the fractions).  Nor under quick-GELU: for |u| of a few tenths to 2 it lies visibly
+    off GELU-erf and off SiLU, further out all three are u or 0 (tests/test_conv_ref_cpu.py swaps them and must see it)."""
     g = geom(c)
     dt = DTYPES[c["dtype"]]
     t = "cv." + c["name"]
     N, M = c["Cout"], g["M"]
     o = dict(x=_q(0.3 + 0.8 * h((c["B"], g["Hi"], g["Wi"], c["Cin"]), t + ".x"), dt))
     wshape = (c["Cin"], N, c["ks"], c["ks"]) if c["tr"] else (N, c["Cin"], c["ks"], c["ks"])
-    centred = c["dact"] is None and c["act"] in ("relu", "tanh")
+    centred = c["dact"] is None and c["act"] in ("relu", "tanh", "quick_gelu")
     o["wl"] = _q(((0.0 if centred else 0.25) + h(wshape, t + ".w")) * (1.5 / math.sqrt(g["K"])), dt)
     o["bias"] = (0.0 if centred else 0.2) + 0.3 * h((N,), t + ".b") if c["bias"] else None
     o["rowadd"] = _q(0.6 * h((c["B"], N), t + ".ra") - 0.1, dt) if c["rowadd"] else None

@@ -21,7 +21,10 @@ BF16_ROUND = 2.0 ** -8        # |round(v) - v| <= 2^-8 |v| for bf16 round-to-nea
 F32_ROUND = 4 * 2.0 ** -24    # fp32 outputs: the final rounding plus the epilogue's own fp32 operations
 A_FLOOR = 2.0 ** -126         # smallest normal fp32 / bf16: values below it carry no relative precision
 # largest |d act / du| over the reals: what an accumulator error can become after the activation
-ACT_SLOPE = {"none": 1.0, "silu": 1.0998, "gelu": 1.1289, "relu": 1.0, "tanh": 1.0}
+# (quick-GELU x sigmoid(c x), c = 1.702, is SiLU on a scaled argument: d/dx = silu'(c x), the same largest slope; the second
+# derivative is c silu''(c x), c times SiLU's curvature.)
+QUICK_GELU_C = 1.702
+ACT_SLOPE = {"none": 1.0, "silu": 1.0998, "gelu": 1.1289, "relu": 1.0, "tanh": 1.0, "quick_gelu": 1.0998}
 # The kernels' activations are not the exact functions: bf16 launches use __expf / rcp SiLU and an erf by Abramowitz-Stegun
 # 7.1.26 (|erf error| <= 1.5e-7).  Relative to the activation's value both stay below 2^-20, except GELU near its zero at
 # u = 0 where the erf error enters as 0.5 |u| 1.5e-7; the bound adds ACT_APPROX * |u| for that.
@@ -29,10 +32,13 @@ ACT_SLOPE = {"none": 1.0, "silu": 1.0998, "gelu": 1.1289, "relu": 1.0, "tanh": 1
 # table lists 2): 5 * 2^-24 < 2^-21 relative to |tanh u| <= |u|; its derivative is 1 - t * t of that value (act_grad /
 # act_both in psg_common.h), an absolute 2 |t| |dt| + 2^-24 <= 11 * 2^-24 < 2^-20.  tests/test_conv_ref_cpu.py evaluates
 # the psg_common.h formulas in fp32 against fp64 and checks both against these entries.
-ACT_APPROX = {"none": 0.0, "silu": 2.0 ** -20, "gelu": 2.0 ** -20, "relu": 0.0, "tanh": 2.0 ** -21}
+# quick-GELU (psg_common.h quick_gelu_f / quick_gelu_grad: the exact-fp32 sigmoid of SiLU and one more fp32 product 1.702 x,
+# whose rounding moves s by at most s (1 - s) |1.702 x| 2^-24) keeps SiLU's 2^-20 in every form
+# (tests/test_row_ref_cpu.py::test_quick_gelu_act_approx_holds_for_the_fp32_formula and tests/test_conv_ref_cpu.py).
+ACT_APPROX = {"none": 0.0, "silu": 2.0 ** -20, "gelu": 2.0 ** -20, "relu": 0.0, "tanh": 2.0 ** -21, "quick_gelu": 2.0 ** -20}
 # largest |d^2 act / du^2| over the reals: what an accumulator error can become in a saved derivative act'(u).  (ReLU's
 # derivative is a step: see saved_dact.)
-ACT_CURV = {"none": 0.0, "silu": 0.5, "gelu": 0.7979, "relu": 0.0, "tanh": 0.7699}
+ACT_CURV = {"none": 0.0, "silu": 0.5, "gelu": 0.7979, "relu": 0.0, "tanh": 0.7699, "quick_gelu": QUICK_GELU_C * 0.5}
 # fp32 launches were not part of the measurement behind c_acc(): tests/test_conv_ref_cpu.py holds torch's own fp32 conv2d /
 # conv_transpose2d / linear of every fp32 case of tests/conv_cases.py against check()'s bound, requires it to lie inside
 # (else the bound would be widened for fp32 alone, by four times the factor torch needs) and writes the worst ratio it
@@ -195,7 +201,7 @@ def _f64(t):
 
 
 def act(u, kind):
-    """The activation in fp64: none, SiLU, GELU in its erf form (nn.GELU()), ReLU or tanh."""
+    """The activation in fp64: none, SiLU, GELU in its erf form (nn.GELU()), ReLU, tanh or quick-GELU x sigmoid(1.702 x)."""
     if kind == "none":
         return u
     if kind == "relu":
@@ -206,6 +212,8 @@ def act(u, kind):
         return u * torch.sigmoid(u)
     if kind == "gelu":
         return 0.5 * u * (1.0 + torch.erf(u * (1.0 / math.sqrt(2.0))))
+    if kind == "quick_gelu":
+        return u * torch.sigmoid(QUICK_GELU_C * u)
     raise ValueError(kind)
 
 
@@ -222,6 +230,9 @@ def act_grad(u, kind):
         return s * (1.0 + u * (1.0 - s))
     if kind == "gelu":
         return 0.5 * (1.0 + torch.erf(u * (1.0 / math.sqrt(2.0)))) + u * torch.exp(-0.5 * u * u) / math.sqrt(2.0 * math.pi)
+    if kind == "quick_gelu":
+        s = torch.sigmoid(QUICK_GELU_C * u)
+        return s * (1.0 + QUICK_GELU_C * u * (1.0 - s))
     raise ValueError(kind)
 
 

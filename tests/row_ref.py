@@ -199,19 +199,12 @@ def prep_weight(w, dtype):
 
 # -------------------------------------------------------------------------------------------- epilogue_bwd, dropout_apply
 ACTS = {"none": 0, "silu": 1, "gelu": 2, "relu": 3, "tanh": 4, "quick_gelu": 5}       # enum psg_act
-QUICK_GELU_C = 1.702
-# quick-GELU x sigmoid(1.702 x) is SiLU's formula on a scaled argument (psg_common.h quick_gelu_grad: the exact-fp32 sigmoid,
-# one more fp32 product 1.702 x whose rounding moves s by at most s (1 - s) |1.702 x| 2^-24): the SiLU entry, 2^-20, holds for
-# it in dact_u's form (4 ACT_APPROX relative + ACT_APPROX absolute); tests/test_row_ref_cpu.py evaluates the fp32 formula
-# against fp64 over |u| <= 9 as tests/test_conv_ref_cpu.py does for the other entries.
-ACT_APPROX_ROW = dict(ACT_APPROX, quick_gelu=2.0 ** -20)
-
-
-def act_grad(u, kind):
-    if kind == "quick_gelu":
-        s = torch.sigmoid(QUICK_GELU_C * u)
-        return s * (1.0 + QUICK_GELU_C * u * (1.0 - s))
-    return gemm_ref.act_grad(u, kind)
+QUICK_GELU_C = gemm_ref.QUICK_GELU_C
+# quick-GELU lives in tests/gemm_ref.py with the other activations (formula, derivative and its 2^-20 ACT_APPROX entry, which
+# holds in dact_u's form - 4 ACT_APPROX relative + ACT_APPROX absolute; tests/test_row_ref_cpu.py evaluates the fp32 formula
+# against fp64 over |u| <= 9); these names stay for the row tests.
+ACT_APPROX_ROW = ACT_APPROX
+act_grad = gemm_ref.act_grad
 
 
 def p32(p):

@@ -1,6 +1,14 @@
 """-m gpu: the CLIP kernels (csrc/clip.hip) and the quick-GELU epilogue against the float64 restatement of tests/clip_ref.py:
 psg_clip_prep_fwd / _bwd, psg_attn_fwd_causal, psg_cosine_loss, ops.linear(act=ACT_QUICK_GELU).  Every bound is `clip_ref.bar`:
-four times the error of torch on the CPU in the same precision on the same case, floored at 1e-6."""
+four times the error of torch on the CPU in the same precision on the same case, floored at 1e-6.
+
+Below them the same kernels through the C ABI on the cases of tests/clip_cases.py, element by element: guarded NaN-filled
+buffers on the least alignment and with the row strides the header allows, every element within the derived bound of the fp64
+reference of the operands the kernel read (tests/clip_ref.py, tests/attn_ref.py), guards and unwritten columns untouched,
+identical bits from identical launches and with or without the optional output.  Every comparison prints
+`RATIO <what> <err / bound>` before it asserts (0 = a bit comparison).  A device error ends the run."""
+import os
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -139,3 +147,173 @@ def test_quick_gelu_through_linear(ops, prec):
     y = ops.linear(xs, ws, bs, act=ops.ACT_QUICK_GELU)
     (y.float() * dy.to(DEV)).sum().backward()
     _check(dict(fwd=y, dx=xs.grad, dw=ws.grad, db=bs.grad), ("qgelu",), prec)
+
+
+# ---- element by element, through the C ABI (tests/clip_cases.py) -----------------------------------------------------------
+from tests import clip_cases as KC  # noqa: E402
+
+REPORT = os.environ.get("PSG_CLIP_REPORT")           # optional: append each case's worst err / bound to this file
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from pokemon_sprite_generator_amd import _lib
+    return _lib.init(0)
+
+
+def _ratio(what, ratios):
+    line = f"{what} " + " ".join(f"{k}={v:.3g}" for k, v in ratios.items())
+    print("RATIO " + line)
+    if REPORT:
+        with open(REPORT, "a") as f:
+            f.write("gpu " + line + "\n")
+
+
+def _run(rc, what):
+    from pokemon_sprite_generator_amd import _lib
+    _lib.check(rc, what)
+    try:
+        torch.cuda.synchronize()
+    except RuntimeError as e:                                          # a device error: nothing more runs on this GPU
+        pytest.exit(f"{what}: {e}", returncode=3)
+
+
+def _bits(t):
+    return t.view(torch.int16 if t.element_size() == 2 else torch.int32)
+
+
+def _least_aligned(pair, what):
+    """The view starts on a 4-element boundary and not on the next larger one (bf16: 8 bytes, not 16; fp32: 16, not 32)."""
+    n = 4 * pair[1].element_size()
+    assert pair[1].data_ptr() % (2 * n) == n, f"{what}: base {pair[1].data_ptr():#x}"
+
+
+@pytest.mark.parametrize("name", [c["name"] for c in KC.CAUSAL])
+def test_causal_elementwise(lib, name):
+    from pokemon_sprite_generator_amd import _lib
+    c = KC.CAUSAL_BY_NAME[name]
+    dt, code = KC.DTYPES[c["dtype"]], KC.DTYPE_CODE[c["dtype"]]
+    B, L, H, d = c["B"], c["L"], c["heads"], c["d"]
+    E, ld = H * d, KC.causal_ld(c)
+    ops = KC.causal_operands(name)
+    src = {n: KC.filled(t.reshape(B * L, E), ld[n], dt, DEV) for n, t in zip("qkv", ops)}
+    outs = []
+    for with_lse in (True, False, True):
+        ob = KC.alloc(B * L, ld["o"], dt, DEV)
+        lb = KC.alloc(1, B * H * L, torch.float32, DEV) if with_lse else None
+        for n, pair in list(src.items()) + [("o", ob)]:
+            _least_aligned(pair, f"{name} {n}")
+        _run(lib.psg_attn_fwd_causal(src["q"][1].data_ptr(), ld["q"], src["k"][1].data_ptr(), ld["k"], src["v"][1].data_ptr(), ld["v"],
+                                     ob[1].data_ptr(), ld["o"], lb[1].data_ptr() if lb else None, B, H, L, L, d, c["scale"], 0.0, 0, code,
+                                     _lib.stream_ptr()), "psg_attn_fwd_causal " + name)
+        KC.guards_ok(ob, E, f"{name} o")
+        if lb:
+            KC.guards_ok(lb, B * H * L, f"{name} lse")
+        outs.append((ob, lb))
+    (ob, lb), (ob_nolse, _), (ob2, lb2) = outs
+    o = ob[1][:, :E].reshape(B, L, E)
+    _ratio(f"causal {name}", KC.causal_check(o, lb[1].view(B, H, L), name, name))
+    assert torch.equal(_bits(ob[0]), _bits(ob_nolse[0])), f"{name}: o depends on whether lse is asked for"
+    assert torch.equal(_bits(ob[0]), _bits(ob2[0])) and torch.equal(_bits(lb[0]), _bits(lb2[0])), f"{name}: two identical launches differ"
+    assert torch.equal(_bits(o[:, 0].contiguous()), _bits(ops[2][:, 0].to(DEV, dt).contiguous())), f"{name}: row 0 is not v[0] to the bit"
+
+
+def _prep_fwd(lib, img_pair, B, Hi, S, P, a, b, extra, dt, what):
+    from pokemon_sprite_generator_amd import _lib
+    G = S // P
+    yb = KC.alloc(B * G * G, 3 * P * P + extra, dt, DEV)
+    _run(lib.psg_clip_prep_fwd(img_pair[1].data_ptr(), yb[1].data_ptr(), 3 * P * P + extra, B, Hi, Hi, S, P, a, b, _lib.dtype_code(dt),
+                               _lib.stream_ptr()), what)
+    KC.guards_ok(yb, 3 * P * P, what)
+    return yb
+
+
+def _prep_bwd(lib, dy_pair, B, Hi, S, P, a, dt, what):
+    from pokemon_sprite_generator_amd import _lib
+    gb = KC.alloc(1, B * 3 * Hi * Hi, torch.float32, DEV)               # NaN-poisoned: every element must be written
+    _run(lib.psg_clip_prep_bwd(dy_pair[1].data_ptr(), dy_pair[1].shape[1], gb[1].data_ptr(), B, Hi, Hi, S, P, a, _lib.dtype_code(dt),
+                               _lib.stream_ptr()), what)
+    KC.guards_ok(gb, B * 3 * Hi * Hi, what)
+    return gb
+
+
+@pytest.mark.parametrize("dn", list(KC.DTYPES))
+@pytest.mark.parametrize("B", KC.PREP_BATCHES)
+@pytest.mark.parametrize("Hi,S,P", KC.PREP_SHAPES)
+def test_prep_elementwise(lib, Hi, S, P, B, dn):
+    """Every (a, b) and row stride of the table.  fp32: each element within K_PREP 2^-24 Mag of the fp64 reference.  bf16: the
+    kernel stores (bf16_t)v, round to nearest even (psg_common.h Elem<bf16_t>::st), so the launch must equal the fp32 launch's
+    result converted with .to(torch.bfloat16) bit for bit.  The backward reads the bf16-representable dy exactly in both."""
+    dt = KC.DTYPES[dn]
+    img, dy = KC.prep_operands(Hi, S, P, B)
+    imgb = KC.filled(img.reshape(1, -1), img.numel(), torch.float32, DEV)
+    worst = {"fwd": 0.0, "bwd": 0.0}
+    for a, b in KC.PREP_AB:
+        ref, mag = R.prep_fwd_ref(img, S, P, a, b)
+        g, M = R.prep_bwd_ref(dy, B, Hi, S, P, a)
+        for extra in KC.PREP_LD_EXTRA:
+            what = f"prep {Hi}->{S} P{P} B{B} {dn} a{a} b{b} ld+{extra}"
+            y32 = _prep_fwd(lib, imgb, B, Hi, S, P, a, b, extra, torch.float32, what + " fwd")
+            if dn == "f32":
+                worst["fwd"] = max(worst["fwd"], R.check_bound(y32[1][:, :3 * P * P], ref, R.prep_fwd_bound(mag), what + " fwd"))
+                again = _prep_fwd(lib, imgb, B, Hi, S, P, a, b, extra, torch.float32, what + " fwd")
+                assert torch.equal(_bits(y32[0]), _bits(again[0])), f"{what}: two identical launches differ"
+            else:
+                y16 = _prep_fwd(lib, imgb, B, Hi, S, P, a, b, extra, dt, what + " fwd")
+                assert torch.equal(_bits(y16[1][:, :3 * P * P].contiguous()), _bits(y32[1][:, :3 * P * P].to(dt).contiguous())), \
+                    f"{what}: the bf16 launch is not the fp32 launch rounded to nearest even"
+            dyb = KC.filled(dy, 3 * P * P + extra, dt, DEV)
+            gb = _prep_bwd(lib, dyb, B, Hi, S, P, a, dt, what + " bwd")
+            worst["bwd"] = max(worst["bwd"], R.check_bound(gb[1].view(B, 3, Hi, Hi), g, R.prep_bwd_bound(M), what + " bwd"))
+            assert torch.equal(_bits(gb[0]), _bits(_prep_bwd(lib, dyb, B, Hi, S, P, a, dt, what + " bwd")[0])), f"{what}: two identical launches differ"
+    _ratio(f"prep {Hi}->{S} P{P} B{B} {dn}", worst)
+
+
+def test_prep_same_size_through_the_abi_with_a_stride(lib):
+    """test_prep_same_size_does_no_resampling on strided rows: Hi == S, every output ((a x + b) - mean) * inv_std of ONE pixel and
+    every gradient one dy times inv_std times a, to the bit."""
+    B, S, P, extra = 3, 16, 4, 8
+    img, dy = KC.prep_operands(S, S, P, B)
+    imgb = KC.filled(img.reshape(1, -1), img.numel(), torch.float32, DEV)
+    mean = torch.tensor(R.MEAN, device=DEV).view(1, 3, 1, 1)
+    inv = (1.0 / torch.tensor(R.STD, device=DEV)).view(1, 3, 1, 1)
+    x = img.to(DEV)
+    for a, b in KC.PREP_AB:
+        yb = _prep_fwd(lib, imgb, B, S, S, P, a, b, extra, torch.float32, "prep same-size fwd")
+        want = R.rows_of(((a * x + b) - mean) * inv, P)
+        assert torch.equal(yb[1][:, :3 * P * P], want), (a, b)
+        dyb = KC.filled(dy, 3 * P * P + extra, torch.float32, DEV)
+        gb = _prep_bwd(lib, dyb, B, S, S, P, a, torch.float32, "prep same-size bwd")
+        assert torch.equal(gb[1].view(B, 3, S, S), R.pixels_of(dy.to(DEV), B, S, P) * inv * a), (a, b)
+    _ratio("prep same-size strided", {"fwd": 0.0, "bwd": 0.0})
+
+
+@pytest.mark.parametrize("dn", list(KC.DTYPES))
+@pytest.mark.parametrize("D", KC.COS_D)
+@pytest.mark.parametrize("B", KC.COS_B)
+def test_cosine_elementwise(lib, B, D, dn):
+    from pokemon_sprite_generator_amd import _lib
+    dt, code, ld = KC.DTYPES[dn], KC.DTYPE_CODE[dn], KC.cosine_ld(D)
+    worst = {}
+    for kind in KC.COS_KINDS if B > 1 else ("none",):
+        what = f"cosine B{B} D{D} {dn} {kind}"
+        u, v = KC.cosine_operands(B, D, kind, dn)
+        ub, vb = KC.filled(u, ld["u"], dt, DEV), KC.filled(v, ld["v"], dt, DEV)
+        outs = []
+        for with_du in (True, False, True):
+            db = KC.alloc(B, ld["du"], dt, DEV) if with_du else None
+            sb = KC.alloc(1, 1, torch.float32, DEV)
+            for n, pair in (("u", ub), ("v", vb)) + ((("du", db),) if db else ()):
+                _least_aligned(pair, f"{what} {n}")
+            _run(lib.psg_cosine_loss(ub[1].data_ptr(), ld["u"], vb[1].data_ptr(), ld["v"], db[1].data_ptr() if db else None, ld["du"] if db else 0,
+                                     sb[1].data_ptr(), B, D, code, _lib.stream_ptr()), "psg_cosine_loss " + what)
+            KC.guards_ok(sb, 1, what + " out")
+            if db:
+                KC.guards_ok(db, D, what + " du")
+            outs.append((sb, db))
+        (sb, db), (sb_nodu, _), (sb2, db2) = outs
+        for k, w in KC.cosine_check(sb[1].reshape(()), db[1][:, :D], B, D, kind, dn, what).items():
+            worst[k] = max(worst.get(k, 0.0), w)
+        assert torch.equal(_bits(sb[0]), _bits(sb_nodu[0])), f"{what}: the loss depends on whether du is asked for"
+        assert torch.equal(_bits(sb[0]), _bits(sb2[0])) and torch.equal(_bits(db[0]), _bits(db2[0])), f"{what}: two identical launches differ"
+    _ratio(f"cosine B{B} D{D} {dn}", worst)

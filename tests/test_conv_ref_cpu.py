@@ -290,10 +290,10 @@ def test_extended_conv_references_equal_autograd(ks, stride, pad, H, W):
     assert torch.allclose(dx, x.grad, rtol=1e-12, atol=1e-12) and bool((Sd >= dx.abs() - 1e-12).all())
 
 
-@pytest.mark.parametrize("kind", ["relu", "tanh", "silu", "gelu"])
+@pytest.mark.parametrize("kind", ["relu", "tanh", "silu", "gelu", "quick_gelu"])
 def test_activation_references_equal_autograd(kind):
     u = torch.linspace(-6, 6, 4001, dtype=torch.float64, requires_grad=True)
-    fn = {"relu": torch.relu, "tanh": torch.tanh, "silu": F.silu, "gelu": F.gelu}[kind]
+    fn = {"relu": torch.relu, "tanh": torch.tanh, "silu": F.silu, "gelu": F.gelu, "quick_gelu": lambda t: t * torch.sigmoid(1.702 * t)}[kind]
     y = fn(u)
     y.sum().backward()
     assert torch.allclose(R.act(u.detach(), kind), y.detach(), rtol=1e-13, atol=1e-15)
@@ -324,6 +324,45 @@ def test_new_act_approx_entries_hold_for_the_fp32_formulas():
     worst_r = float(((d32 - d).abs() / (4.0 * R.ACT_APPROX["tanh"] * d.abs() + R.ACT_APPROX["tanh"])).max())
     _report(f"act_approx tanh value {worst_v:.3f} derivative {worst_d:.3f} relative-form {worst_r:.3f} (fp32 torch vs fp64, ratio to the bound)")
     assert worst_v <= 0.5 and worst_d <= 0.5 and worst_r <= 0.5, (worst_v, worst_d, worst_r)
+    # quick-GELU, psg_common.h quick_gelu_f / quick_gelu_grad / act_both: s = 1 / (1 + exp(-(1.702f x))), y = x s,
+    # dy = s (1 + 1.702f x (1 - s)), every operation in fp32
+    c32 = torch.tensor(1.702)
+    s32 = 1.0 / (1.0 + torch.exp(-(c32 * u32)))
+    y32, d32 = (u32 * s32).double(), (s32 * (1.0 + c32 * u32 * (1.0 - s32))).double()
+    y, d, A = R.act(u, "quick_gelu"), R.act_grad(u, "quick_gelu"), R.ACT_APPROX["quick_gelu"]
+    worst_v = float(((y32 - y).abs() / (A * (y.abs() + u.abs()) + R.A_FLOOR)).max())
+    worst_d = float(((d32 - d).abs() / ((u.abs() + 1.0) * A)).max())
+    worst_r = float(((d32 - d).abs() / (4.0 * A * d.abs() + A)).max())
+    _report(f"act_approx quick_gelu value {worst_v:.3f} derivative {worst_d:.3f} relative-form {worst_r:.3f} (fp32 torch vs fp64, ratio to the bound)")
+    assert worst_v <= 0.5 and worst_d <= 0.5 and worst_r <= 0.5, (worst_v, worst_d, worst_r)
+
+
+def test_quick_gelu_cases_reach_every_epilogue_form():
+    """The forms the quick-GELU cases run, from the stored routes: the staged bf16 epilogue, the direct one, fp32, the split-K
+    finishing kernel, a parity-class launch and the CLIP MLP's whole-tile pointwise class; value alone, value + saved
+    derivative, value under dropout, derivative of a saved pre-activation on each of staged / direct / fp32."""
+    forms = {}
+    for c in K.CASES:
+        if c["act"] != "quick_gelu":
+            continue
+        assert c["recipe"] in K.QGELU_RECIPES
+        for l in K.expected_route(c["name"]):
+            f = K.epi_form(c, l).split(":")[0]
+            forms.setdefault(f, set()).add(c["recipe"])
+            if c["name"].startswith("g.bf16.3x3s2.dgrad"):
+                assert dict(zip(K.ROUTE_FIELDS, l))["mode"] == 3
+    assert set(forms) >= {"lds", "direct", "f32", "split"}, forms
+    for f in ("lds", "direct", "f32"):
+        assert forms[f] >= set(K.QGELU_RECIPES), (f, forms[f])
+    assert {c["dtype"] for c in K.CASES if c["act"] == "quick_gelu" and K.expected_route(c["name"])[0][3] > 1} == {"bf16", "f32"}
+    # the MLP's class: unsplit whole tiles, more workgroups than resident slots; quick-GELU has no per-kind copy, so the staged
+    # epilogue is the generic one and the persistent pointwise kernel (which has none) must not take the launch
+    c = K.BY_NAME["pw.qgelu.plan"]
+    (l,) = K.expected_route(c["name"])
+    L = dict(zip(K.ROUTE_FIELDS, l))
+    assert L["splits"] == 1 and L["M"] % L["BM"] == 0 and c["Cout"] % L["BN"] == 0 and L["mtiles"] * L["ntiles"] > 16
+    assert K.epi_form(c, l) == ("pw:GENERIC" if L["pw"] else "lds:GENERIC:two_pass")
+    assert L["pw"] == 0, "the persistent pointwise kernel has no generic (quick-GELU) instantiation"
 
 
 def _torch_f32(c, o):
@@ -490,14 +529,15 @@ def emulate(c, o, launches, defect=None):
         v += o["rowadd"][(b + 1) % c["B"] if defect == "rowadd_neighbour" else b]
     pre = v.clone()
     d = torch.ones_like(v)
+    kind = {"act_as_gelu_erf": "gelu", "act_as_silu": "silu"}.get(defect, c["act"])     # another activation's code taken
     if c["dact"] == "mul":
         v = v * o["dact"]
     elif c["dact"] == "u":
-        v = v * R.act_grad(o["dact"].double(), c["act"]).float()
+        v = v * R.act_grad(o["dact"].double(), kind).float()
     elif c["act"] != "none":
-        d = R.act_grad(v.double(), c["act"]).float()
+        d = R.act_grad(v.double(), kind).float()
         if defect != "act_as_identity":               # (a ReLU that clamps nothing, a tanh that is not applied)
-            v = R.act(v.double(), c["act"]).float()
+            v = R.act(v.double(), kind).float()
         if defect == "dact_constant_one":
             d = torch.ones_like(d)
     if defect == "preact_post_activation":
@@ -554,6 +594,8 @@ DEFECTS = {
                         "epi.staged.tanh", "epi.direct.tanh", "epi.f32.tanh", "split.bf16.tanh", "split.bf16.128x128.mode2"),
     "dact_constant_one": ("epi.staged.relu_save", "epi.direct.relu_save", "epi.f32.relu_save", "split.bf16.relu_save", "split.f32.relu_save",
                           "epi.staged.gelu_drop_save", "split.bf16.silu_save_res"),
+    "act_as_gelu_erf": tuple(c["name"] for c in K.CASES if c["act"] == "quick_gelu"),
+    "act_as_silu": tuple(c["name"] for c in K.CASES if c["act"] == "quick_gelu"),
     "store_past_M": ("tile.bf16.64x64.m63.n8", "tile.f32.128x64.m259.n64", "epi.staged.plain", "ld.staged.all"),
 }
 
