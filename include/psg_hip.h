@@ -111,6 +111,37 @@ int psg_ddpm_update_f32(float* x, const float* eps, const float* z, const float*
 int psg_sampler_update_f32(float* x, const float* eps, const float* z, int mode, float c0, float c1, float c2,
                            float c3, int64_t n, psg_stream_t stream);
 
+/* Classifier-free guidance and the DDIM step (no counterpart in the reference; opt-in on the host side).  fp32, every
+ * operation rounded on its own (no FMA), so a numpy-float32 restatement gives the same bits.
+ *
+ * Per-sample text drop for training: text, out [B, row] (row = S * text_dim), null_text [row].  Sample b takes null_text when
+ * the library's stateless dropout hash drops element index b at rate p, else its own row of text.  The device word of
+ * psg_set_seed_source is added to seed when the launch runs, so a captured train step draws a new mask on every replay.
+ * dropped (int32 [B], may be NULL) receives 1 for a replaced sample and 0 otherwise.  16-byte loads and stores when row is a
+ * multiple of 4 and text, null_text and out are 16-byte aligned, element by element otherwise.  B == 0 is PSG_OK with nothing
+ * launched; B < 0 or row <= 0 is PSG_ERR_SHAPE; p outside [0, 1) (the hash's 16-bit threshold saturates: p = 1 would still keep
+ * one sample in 65 536), a null text, null_text or out, or out == text is PSG_ERR_ARG. */
+int psg_text_cond_drop_f32(const float* text, const float* null_text, float* out, int32_t* dropped, int64_t B, int64_t row,
+                           float p, uint64_t seed, psg_stream_t stream);
+/* out = eps_u + w * (eps_c - eps_u), three roundings; for the chains that keep their own update (psg_ddpm_update_f32,
+ * psg_sampler_update_f32).  out may alias eps_c.  n <= 0 is PSG_OK with nothing launched; a null pointer is PSG_ERR_ARG. */
+int psg_cfg_combine_f32(const float* eps_c, const float* eps_u, float w, float* out, int64_t n, psg_stream_t stream);
+/* One DDIM step in place on x, one launch.  tab: device [5, k] fp32, rows S0 = sqrt(abar_t), S1 = sqrt(1 - abar_t),
+ * P0 = sqrt(abar_prev), P1 = sqrt(1 - abar_prev - sigma^2), SG = sigma of step j (built by the host in fp64, rounded once).
+ * step_dev: int32 device scalar j, read on the device (graph-replayable); a j outside 0..k-1 reads the nearest entry.
+ *   e  = eps_c                                   when eps_u == NULL
+ *   e  = eps_u + w * (eps_c - eps_u)             otherwise
+ *   x0 = (x - S1[j] * e) / S0[j]
+ *   if clip > 0:  c = clamp(x0, -clip, clip)     (NaN stays NaN, as numpy.clip)
+ *                 where c != x0:  e = (x - S0[j] * c) / S1[j]
+ *                 x0 = c
+ *   x' = P0[j] * x0 + P1[j] * e  [+ SG[j] * z    when z != NULL]
+ * x' is written to x and, when x_copy != NULL, to x_copy too (the unconditional half of a 2n input buffer: no copy runs
+ * between steps).  16-byte accesses when n is a multiple of 4 and every pointer given is 16-byte aligned, element by element
+ * otherwise.  clip < 0, k < 1, or a null x, eps_c, tab or step_dev is PSG_ERR_ARG; n <= 0 is PSG_OK with nothing launched. */
+int psg_guided_update_f32(float* x, float* x_copy, const float* eps_c, const float* eps_u, const float* z, const float* tab, int k,
+                          const int32_t* step_dev, float w, float clip, int64_t n, psg_stream_t stream);
+
 /* VAE reparameterisation, src/models/vae_decoder.py:120-123: out = mu + eps * exp(0.5 * logvar) (fp32, separately rounded).
  * n <= 0 is PSG_OK with nothing launched; a null pointer is PSG_ERR_ARG. */
 int psg_reparam_f32(const float* mu, const float* logvar, const float* eps, float* out, int64_t n, psg_stream_t stream);

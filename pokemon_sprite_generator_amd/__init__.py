@@ -13,6 +13,7 @@ from .optim import FusedAdamW, GradArena, GroupedAdamW, ParamArena
 from .ddp import BucketedAllReduce
 from .trainer import DiffusionStepper, DiffusionTrainer, ImprovedDiffusionTrainer
 from .inference import LatentGenerator, LinearNoiseScheduler, gradio_ddpm_sample, load_unet_state
+from .guidance import DdimRun, cfg_combine, ddim_sample, ddim_tables, ddim_timesteps, text_cond_drop
 from .vae import PokemonVAE, VAEDecoder, VAEEncoder
 from .text_encoder import TextEncoder
 from .losses import CombinedLoss, VGGPerceptualLoss
@@ -27,5 +28,6 @@ from .generate import SpriteGenerator
 __all__ = ["UNet", "UNetBlock", "ResBlock", "CrossAttentionBlock", "TimestepEmbedding", "NoiseScheduler",
            "ImprovedDiffusionTrainer", "DiffusionTrainer", "DiffusionStepper", "FusedAdamW", "GradArena", "ParamArena",
            "BucketedAllReduce", "LatentGenerator", "LinearNoiseScheduler", "gradio_ddpm_sample", "load_unet_state", "PokemonVAE", "VAEEncoder", "VAEDecoder", "TextEncoder", "VGGPerceptualLoss", "CombinedLoss", "CLIPLoss",
-           "FinalPokemonGenerator", "FinalStepper", "GroupedAdamW", "VAEStepper", "SpriteDataset", "SpriteLoader", "create_data_loaders", "draw_params", "SpriteGenerator", "VAETrainer", "FinalTrainer", "TokenTable", "PsgError", "LIB_PATH"]
+           "FinalPokemonGenerator", "FinalStepper", "GroupedAdamW", "VAEStepper", "SpriteDataset", "SpriteLoader", "create_data_loaders", "draw_params", "SpriteGenerator", "VAETrainer", "FinalTrainer", "TokenTable", "PsgError", "LIB_PATH",
+           "DdimRun", "ddim_sample", "ddim_tables", "ddim_timesteps", "cfg_combine", "text_cond_drop"]
 __version__ = "0.1.0"

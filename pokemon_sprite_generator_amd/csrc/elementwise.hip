@@ -109,6 +109,90 @@ __global__ void sampler_update_kernel(float* __restrict__ x, const float* __rest
 }
 
 // ---------------------------------------------------------------------------
+// Classifier-free guidance and the DDIM step (opt-in; nothing above changes).  Every operation is its own rounding, so a
+// numpy-float32 restatement (tests/guided_ref.py) gives the same bits.
+// ---------------------------------------------------------------------------
+// training: sample b keeps its text or takes the null text; the mask is drop_keep at element index b
+template <bool VEC>
+__global__ void text_cond_drop_kernel(const float* __restrict__ text, const float* __restrict__ null_text, float* __restrict__ out,
+                                      int32_t* __restrict__ dropped, int64_t B, int64_t row, uint32_t thresh, uint64_t seed0,
+                                      const uint64_t* seed_dev) {
+    const uint64_t seed = eff_seed(seed0, seed_dev);
+    constexpr int W = VEC ? 4 : 1;
+    const int64_t per_row = row / W, total = B * per_row;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = i / per_row, c = (i - b * per_row) * W;
+        const bool keep = drop_keep(seed, (uint64_t)b, thresh);
+        const float* src = keep ? text + b * row + c : null_text + c;
+        if (VEC) store4<float>(out + b * row + c, load4<float>(src));
+        else out[b * row + c] = *src;
+        if (c == 0 && dropped) dropped[b] = keep ? 0 : 1;
+    }
+}
+
+// eps_u + w (eps_c - eps_u); out may be eps_c (each element is read before it is written, by the same lane)
+template <bool VEC>
+__global__ void cfg_combine_kernel(const float* eps_c, const float* __restrict__ eps_u, float w, float* out, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (VEC) {
+            const f32x4 c = load4<float>(eps_c + 4 * i), u = load4<float>(eps_u + 4 * i);
+            f32x4 r;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) r[e] = __fadd_rn(u[e], __fmul_rn(w, __fsub_rn(c[e], u[e])));
+            store4<float>(out + 4 * i, r);
+        } else {
+            const float c = eps_c[i], u = eps_u[i];
+            out[i] = __fadd_rn(u, __fmul_rn(w, __fsub_rn(c, u)));
+        }
+    }
+}
+
+// One DDIM step of one element (the formula of psg_guided_update_f32 in psg_hip.h).  The clamp lets NaN through (both
+// comparisons are false), as numpy.clip; `c != x0` is then true and e becomes NaN with it.
+struct GuidedCoef { float s0, s1, p0, p1, sg; };
+__device__ __forceinline__ float guided_elem(float x, float ec, float eu, bool has_u, float w, const GuidedCoef& k, float clip,
+                                             float z, bool has_z) {
+    float e = ec;
+    if (has_u) e = __fadd_rn(eu, __fmul_rn(w, __fsub_rn(ec, eu)));
+    float x0 = __fdiv_rn(__fsub_rn(x, __fmul_rn(k.s1, e)), k.s0);
+    if (clip > 0.f) {
+        const float c = x0 < -clip ? -clip : (x0 > clip ? clip : x0);
+        if (c != x0) e = __fdiv_rn(__fsub_rn(x, __fmul_rn(k.s0, c)), k.s1);
+        x0 = c;
+    }
+    float r = __fadd_rn(__fmul_rn(k.p0, x0), __fmul_rn(k.p1, e));
+    if (has_z) r = __fadd_rn(r, __fmul_rn(k.sg, z));
+    return r;
+}
+
+// n counts float4s when VEC.  x_copy (may be NULL) receives the same values as x: the unconditional half of a 2n input.
+template <bool VEC>
+__global__ void guided_update_kernel(float* x, float* x_copy, const float* __restrict__ eps_c, const float* __restrict__ eps_u,
+                                     const float* __restrict__ z, const float* __restrict__ tab, int k,
+                                     const int32_t* __restrict__ step_dev, float w, float clip, int64_t n) {
+    int j = *step_dev;
+    j = j < 0 ? 0 : (j >= k ? k - 1 : j);
+    const GuidedCoef co = {tab[j], tab[k + j], tab[2 * k + j], tab[3 * k + j], tab[4 * k + j]};
+    const bool has_u = eps_u != nullptr, has_z = z != nullptr;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (VEC) {
+            const f32x4 xv = load4<float>(x + 4 * i), ec = load4<float>(eps_c + 4 * i);
+            f32x4 eu = {0.f, 0.f, 0.f, 0.f}, zv = {0.f, 0.f, 0.f, 0.f}, r;
+            if (has_u) eu = load4<float>(eps_u + 4 * i);
+            if (has_z) zv = load4<float>(z + 4 * i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) r[e] = guided_elem(xv[e], ec[e], eu[e], has_u, w, co, clip, zv[e], has_z);
+            store4<float>(x + 4 * i, r);
+            if (x_copy) store4<float>(x_copy + 4 * i, r);
+        } else {
+            const float r = guided_elem(x[i], eps_c[i], has_u ? eps_u[i] : 0.f, has_u, w, co, clip, has_z ? z[i] : 0.f, has_z);
+            x[i] = r;
+            if (x_copy) x_copy[i] = r;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // deterministic two-stage reductions (fixed grid, fixed order)
 // ---------------------------------------------------------------------------
 constexpr int RED_BLOCKS = 1024;
@@ -982,6 +1066,53 @@ int psg_sampler_update_f32(float* x, const float* eps, const float* z, int mode,
     if (n <= 0) return PSG_OK;
     hipLaunchKernelGGL(sampler_update_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, eps, z, mode, c0, c1, c2, c3, n);
     PSG_LAUNCH_CHECK("sampler_update");
+    return PSG_OK;
+}
+
+int psg_text_cond_drop_f32(const float* text, const float* null_text, float* out, int32_t* dropped, int64_t B, int64_t row,
+                           float p, uint64_t seed, psg_stream_t stream) {
+    PSG_REQUIRE(text && null_text && out, PSG_ERR_ARG, "text_cond_drop: null pointer");
+    PSG_REQUIRE(out != text, PSG_ERR_ARG, "text_cond_drop: out aliases text");
+    PSG_REQUIRE(p >= 0.f && p < 1.f, PSG_ERR_ARG, "text_cond_drop: p=%g outside [0, 1)", (double)p);
+    PSG_REQUIRE(B >= 0 && row > 0, PSG_ERR_SHAPE, "text_cond_drop: bad shape B=%ld row=%ld", (long)B, (long)row);
+    if (B == 0) return PSG_OK;
+    const uint32_t th = drop_thresh(p);
+    if ((row & 3) == 0 && aligned16(text) && aligned16(null_text) && aligned16(out))
+        hipLaunchKernelGGL(text_cond_drop_kernel<true>, dim3(grid_for(B * (row / 4), 256)), dim3(256), 0, (hipStream_t)stream, text,
+                           null_text, out, dropped, B, row, th, seed, seed_source());
+    else
+        hipLaunchKernelGGL(text_cond_drop_kernel<false>, dim3(grid_for(B * row, 256)), dim3(256), 0, (hipStream_t)stream, text,
+                           null_text, out, dropped, B, row, th, seed, seed_source());
+    PSG_LAUNCH_CHECK("text_cond_drop");
+    return PSG_OK;
+}
+
+int psg_cfg_combine_f32(const float* eps_c, const float* eps_u, float w, float* out, int64_t n, psg_stream_t stream) {
+    PSG_REQUIRE(eps_c && eps_u && out, PSG_ERR_ARG, "cfg_combine: null pointer");
+    if (n <= 0) return PSG_OK;
+    if ((n & 3) == 0 && aligned16(eps_c) && aligned16(eps_u) && aligned16(out))
+        hipLaunchKernelGGL(cfg_combine_kernel<true>, dim3(grid_for(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, eps_c, eps_u, w,
+                           out, n / 4);
+    else
+        hipLaunchKernelGGL(cfg_combine_kernel<false>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, eps_c, eps_u, w, out, n);
+    PSG_LAUNCH_CHECK("cfg_combine");
+    return PSG_OK;
+}
+
+int psg_guided_update_f32(float* x, float* x_copy, const float* eps_c, const float* eps_u, const float* z, const float* tab, int k,
+                          const int32_t* step_dev, float w, float clip, int64_t n, psg_stream_t stream) {
+    PSG_REQUIRE(x && eps_c && tab && step_dev, PSG_ERR_ARG, "guided_update: null pointer");
+    PSG_REQUIRE(clip >= 0.f && k >= 1, PSG_ERR_ARG, "guided_update: clip=%g k=%d", (double)clip, k);
+    if (n <= 0) return PSG_OK;
+    // x_copy = x + n with n % 4 != 0 is off the 16-byte boundary: every pointer is looked at, not only x
+    const bool vec = (n & 3) == 0 && aligned16(x) && aligned16(x_copy) && aligned16(eps_c) && aligned16(eps_u) && aligned16(z);
+    if (vec)
+        hipLaunchKernelGGL(guided_update_kernel<true>, dim3(grid_for(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, x, x_copy, eps_c,
+                           eps_u, z, tab, k, step_dev, w, clip, n / 4);
+    else
+        hipLaunchKernelGGL(guided_update_kernel<false>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, x_copy, eps_c,
+                           eps_u, z, tab, k, step_dev, w, clip, n);
+    PSG_LAUNCH_CHECK("guided_update");
     return PSG_OK;
 }
 

@@ -15,6 +15,7 @@ import torch
 
 from . import imaging
 from ._lib import PsgError
+from .guidance import ddim_sample, encode_null_text
 from .inference import gradio_ddpm_sample, load_unet_state
 from .text_encoder import TextEncoder
 from .unet import UNet
@@ -73,10 +74,24 @@ class SpriteGenerator:
             return self.text_encoder.encode_ids(*descriptions)
         return self.text_encoder(list(descriptions))
 
-    def _sample(self, text_emb, num_inference_steps, initial_latent, noise_fn):
-        return gradio_ddpm_sample(self.unet, text_emb, num_inference_steps, initial_latent=initial_latent,
-                                  num_timesteps=self.num_timesteps, beta_start=self.beta_start, beta_end=self.beta_end,
-                                  latent_dim=self.latent_dim, noise_fn=noise_fn)
+    def _null_text(self, descriptions, S):
+        """[S, text_dim]: the empty description encoded to the prompts' token length."""
+        like = descriptions[:2] if isinstance(descriptions, tuple) else None
+        return encode_null_text(self.text_encoder, S, like)
+
+    def _sample(self, text_emb, num_inference_steps, initial_latent, noise_fn, sampler="gradio", guidance_scale=None, eta=0.0,
+                clip=3.0, descriptions=None):
+        null = self._null_text(descriptions, text_emb.shape[1]) if guidance_scale is not None else None
+        if sampler == "gradio":
+            kw = {} if guidance_scale is None else {"guidance_scale": guidance_scale, "null_text": null}
+            return gradio_ddpm_sample(self.unet, text_emb, num_inference_steps, initial_latent=initial_latent,
+                                      num_timesteps=self.num_timesteps, beta_start=self.beta_start, beta_end=self.beta_end,
+                                      latent_dim=self.latent_dim, noise_fn=noise_fn, **kw)
+        if sampler != "ddim":
+            raise PsgError(f"sampler={sampler!r} (\"gradio\" or \"ddim\")")
+        betas = torch.linspace(self.beta_start, self.beta_end, self.num_timesteps)        # the demo's linear schedule (:279-288)
+        return ddim_sample(self.unet, text_emb, torch.cumprod(1.0 - betas, dim=0), num_inference_steps, eta, guidance_scale, null, clip,
+                           initial_latent, noise_fn, latent_dim=self.latent_dim)
 
     @staticmethod
     def _seed(seed):
@@ -94,21 +109,27 @@ class SpriteGenerator:
     # -- :363-392 --------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def generate_from_text(self, descriptions, num_inference_steps: int = 50, seed: Optional[int] = None, noise_fn=None,
-                           as_pil: bool = False):
+                           as_pil: bool = False, sampler: str = "gradio", guidance_scale: Optional[float] = None, eta: float = 0.0,
+                           clip: float = 3.0):
         """uint8 [B, S, S, 3] on the device (S = 215).  `noise_fn(i, shape)`: `gradio_ddpm_sample`'s - i = -1 the initial
-        latent, i >= 0 the i-th sampler draw.  as_pil=True: PIL images instead (one image for one string, else a list)."""
+        latent, i >= 0 the i-th sampler draw.  as_pil=True: PIL images instead (one image for one string, else a list).
+        Opt-in: sampler="ddim" (guidance.ddim_sample over the demo's linear schedule, with `eta` and `clip`) and
+        `guidance_scale` (either sampler; the null text is the empty description at the prompts' token length)."""
         self._seed(seed)
         text_emb = self._encode_text(descriptions)
-        latent = self._sample(text_emb, num_inference_steps, None, noise_fn)
+        latent = self._sample(text_emb, num_inference_steps, None, noise_fn, sampler, guidance_scale, eta, clip, descriptions)
         return self._finish(self.vae.decode(latent, text_emb), as_pil, isinstance(descriptions, str))
 
     # -- :394-438 --------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def generate_from_image_and_text(self, images, descriptions, num_inference_steps: int = 50, noise_strength: float = 0.7,
-                                     seed: Optional[int] = None, eps=None, noise=None, noise_fn=None, as_pil: bool = False):
+                                     seed: Optional[int] = None, eps=None, noise=None, noise_fn=None, as_pil: bool = False,
+                                     sampler: str = "gradio", guidance_scale: Optional[float] = None, eta: float = 0.0,
+                                     clip: float = 3.0):
         """`images`: one upload (PIL image, uint8 array or tensor, any size) or a list of them, one per description.  `eps`:
         the encoder's reparameterisation noise, `noise`: the blend's (both default to randn draws, [B, latent_dim, 27, 27]);
-        noise_strength <= 0 skips the blend and draws nothing for it."""
+        noise_strength <= 0 skips the blend and draws nothing for it.  sampler / guidance_scale / eta / clip: as
+        generate_from_text; the blended latent is the chain's initial latent and the full chain runs, as with "gradio"."""
         self._seed(seed)
         dev = self._device()
         single = not isinstance(images, (list, tuple))
@@ -122,5 +143,5 @@ class SpriteGenerator:
         text_emb = self._encode_text(descriptions)
         if text_emb.shape[0] != latent.shape[0]:
             raise PsgError(f"generate_from_image_and_text: {latent.shape[0]} image(s) but {text_emb.shape[0]} description(s)")
-        latent = self._sample(text_emb, num_inference_steps, latent, noise_fn)
+        latent = self._sample(text_emb, num_inference_steps, latent, noise_fn, sampler, guidance_scale, eta, clip, descriptions)
         return self._finish(self.vae.decode(latent, text_emb), as_pil, single)

@@ -22,6 +22,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
+from .guidance import expand_null_text, guided_eps
 
 
 def _lib_for(t):
@@ -157,8 +158,10 @@ class LatentGenerator:
 @torch.no_grad()
 def gradio_ddpm_sample(unet, text_emb: torch.Tensor, num_inference_steps: int = 50, initial_latent: Optional[torch.Tensor] = None,
                        num_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02, latent_dim: int = 8,
-                       noise_fn=None, trace=None) -> torch.Tensor:
-    """PokemonGradioGenerator.ddpm_sample (gradio_app.py:297-361) with its own linear schedule (:279-288)."""
+                       noise_fn=None, trace=None, guidance_scale=None, null_text=None) -> torch.Tensor:
+    """PokemonGradioGenerator.ddpm_sample (gradio_app.py:297-361) with its own linear schedule (:279-288).
+    Opt-in: `guidance_scale` with `null_text` [S, text_dim] runs each forward at batch 2n on [x; x] with [text; null_text] and
+    feeds eps_u + w (eps_c - eps_u) (psg_cfg_combine_f32) to the same update."""
     unet.eval()
     dev = next(unet.parameters()).device
     betas = torch.linspace(beta_start, beta_end, num_timesteps)
@@ -171,11 +174,18 @@ def gradio_ddpm_sample(unet, text_emb: torch.Tensor, num_inference_steps: int = 
         latent = rnd(-1, (B, latent_dim, 27, 27)).to(device=dev, dtype=torch.float32).contiguous().clone()
     else:
         latent = initial_latent.to(device=dev, dtype=torch.float32).contiguous().clone()
+    guided = guidance_scale is not None
+    if guided:
+        if null_text is None:
+            raise ValueError("gradio_ddpm_sample: guidance_scale needs null_text")
+        xin = torch.cat([latent, latent], dim=0).contiguous()
+        latent = xin[:B]
+        text2 = torch.cat([text_emb, expand_null_text(null_text, text_emb)], dim=0).contiguous()
     timesteps = torch.linspace(num_timesteps - 1, 0, num_inference_steps, dtype=torch.long)
     draws = 0
     for i, t in enumerate(timesteps):
-        tv = torch.full((B,), t.item(), dtype=torch.long, device=dev)
-        eps = unet(latent, tv, text_emb)
+        tv = torch.full((2 * B if guided else B,), t.item(), dtype=torch.long, device=dev)
+        eps = guided_eps(unet, xin, tv, text2, float(guidance_scale), B) if guided else unet(latent, tv, text_emb)
         one = np.float32(1.0)                                   # fp32 scalar arithmetic, as the reference's 0-d tensors
         a_t, ac_t = _f32(alphas[t]), _f32(alphas_cumprod[t])
         k0 = float((one - a_t) / _sqrt32(one - ac_t))
@@ -189,6 +199,8 @@ def gradio_ddpm_sample(unet, text_emb: torch.Tensor, num_inference_steps: int = 
                 a_n = _f32(alphas[next_t])
                 c2, c3 = float(_sqrt32(a_n)), float(_sqrt32(one - a_n))
         _update(latent, eps, z, 3, k0, k1, c2, c3)
+        if guided:
+            xin[B:].copy_(latent)
         if trace is not None:
             trace.append(latent.clone())
-    return latent
+    return latent.clone() if guided else latent

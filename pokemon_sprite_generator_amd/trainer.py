@@ -34,6 +34,7 @@ import torch
 from . import _lib
 from . import ops as ops_mod
 from ._lib import FLAG_INPUT_BAD, FLAG_LOSS_BAD, FLAG_NOISY_BAD, FLAG_PRED_BAD, FLAG_SKIP_MASK, FLAG_T_RANGE, check, ptr, stream_ptr
+from .guidance import DdimRun, encode_null_text, expand_null_text, guided_eps, text_cond_drop
 from .ddp import BucketedAllReduce, ShardedLoader, dist_info, rank_generator
 from .optim import FusedAdamW, GradArena, ParamArena
 from .scheduler import NoiseScheduler
@@ -65,8 +66,14 @@ class DiffusionStepper:
 
     def __init__(self, unet: UNet, noise_scheduler: NoiseScheduler, lr=1e-4, betas=(0.9, 0.999), weight_decay=0.01,
                  eps=1e-6, max_grad_norm=1.0, optimizer_type="adamw", distributed=None, bucket_bytes=64 << 20,
-                 grad_bucket_dtype=torch.float32, ddp_cu_reserve=None, ema_decay=None, ema_warmup=True):
+                 grad_bucket_dtype=torch.float32, ddp_cu_reserve=None, ema_decay=None, ema_warmup=True, cond_drop_prob=None):
         self.unet, self.noise_scheduler = unet, noise_scheduler
+        # classifier-free guidance training (opt-in; None or 0: nothing is launched and no seed is drawn): each sample's text is
+        # replaced by the null text with this probability before the U-Net (psg_text_cond_drop_f32)
+        if cond_drop_prob is not None and not 0.0 <= float(cond_drop_prob) < 1.0:
+            raise ValueError(f"cond_drop_prob={cond_drop_prob} outside [0, 1)")
+        self.cond_drop_prob = float(cond_drop_prob) if cond_drop_prob else None
+        self.last_text_dropped = None              # int32 [B] on the device: 1 where the last step dropped the text
         self.max_grad_norm = max_grad_norm
         self.device = next(unet.parameters()).device
         if self.device.type != "cuda":
@@ -206,20 +213,30 @@ class DiffusionStepper:
         torch.distributed.all_reduce(skip, op=torch.distributed.ReduceOp.MAX)
         self.flag.copy_((self.flag & ~FLAG_SKIP_MASK) | skip)
 
-    def train_step(self, latents, text_emb, t, noise=None, lr=None, pre_flag=None) -> Dict[str, torch.Tensor]:
+    def train_step(self, latents, text_emb, t, noise=None, lr=None, pre_flag=None, null_text=None,
+                   text_drop_seed=None) -> Dict[str, torch.Tensor]:
         """One optimizer step on a batch of clean latents (the body of train_epoch, :363-413).
 
         latents [B,8,27,27] fp32 (un-clamped VAE output), text_emb [B,S,text_dim], t [B] int64, optional
         noise (default randn_like).  `pre_flag` (int32 device tensor or None) is OR-ed into the step's flag word
         (the caller's own input checks, :353,359).  Returns device tensors {'loss','grad_norm','nan_flag'} (no sync);
         a step whose flag has a bit of FLAG_SKIP_MASK leaves parameters, optimizer state, step count and schedule
-        untouched."""
+        untouched.  With `cond_drop_prob`, `null_text` [S, text_dim] is required and replaces the text of the samples the mask
+        of `text_drop_seed` (default: the next seed of the dropout seed stream) drops; `last_text_dropped` tells which."""
         self._no_ema_scope("train_step")
         if not self.unet.training:             # (module.train() walks all ~390 submodules: 1.6 ms of host time per call)
             self.unet.train()
         if ops_mod.SeedSource.enabled():       # fixed per-site seeds + a device word that changes per step (graph replay)
             from .unet import _SeedStream
             _SeedStream.counter = 0
+        if self.cond_drop_prob:
+            if null_text is None:
+                raise _lib.PsgError("train_step: cond_drop_prob needs null_text (the embedding of the empty description)")
+            from .unet import _SeedStream
+            seed = int(text_drop_seed) if text_drop_seed is not None else _SeedStream.next()
+            if self.last_text_dropped is None or self.last_text_dropped.numel() != text_emb.shape[0]:
+                self.last_text_dropped = torch.zeros((text_emb.shape[0],), dtype=torch.int32, device=self.device)
+            text_emb, _ = text_cond_drop(text_emb.to(self.device), null_text, self.cond_drop_prob, seed, dropped=self.last_text_dropped)
         if noise is None:
             noise = self.randn_like(latents)
         self.flag.zero_()
@@ -250,7 +267,7 @@ class DiffusionStepper:
         ops_mod.SeedSource.advance()
         return {"loss": loss.clone(), "grad_norm": normsq.sqrt(), "nan_flag": self.flag.clone()}
 
-    def capture_train_step(self, latents, text_emb, t, warmup=2):
+    def capture_train_step(self, latents, text_emb, t, warmup=2, null_text=None, text_drop_seed=None):
         """hipGraph of one whole train step (add_noise .. AdamW, ~1200 launches) for fixed shapes: returns a `GraphedTrainStep`
         whose `run(latents, text_emb, t)` copies the batch into the captured buffers and replays.  The step has no host
         reads (flags, step count and schedule live on the device) and its dropout masks keep changing between replays
@@ -260,13 +277,15 @@ class DiffusionStepper:
         MODE SWITCH: capturing enables `ops.SeedSource` (fixed per-site dropout seeds + a device word advanced every step)
         for the whole process - eager steps of this and any other stepper draw their masks that way too from then on -
         until the LAST live graph is closed (`GraphedTrainStep.close()`, or this stepper's `close()`; the source is reference
-        counted, one count per graph: the device word is baked into captured kernel arguments)."""
+        counted, one count per graph: the device word is baked into captured kernel arguments).
+        With `cond_drop_prob` the text drop is part of the graph: its seed is a launch argument like the dropout seeds and the
+        device word makes every replay drop other samples; `null_text` is copied into a captured buffer."""
         self._no_ema_scope("capture_train_step")
         if self.reducer is not None:
             raise NotImplementedError("capture_train_step: data-parallel steps are not captured")
         if not isinstance(self.optimizer, FusedAdamW):
             raise NotImplementedError("capture_train_step needs the fused optimizer (device-side step count)")
-        return GraphedTrainStep(self, latents, text_emb, t, warmup)
+        return GraphedTrainStep(self, latents, text_emb, t, warmup, null_text, text_drop_seed)
 
     def autotune_exchange(self, latents, text_emb, t, trials=3):
         """Data parallel: measure which gradient-exchange mode is fastest on THIS machine (ddp.BucketedAllReduce.autotune: real
@@ -321,29 +340,50 @@ class DiffusionStepper:
 
     @torch.no_grad()
     def sample(self, text_emb, num_samples, fast_sampling=True, noise_fn=None, latent_dim=8, hw=27, trace=None, use_graph=None,
-               max_steps=None):
+               max_steps=None, sampler="ddpm", num_steps=None, eta=0.0, guidance_scale=None, null_text=None, clip=3.0):
         """ddpm_sample (:508-569): x <- (x - c2*eps)/sqrt(alpha_t) [+ sqrt(beta_t)*z if t>0], t strided by 50 when fast.
         noise_fn(i, shape) -> tensor supplies x_T (i = -1) and the per-step z (tests inject it); default torch.randn.
         `max_steps` runs only the first that many steps of the chain (benchmarks / property tests of the 1000-step loop).
-        See SamplerRun for the hipGraph form (use_graph=True or PSG_GRAPH=1; bit-identical to the eager loop)."""
-        run = SamplerRun(self, text_emb, num_samples, fast_sampling, noise_fn, latent_dim, hw, use_graph, max_steps)
+        See SamplerRun for the hipGraph form (use_graph=True or PSG_GRAPH=1; bit-identical to the eager loop).
+        Opt-in (guidance.py; the defaults are the chain above, untouched): sampler="ddim" runs `ddim_sample` over this
+        scheduler's alphas_cumprod with `num_steps` (default 50) forwards, `eta` and `clip`; `guidance_scale` with `null_text`
+        guides either chain - "ddpm" then runs one forward at batch 2n, psg_cfg_combine_f32 and the same update."""
+        run = self.sampler(text_emb, num_samples, fast_sampling, noise_fn, latent_dim, hw, use_graph, max_steps, sampler, num_steps,
+                           eta, guidance_scale, null_text, clip)
         while run.remaining():
             run.step()
             if trace is not None:
                 trace.append(run.x.clone())
-        return run.x
+        return run.x if type(run) is SamplerRun else run.x.clone()     # (guided: x is a view of the 2n input buffer)
 
-    def sampler(self, text_emb, num_samples, fast_sampling=True, noise_fn=None, latent_dim=8, hw=27, use_graph=None, max_steps=None):
+    def sampler(self, text_emb, num_samples, fast_sampling=True, noise_fn=None, latent_dim=8, hw=27, use_graph=None, max_steps=None,
+                sampler="ddpm", num_steps=None, eta=0.0, guidance_scale=None, null_text=None, clip=3.0):
         """The same chain, one `step()` at a time (bench.py times single denoising steps)."""
-        return SamplerRun(self, text_emb, num_samples, fast_sampling, noise_fn, latent_dim, hw, use_graph, max_steps)
+        if sampler == "ddpm" and guidance_scale is None:
+            return SamplerRun(self, text_emb, num_samples, fast_sampling, noise_fn, latent_dim, hw, use_graph, max_steps)
+        if guidance_scale is not None and null_text is None:
+            raise ValueError("sample: guidance_scale needs null_text")
+        if sampler == "ddpm":
+            return GuidedSamplerRun(self, text_emb, num_samples, fast_sampling, noise_fn, latent_dim, hw, use_graph, max_steps,
+                                    guidance_scale=guidance_scale, null_text=null_text)
+        if sampler != "ddim":
+            raise ValueError(f"sample: sampler={sampler!r} (\"ddpm\" or \"ddim\")")
+        if max_steps is not None:
+            raise ValueError("sample: max_steps cuts the ddpm chain short; a ddim chain takes num_steps")
+        if text_emb.shape[0] != num_samples:
+            raise ValueError(f"sample: {num_samples} samples for {text_emb.shape[0]} texts")
+        return DdimRun(self.unet, text_emb, self.noise_scheduler.alphas_cumprod, 50 if num_steps is None else num_steps, eta,
+                       guidance_scale, null_text, clip, None, noise_fn, use_graph, latent_dim, hw)
 
 
 class GraphedTrainStep:
     """See DiffusionStepper.capture_train_step."""
 
-    def __init__(self, stepper, latents, text_emb, t, warmup):
+    def __init__(self, stepper, latents, text_emb, t, warmup, null_text=None, text_drop_seed=None):
         from .ops import SeedSource, WeightCache
         self.stepper = stepper
+        self.null = None if null_text is None else null_text.detach().to(device=stepper.device, dtype=torch.float32).contiguous().clone()
+        kw = {} if self.null is None else {"null_text": self.null, "text_drop_seed": text_drop_seed}
         dev = stepper.device
         SeedSource.acquire(dev)
         self._ws_hold = None
@@ -355,13 +395,13 @@ class GraphedTrainStep:
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
-                stepper.train_step(self.lat, self.txt, self.t)
+                stepper.train_step(self.lat, self.txt, self.t, **kw)
             torch.cuda.synchronize(dev)
             self.graph = torch.cuda.CUDAGraph()
             _lib.freeze_workspaces(True)           # a growing request inside the capture raises instead of replacing a captured buffer
             try:
                 with torch.cuda.graph(self.graph, stream=side):
-                    self.out = stepper.train_step(self.lat, self.txt, self.t)
+                    self.out = stepper.train_step(self.lat, self.txt, self.t, **kw)
             finally:
                 _lib.freeze_workspaces(False)
             # the captured launches hold raw pointers into this stream's scratch buffer: pin it (torch recycles stream handles)
@@ -384,7 +424,7 @@ class GraphedTrainStep:
         if self in self.stepper._graphs:
             self.stepper._graphs.remove(self)
 
-    def run(self, latents=None, text_emb=None, t=None):
+    def run(self, latents=None, text_emb=None, t=None, null_text=None):
         from .ops import WeightCache
         if self._closed:
             raise _lib.PsgError("GraphedTrainStep.run after close()")
@@ -395,6 +435,8 @@ class GraphedTrainStep:
             self.txt.copy_(text_emb)
         if t is not None:
             self.t.copy_(t)
+        if null_text is not None and self.null is not None:
+            self.null.copy_(null_text.reshape(self.null.shape))
         self.graph.replay()
         WeightCache.invalidate()          # the replay moved the weights: entries prepared by eager code are stale
         return self.out
@@ -505,6 +547,31 @@ class SamplerRun:
             self.graph.replay()
         else:
             self._body()
+
+
+class GuidedSamplerRun(SamplerRun):
+    """The same chain with classifier-free guidance: ONE forward at batch 2n on [x; x] with the text [text; null_text],
+    psg_cfg_combine_f32 on the two halves of its output, the same psg_ddpm_update_f32, and a copy of x into the second half."""
+
+    @torch.no_grad()
+    def __init__(self, stepper, text_emb, num_samples, fast_sampling=True, noise_fn=None, latent_dim=8, hw=27, use_graph=None,
+                 max_steps=None, guidance_scale=1.0, null_text=None):
+        super().__init__(stepper, text_emb, num_samples, fast_sampling, noise_fn, latent_dim, hw, use_graph, max_steps)
+        if self.text.shape[0] != num_samples:
+            raise ValueError(f"sample: {num_samples} samples for {self.text.shape[0]} texts")
+        n = num_samples
+        self.w = float(guidance_scale)
+        self.xin = torch.cat([self.x, self.x], dim=0).contiguous()
+        self.x = self.xin[:n]
+        self.tv = torch.zeros((2 * n,), device=stepper.device, dtype=torch.long)
+        self.text = torch.cat([self.text, expand_null_text(null_text, self.text)], dim=0).contiguous()
+
+    def _body(self):
+        st, n = self.st, self.x.shape[0]
+        eps = guided_eps(st.unet, self.xin, self.tv, self.text, self.w, n)
+        check(st.lib.psg_ddpm_update_f32(ptr(self.x), ptr(eps), ptr(self.z), ptr(self.c1), ptr(self.c2), ptr(self.sg), ptr(self.t_dev),
+                                         self.x.numel(), stream_ptr()), "psg_ddpm_update_f32")
+        self.xin[n:].copy_(self.x)
 
 
 def schedule_tables(make_scheduler, lr, betas, total):
@@ -717,16 +784,29 @@ class ImprovedDiffusionTrainer(TrainerBase):
         # opt-in EMA of the U-Net weights (`training.ema_decay`; absent, None or 0: off, the reference's behaviour)
         tc = self.config.get("training", {}) or {}
         self.ema_decay = float(tc["ema_decay"]) if tc.get("ema_decay") else None
+        # opt-in classifier-free guidance and DDIM sampling (absent: today's behaviour): `training.cond_drop_prob` trains with
+        # the text dropped at that rate; `training.sampler` ("ddpm" / "ddim"), `sample_steps`, `guidance_scale`, `ddim_eta`
+        # are what sample() / ddpm_sample() / generate_samples() run
+        self.cond_drop_prob = float(tc["cond_drop_prob"]) if tc.get("cond_drop_prob") else None
+        self.sample_opts = {"sampler": str(tc.get("sampler", "ddpm")), "num_steps": tc.get("sample_steps"),
+                            "guidance_scale": None if tc.get("guidance_scale") is None else float(tc["guidance_scale"]),
+                            "eta": float(tc.get("ddim_eta", 0.0))}
+        if self.sample_opts["sampler"] not in ("ddpm", "ddim"):
+            raise ValueError(f"training.sampler={self.sample_opts['sampler']!r} (\"ddpm\" or \"ddim\")")
+        self._null_cache = {}
         self._betas = (get("beta1", 0.9), get("beta2", 0.999))
         self.stepper = DiffusionStepper(self.unet, self.noise_scheduler, lr=lr, betas=self._betas,
                                         weight_decay=get("weight_decay"), eps=1e-6, max_grad_norm=self.max_grad_norm,
                                         optimizer_type=get("optimizer", "adamw"), grad_bucket_dtype=self._grad_bucket_dtype,
-                                        ema_decay=self.ema_decay, ema_warmup=bool(tc.get("ema_warmup", True)))
+                                        ema_decay=self.ema_decay, ema_warmup=bool(tc.get("ema_warmup", True)),
+                                        cond_drop_prob=self.cond_drop_prob)
         self.optimizer = self.stepper.optimizer
         self.scheduler_config = {"type": uc.get("scheduler", oc.get("scheduler", "cosine")), "lr": lr}
         self.logger.info(f"Using U-Net optimization: {get('optimizer', 'adamw')}, lr={lr}, wd={get('weight_decay')}, clip={self.max_grad_norm}")
         if self.ema_decay:
             self.logger.info(f"EMA of the U-Net weights: decay={self.ema_decay}, warmup={bool(tc.get('ema_warmup', True))}")
+        if self.cond_drop_prob:
+            self.logger.info(f"Classifier-free guidance training: the text is dropped with probability {self.cond_drop_prob}")
 
     def _make_scheduler(self, optimizer):
         if self.scheduler_config["type"] == "cosine":
@@ -772,10 +852,21 @@ class ImprovedDiffusionTrainer(TrainerBase):
         self.scheduler._last_lr = [g["lr"]]
 
     # -- facade ---------------------------------------------------------------------------------------
-    def train_step(self, latents, text_emb, t, noise=None, pre_flag=None):
+    def null_text(self, S: int, like=None) -> torch.Tensor:
+        """[S, text_dim]: the embedding of the empty description at token length S ([CLS] [SEP] [PAD]..., mask 1, 1, 0, ...),
+        cached per S - the text encoder is frozen in stage 2."""
+        S = int(S)
+        if S not in self._null_cache:
+            self._null_cache[S] = encode_null_text(self.text_encoder, S, like).to(self.device).contiguous()
+        return self._null_cache[S]
+
+    def train_step(self, latents, text_emb, t, noise=None, pre_flag=None, null_text=None, text_drop_seed=None):
         """The loop body :363-413 on clean latents; see DiffusionStepper.train_step.  No host sync with the fused
         optimizer: the step count and the lr / beta1 schedule advance on the device, and only when the step happened."""
-        out = self.stepper.train_step(latents, text_emb, t, noise, pre_flag=pre_flag)
+        kw = {}
+        if self.cond_drop_prob:
+            kw = {"null_text": null_text if null_text is not None else self.null_text(text_emb.shape[1]), "text_drop_seed": text_drop_seed}
+        out = self.stepper.train_step(latents, text_emb, t, noise, pre_flag=pre_flag, **kw)
         if not self._fused and (int(out["nan_flag"].item()) & FLAG_SKIP_MASK) == 0:
             self.scheduler.step()                                                                    # :413
         return out
@@ -789,8 +880,12 @@ class ImprovedDiffusionTrainer(TrainerBase):
         return self.stepper.ema_weights() if use_ema else contextlib.nullcontext()
 
     def sample(self, text_emb, num_samples, fast_sampling=True, noise_fn=None, use_ema=None):
+        o = self.sample_opts
+        kw = {}
+        if o["sampler"] != "ddpm" or o["guidance_scale"] is not None:        # (else: the call below is exactly what it was)
+            kw = dict(o, null_text=self.null_text(text_emb.shape[1]) if o["guidance_scale"] is not None else None)
         with self._ema_ctx(use_ema):
-            return self.stepper.sample(text_emb, num_samples, fast_sampling, noise_fn, latent_dim=self.config["model"].get("latent_dim", 8))
+            return self.stepper.sample(text_emb, num_samples, fast_sampling, noise_fn, latent_dim=self.config["model"].get("latent_dim", 8), **kw)
 
     def ddpm_sample(self, text_emb: torch.Tensor, num_samples: int, fast_sampling: bool = True, use_ema=None) -> torch.Tensor:
         return self.sample(text_emb, num_samples, fast_sampling, use_ema=use_ema)
@@ -836,6 +931,8 @@ class ImprovedDiffusionTrainer(TrainerBase):
                     rec = self.stepper.autotune_exchange(latent, text_emb, t)
                     if rec is not None and self.is_main:
                         self.logger.info(f"gradient exchange mode: {rec['chosen']} ({rec['ms_per_step']})")
+                if self.cond_drop_prob and "input_ids" in batch:      # (fills the cache; an encoder without tokenizer reads its special ids here)
+                    self.null_text(text_emb.shape[1], like=(batch["input_ids"], batch["attention_mask"]))
                 out = self.train_step(latent, text_emb, t, pre_flag=pre)
                 flag = out["nan_flag"]
                 good = (flag & FLAG_SKIP_MASK) == 0
@@ -924,6 +1021,8 @@ class ImprovedDiffusionTrainer(TrainerBase):
         ckpt = {"epoch": epoch, "global_step": self.global_step, "unet_state_dict": self.unet.state_dict(),
                 "optimizer_state_dict": self.optimizer.state_dict(), "scheduler_state_dict": self.scheduler.state_dict(),
                 "best_val_loss": self.best_val_loss, "config": self.config}
+        if self.cond_drop_prob:                    # tells a loader that guidance means something on these weights
+            ckpt["cond_drop_prob"] = self.cond_drop_prob
         if self.stepper.ema_enabled:               # next to the reference's keys, none of which changes
             ckpt["ema_unet_state_dict"], ckpt["ema_decay"] = self.stepper.ema_state_dict(), self.ema_decay
         if is_best:
