@@ -49,6 +49,9 @@ enum psg_status {
 enum psg_dtype { PSG_F32 = 0, PSG_BF16 = 1 };
 enum psg_act { PSG_ACT_NONE = 0, PSG_ACT_SILU = 1, PSG_ACT_GELU = 2, PSG_ACT_RELU = 3, PSG_ACT_TANH = 4,   /* RELU / TANH: the frozen VAE (vae_decoder.py:82-91,185) */
                PSG_ACT_QUICK_GELU = 5 };   /* x * sigmoid(1.702 x): both CLIP towers (transformers' `quick_gelu`, clip_loss.py:22); any other value is PSG_ERR_ARG */
+/* What the U-Net's output means (opt-in v-prediction; every entry without this argument is eps-prediction):
+ * PSG_PRED_EPS the noise, PSG_PRED_V  v = sqrt(abar_t) eps - sqrt(1 - abar_t) x0. */
+enum psg_prediction { PSG_PRED_EPS = 0, PSG_PRED_V = 1 };
 /* Bits of the device-side NaN/Inf flag word of one train step (the reference's five host-side
  * check_for_nans scans, improved_diffusion_trainer.py:353-393).  A step whose word has any bit of
  * PSG_FLAG_SKIP_MASK set is skipped like the reference's `continue`: no optimizer step, no scheduler
@@ -141,6 +144,26 @@ int psg_cfg_combine_f32(const float* eps_c, const float* eps_u, float w, float* 
  * otherwise.  clip < 0, k < 1, or a null x, eps_c, tab or step_dev is PSG_ERR_ARG; n <= 0 is PSG_OK with nothing launched. */
 int psg_guided_update_f32(float* x, float* x_copy, const float* eps_c, const float* eps_u, const float* z, const float* tab, int k,
                           const int32_t* step_dev, float w, float clip, int64_t n, psg_stream_t stream);
+/* psg_guided_update_f32 for a network that predicts `prediction` (enum psg_prediction), same table, x_copy, vector rule and
+ * refusals; a prediction outside the enum is PSG_ERR_ARG.  PSG_PRED_EPS gives psg_guided_update_f32's bits.  PSG_PRED_V:
+ *   p  = pred_c                                  when pred_u == NULL
+ *   p  = pred_u + w * (pred_c - pred_u)          otherwise
+ *   x0 = S0[j] * x - S1[j] * p                   (two rounded products, one rounded subtraction; no division)
+ *   e  = S1[j] * x + S0[j] * p
+ * and from there the clamp, the eps recompute where it acts and x' exactly as above. */
+int psg_guided_update_pred_f32(float* x, float* x_copy, const float* pred_c, const float* pred_u, const float* z, const float* tab, int k,
+                               const int32_t* step_dev, float w, float clip, int64_t n, int prediction, psg_stream_t stream);
+/* The guided prediction as eps, for the chains that keep their own update (psg_ddpm_update_f32, psg_sampler_update_f32); under
+ * guidance it takes psg_cfg_combine_f32's place, so those chains gain no launch:
+ *   p   = pred_c, or pred_u + w * (pred_c - pred_u) when pred_u != NULL        (psg_cfg_combine_f32's three roundings)
+ *   out = p                                      PSG_PRED_EPS (x, tabA, tabB are not read and may be NULL)
+ *   out = tabB[t] * x + tabA[t] * p              PSG_PRED_V, tabA = sqrt(abar), tabB = sqrt(1 - abar): the tables of psg_noise_add_f32
+ * t = *t_dev (int32 device scalar, read on the device: graph-replayable; outside 0..num_t-1 it reads the nearest entry).
+ * out may alias pred_c.  16-byte accesses when n is a multiple of 4 and every pointer read or written is 16-byte aligned.
+ * A prediction outside the enum, a null pred_c, out or t_dev, or PSG_PRED_V with a null x, tabA or tabB is PSG_ERR_ARG;
+ * num_t <= 0 is PSG_ERR_SHAPE; n <= 0 is PSG_OK with nothing launched, as is PSG_PRED_EPS without pred_u and out == pred_c. */
+int psg_pred_to_eps_f32(const float* x, const float* pred_c, const float* pred_u, float w, const float* tabA, const float* tabB, int num_t,
+                        const int32_t* t_dev, int prediction, float* out, int64_t n, psg_stream_t stream);
 
 /* VAE reparameterisation, src/models/vae_decoder.py:120-123: out = mu + eps * exp(0.5 * logvar) (fp32, separately rounded).
  * n <= 0 is PSG_OK with nothing launched; a null pointer is PSG_ERR_ARG. */
@@ -161,6 +184,27 @@ int psg_smooth_l1_f32(const float* pred, const float* target, float* grad, float
                       int32_t* nan_flag, float beta, float grad_scale, int64_t n, void* ws,
                       psg_stream_t stream);
 int64_t psg_reduce_workspace_bytes(void);
+/* The diffusion loss with its target built in registers and a per-timestep weight (opt-in: v-prediction, Min-SNR), one
+ * fused launch in psg_smooth_l1_f32's place.  pred, noise, x0 [B, chw] fp32, t [B] int64, tabA / tabB / wtab [num_t] fp32
+ * (tabA = sqrt(abar), tabB = sqrt(1 - abar), psg_noise_add_f32's tables).  For element i of sample b, tt = t[b] clamped to
+ * 0..num_t-1:
+ *   target = noise                                         PSG_PRED_EPS (x0, tabA, tabB are not read and may be NULL)
+ *   target = tabA[tt] * noise - tabB[tt] * clamp?(x0)      PSG_PRED_V: two rounded products, one rounded subtraction;
+ *                                                          do_clamp is psg_noise_add_f32's clamp to +-3 (NaN kept)
+ *   w      = wtab ? wtab[tt] : 1
+ *   loss   = (1 / n) sum_i w * smoothl1_beta(pred - target),  n = B * chw   (a mean over all elements, not divided by sum w)
+ *   grad   (may be NULL) = w * smoothl1'(pred - target) / n * grad_scale
+ *   target_out (may be NULL) = target
+ * Deterministic two-stage reduction in a fixed order; ws: >= psg_reduce_workspace_bytes() bytes.  *nan_flag (may be NULL; never
+ * cleared here) is OR-ed with PSG_FLAG_PRED_BAD if any pred is NaN/Inf, with PSG_FLAG_LOSS_BAD if the loss is, and with
+ * PSG_FLAG_T_RANGE if any t[b] is outside the tables.  16-byte loads and stores when chw is a multiple of 4 and every pointer
+ * given among pred, noise, x0 (PSG_PRED_V), grad and target_out is 16-byte aligned; element by element otherwise.
+ * B < 0, chw <= 0, num_t <= 0 or beta <= 0 is PSG_ERR_SHAPE; a prediction outside the enum, a null pred, noise, t, loss_out or
+ * ws, or PSG_PRED_V with a null x0, tabA or tabB is PSG_ERR_ARG; B == 0 is PSG_OK with nothing launched. */
+int psg_diffusion_loss_f32(const float* pred, const float* x0, const float* noise, const int64_t* t, const float* tabA,
+                           const float* tabB, const float* wtab, int prediction, float* grad, float* target_out, float* loss_out,
+                           int32_t* nan_flag, float beta, float grad_scale, int64_t B, int64_t chw, int num_t, int do_clamp, void* ws,
+                           psg_stream_t stream);
 
 /* Stage 3's reconstruction loss and its gradient in one pass - compute_generation_loss, final_trainer.py:425-440
  * (F.l1_loss + 0.1 * F.mse_loss, both means over all n elements):

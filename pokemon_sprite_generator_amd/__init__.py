@@ -14,6 +14,7 @@ from .ddp import BucketedAllReduce
 from .trainer import DiffusionStepper, DiffusionTrainer, ImprovedDiffusionTrainer
 from .inference import LatentGenerator, LinearNoiseScheduler, gradio_ddpm_sample, load_unet_state
 from .guidance import DdimRun, cfg_combine, ddim_sample, ddim_tables, ddim_timesteps, text_cond_drop
+from .objective import diffusion_loss, min_snr_weights, pred_to_eps, v_target
 from .vae import PokemonVAE, VAEDecoder, VAEEncoder
 from .text_encoder import TextEncoder
 from .losses import CombinedLoss, VGGPerceptualLoss
@@ -29,5 +30,6 @@ __all__ = ["UNet", "UNetBlock", "ResBlock", "CrossAttentionBlock", "TimestepEmbe
            "ImprovedDiffusionTrainer", "DiffusionTrainer", "DiffusionStepper", "FusedAdamW", "GradArena", "ParamArena",
            "BucketedAllReduce", "LatentGenerator", "LinearNoiseScheduler", "gradio_ddpm_sample", "load_unet_state", "PokemonVAE", "VAEEncoder", "VAEDecoder", "TextEncoder", "VGGPerceptualLoss", "CombinedLoss", "CLIPLoss",
            "FinalPokemonGenerator", "FinalStepper", "GroupedAdamW", "VAEStepper", "SpriteDataset", "SpriteLoader", "create_data_loaders", "draw_params", "SpriteGenerator", "VAETrainer", "FinalTrainer", "TokenTable", "PsgError", "LIB_PATH",
-           "DdimRun", "ddim_sample", "ddim_tables", "ddim_timesteps", "cfg_combine", "text_cond_drop"]
+           "DdimRun", "ddim_sample", "ddim_tables", "ddim_timesteps", "cfg_combine", "text_cond_drop",
+           "diffusion_loss", "min_snr_weights", "pred_to_eps", "v_target"]
 __version__ = "0.1.0"

@@ -1,6 +1,7 @@
 // HBM-bound elementwise / reduction kernels of the U-Net train step (gfx950).
 // Every kernel is a single streaming pass; roofline = HBM bandwidth.
 #include "psg_common.h"
+#include "guided_step.h"
 
 namespace psg {
 
@@ -147,23 +148,8 @@ __global__ void cfg_combine_kernel(const float* eps_c, const float* __restrict__
     }
 }
 
-// One DDIM step of one element (the formula of psg_guided_update_f32 in psg_hip.h).  The clamp lets NaN through (both
-// comparisons are false), as numpy.clip; `c != x0` is then true and e becomes NaN with it.
-struct GuidedCoef { float s0, s1, p0, p1, sg; };
-__device__ __forceinline__ float guided_elem(float x, float ec, float eu, bool has_u, float w, const GuidedCoef& k, float clip,
-                                             float z, bool has_z) {
-    float e = ec;
-    if (has_u) e = __fadd_rn(eu, __fmul_rn(w, __fsub_rn(ec, eu)));
-    float x0 = __fdiv_rn(__fsub_rn(x, __fmul_rn(k.s1, e)), k.s0);
-    if (clip > 0.f) {
-        const float c = x0 < -clip ? -clip : (x0 > clip ? clip : x0);
-        if (c != x0) e = __fdiv_rn(__fsub_rn(x, __fmul_rn(k.s0, c)), k.s1);
-        x0 = c;
-    }
-    float r = __fadd_rn(__fmul_rn(k.p0, x0), __fmul_rn(k.p1, e));
-    if (has_z) r = __fadd_rn(r, __fmul_rn(k.sg, z));
-    return r;
-}
+// One DDIM step of one element (the formula of psg_guided_update_f32 in psg_hip.h): GuidedCoef and guided_elem live in
+// guided_step.h, which objective.hip shares.
 
 // n counts float4s when VEC.  x_copy (may be NULL) receives the same values as x: the unconditional half of a 2n input.
 template <bool VEC>

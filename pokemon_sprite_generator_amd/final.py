@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import PsgError
-from .inference import LatentGenerator, LinearNoiseScheduler, load_unet_state
+from .inference import LatentGenerator, LinearNoiseScheduler, load_unet_checkpoint, refuse_v_prediction
 from .ops import WeightCache
 from .optim import GradArena, GroupedAdamW, ParamArena
 from .text_encoder import TextEncoder
@@ -61,10 +61,12 @@ class FinalPokemonGenerator(nn.Module):
         """:90-160 - 'vae_state_dict' split into its encoder. / decoder. halves, 'unet_state_dict', and the stage-1
         checkpoint's optional 'text_encoder_state_dict'.  `trainable_decoder`: build the decoder with `trainable=True`, which
         the joint phase needs (it starts frozen either way).  `use_ema`: the U-Net takes the checkpoint's 'ema_unet_state_dict'
-        (inference.load_unet_state; an error if it has none)."""
+        (inference.load_unet_state; an error if it has none).  A checkpoint trained with training.prediction_type =
+        "v_prediction" is refused: this class samples with stage 3's eps-only loop."""
         cfg = text_encoder_config
         latent_dim, text_dim = cfg.get("latent_dim", 8), cfg["text_embedding_dim"]
-        unet_state = load_unet_state(diffusion_path, use_ema=use_ema)        # (first: refused before anything is built)
+        unet_state, prediction = load_unet_checkpoint(diffusion_path, use_ema=use_ema)        # (first: refused before anything is built)
+        refuse_v_prediction(prediction, f"FinalPokemonGenerator.from_checkpoints({diffusion_path})")
         vae_ckpt = torch.load(vae_path, map_location="cpu")
         enc = VAEEncoder(input_channels=3, latent_dim=latent_dim, compute_dtype=compute_dtype)
         dec = VAEDecoder(latent_dim=latent_dim, text_dim=text_dim, output_channels=3, compute_dtype=compute_dtype,

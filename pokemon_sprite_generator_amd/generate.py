@@ -16,7 +16,8 @@ import torch
 from . import imaging
 from ._lib import PsgError
 from .guidance import ddim_sample, encode_null_text
-from .inference import gradio_ddpm_sample, load_unet_state
+from .inference import gradio_ddpm_sample, load_unet_checkpoint
+from .objective import prediction_name
 from .text_encoder import TextEncoder
 from .unet import UNet
 from .vae import PokemonVAE
@@ -29,8 +30,9 @@ class SpriteGenerator:
     `unet(latent, timesteps, text_emb)`), a `TextEncoder` and the linear schedule's constants (gradio_app.py:241-247)."""
 
     def __init__(self, vae: PokemonVAE, unet: torch.nn.Module, text_encoder: TextEncoder, num_timesteps: int = 1000,
-                 beta_start: float = 0.0001, beta_end: float = 0.02, image_size: int = 215):
+                 beta_start: float = 0.0001, beta_end: float = 0.02, image_size: int = 215, prediction=None):
         self.vae, self.unet, self.text_encoder = vae.eval(), unet.eval(), text_encoder.eval()       # :237-239
+        self.prediction_type = prediction_name(prediction)      # what the U-Net returns ("epsilon" / "v_prediction"): both samplers take it
         self.num_timesteps, self.beta_start, self.beta_end = int(num_timesteps), float(beta_start), float(beta_end)
         self.image_size = int(image_size)
         self.latent_dim = vae.latent_dim
@@ -41,10 +43,12 @@ class SpriteGenerator:
         """:186-277 with the custom U-Net - `config` is the reference's config dict (its 'model' section is read; a flat dict
         of those keys is taken as that section).  'vae_state_dict', 'unet_state_dict' and the stage-1 checkpoint's optional
         'text_encoder_state_dict', as `FinalPokemonGenerator.from_checkpoints` reads them.  device=None: the current GPU.
-        `use_ema`: the U-Net takes the checkpoint's 'ema_unet_state_dict' (inference.load_unet_state; an error if it has none)."""
+        `use_ema`: the U-Net takes the checkpoint's 'ema_unet_state_dict' (inference.load_unet_state; an error if it has none).
+        The checkpoint's 'prediction_type' (written by a trainer with training.prediction_type = "v_prediction") decides how the
+        samplers read the U-Net's output."""
         cfg = config.get("model", config)
         latent_dim, text_dim = cfg.get("latent_dim", 8), cfg.get("text_embedding_dim", 768)
-        unet_state = load_unet_state(diffusion_path, use_ema=use_ema)        # (first: refused before anything is built)
+        unet_state, prediction = load_unet_checkpoint(diffusion_path, use_ema=use_ema)        # (first: refused before anything is built)
         vae_ckpt = torch.load(vae_path, map_location="cpu")
         vae = PokemonVAE(latent_dim=latent_dim, text_dim=text_dim, compute_dtype=compute_dtype)
         vae.load_state_dict(vae_ckpt["vae_state_dict"])
@@ -60,7 +64,7 @@ class SpriteGenerator:
                 raise PsgError("SpriteGenerator.from_checkpoints needs a GPU: the HIP kernels are the only implementation")
             device = torch.device("cuda", torch.cuda.current_device())
         return cls(vae.to(device), unet.to(device), te.to(device), num_timesteps=cfg.get("num_timesteps", 1000),
-                   beta_start=cfg.get("beta_start", 0.0001), beta_end=cfg.get("beta_end", 0.02))
+                   beta_start=cfg.get("beta_start", 0.0001), beta_end=cfg.get("beta_end", 0.02), prediction=prediction)
 
     # -- helpers ---------------------------------------------------------------------------------------------------------
     def _device(self):
@@ -84,6 +88,8 @@ class SpriteGenerator:
         null = self._null_text(descriptions, text_emb.shape[1]) if guidance_scale is not None else None
         if sampler == "gradio":
             kw = {} if guidance_scale is None else {"guidance_scale": guidance_scale, "null_text": null}
+            if self.prediction_type != "epsilon":
+                kw["prediction"] = self.prediction_type
             return gradio_ddpm_sample(self.unet, text_emb, num_inference_steps, initial_latent=initial_latent,
                                       num_timesteps=self.num_timesteps, beta_start=self.beta_start, beta_end=self.beta_end,
                                       latent_dim=self.latent_dim, noise_fn=noise_fn, **kw)
@@ -91,7 +97,7 @@ class SpriteGenerator:
             raise PsgError(f"sampler={sampler!r} (\"gradio\" or \"ddim\")")
         betas = torch.linspace(self.beta_start, self.beta_end, self.num_timesteps)        # the demo's linear schedule (:279-288)
         return ddim_sample(self.unet, text_emb, torch.cumprod(1.0 - betas, dim=0), num_inference_steps, eta, guidance_scale, null, clip,
-                           initial_latent, noise_fn, latent_dim=self.latent_dim)
+                           initial_latent, noise_fn, latent_dim=self.latent_dim, prediction=self.prediction_type)
 
     @staticmethod
     def _seed(seed):

@@ -4,7 +4,8 @@ opt-in, and without them every launch of the step and of the existing samplers i
   * `ddim_timesteps`, `ddim_tables` - the host side of the schedule: k strictly descending timesteps and the [5, k] fp32
     table `psg_guided_update_f32` reads (fp64 arithmetic on the fp32 `alphas_cumprod`, rounded once).  Schedule-agnostic.
   * `text_cond_drop`, `cfg_combine` - the two small launches: the per-sample text drop of training and
-    eps_u + w (eps_c - eps_u) for the chains that keep their own reference update.
+    eps_u + w (eps_c - eps_u) for the chains that keep their own reference update (a v-predicting network goes through
+    objective.pred_to_eps instead, one launch as well).
   * `DdimRun` / `ddim_sample` - the chain.  Guided, ONE U-Net forward runs at batch 2n on [x; x] with the text
     [text; null_text], and ONE launch combines the two halves of its output, takes the DDIM step in place on the first half of
     the input and writes the same values to the second half; nothing is copied or concatenated between steps.
@@ -21,6 +22,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
+from .objective import PRED_EPS, pred_to_eps, prediction_code
 
 
 def _lib_for(t):
@@ -137,11 +139,15 @@ def encode_null_text(text_encoder, S: int, like=None) -> torch.Tensor:
     return null
 
 
-def guided_eps(unet, xin, tv, text2, w, n):
+def guided_eps(unet, xin, tv, text2, w, n, prediction=None, tables=None, t_dev=None):
     """The 2n forward and the combine, for the chains that keep their own update: xin [2n, ...] whose second half the caller
-    keeps equal to the first; returns eps [n, ...] (a view of the forward's output, overwritten in place)."""
+    keeps equal to the first; returns eps [n, ...] (a view of the forward's output, overwritten in place).  A v-predicting
+    network (`prediction`) needs `tables` (a NoiseScheduler or the pair of sqrt tables) and `t_dev` (the timestep, int32 on the
+    device): psg_pred_to_eps_f32 then stands where psg_cfg_combine_f32 stood."""
     out = unet(xin, tv, text2).detach().contiguous().float()
-    return cfg_combine(out[:n], out[n:], w, out=out[:n])
+    if prediction_code(prediction) == PRED_EPS:
+        return cfg_combine(out[:n], out[n:], w, out=out[:n])
+    return pred_to_eps(xin[:n], out[:n], out[n:], w, tables, t_dev, prediction, out=out[:n])
 
 
 # ------------------------------------------------------------------------------------------------------------- the chain
@@ -157,8 +163,9 @@ class DdimRun:
 
     @torch.no_grad()
     def __init__(self, unet, text_emb, alphas_cumprod, num_steps=50, eta=0.0, guidance_scale=None, null_text=None, clip=3.0,
-                 initial_latent=None, noise_fn=None, use_graph=None, latent_dim=8, hw=27):
+                 initial_latent=None, noise_fn=None, use_graph=None, latent_dim=8, hw=27, prediction=None):
         self.unet = unet
+        self.prediction = prediction_code(prediction)
         unet.eval()
         dev = next(unet.parameters()).device
         self.dev = dev
@@ -229,9 +236,14 @@ class DdimRun:
             out = out.float()
         n = self.n
         eps_c, eps_u = (out[:n], out[n:]) if self.guided else (out, None)
-        check(self.lib.psg_guided_update_f32(ptr(self.x), ptr(self.x_copy), ptr(eps_c), ptr(eps_u), ptr(self.z if with_z else None),
-                                             ptr(self.tab), self.k, ptr(self.step_dev), self.w, self.clip, self.x.numel(),
-                                             stream_ptr()), "psg_guided_update_f32")
+        if self.prediction == PRED_EPS:
+            check(self.lib.psg_guided_update_f32(ptr(self.x), ptr(self.x_copy), ptr(eps_c), ptr(eps_u), ptr(self.z if with_z else None),
+                                                 ptr(self.tab), self.k, ptr(self.step_dev), self.w, self.clip, self.x.numel(),
+                                                 stream_ptr()), "psg_guided_update_f32")
+        else:                                        # a v-predicting network: x0 = S0 x - S1 v, no division
+            check(self.lib.psg_guided_update_pred_f32(ptr(self.x), ptr(self.x_copy), ptr(eps_c), ptr(eps_u), ptr(self.z if with_z else None),
+                                                      ptr(self.tab), self.k, ptr(self.step_dev), self.w, self.clip, self.x.numel(),
+                                                      self.prediction, stream_ptr()), "psg_guided_update_pred_f32")
 
     @torch.no_grad()
     def step(self):
@@ -285,10 +297,12 @@ class DdimRun:
 
 @torch.no_grad()
 def ddim_sample(unet, text_emb, alphas_cumprod, num_steps=50, eta=0.0, guidance_scale=None, null_text=None, clip=3.0,
-                initial_latent=None, noise_fn=None, trace=None, use_graph=None, latent_dim=8, hw=27) -> torch.Tensor:
+                initial_latent=None, noise_fn=None, trace=None, use_graph=None, latent_dim=8, hw=27, prediction=None) -> torch.Tensor:
     """DDIM chain of `num_steps` U-Net forwards over `alphas_cumprod` (any schedule), optionally guided.
 
     unet: any module with parameters on the device, called as unet(x, t, text) -> eps.  text_emb [n, S, text_dim].
+    prediction: what the network returns - "epsilon" (default) or "v_prediction" (objective.py): guidance then combines the
+      two v, and the step takes x0 = S0 x - S1 v, eps = S1 x + S0 v before the same clamp and update.
     eta: 0 the deterministic chain, 1 the posterior-variance noise of DDPM on consecutive timesteps.
     guidance_scale: None runs at batch n; a float w runs one forward at batch 2n with [text; null_text] and steps with
       eps_u + w (eps_c - eps_u); it needs null_text ([S, text_dim]).
@@ -296,7 +310,7 @@ def ddim_sample(unet, text_emb, alphas_cumprod, num_steps=50, eta=0.0, guidance_
     noise_fn(i, shape): i = -1 is x_T (unless initial_latent is given), i >= 0 the i-th z; z is drawn only when eta > 0
       and not on the last step.  trace: a list that receives a copy of the latent after every step."""
     run = DdimRun(unet, text_emb, alphas_cumprod, num_steps, eta, guidance_scale, null_text, clip, initial_latent, noise_fn,
-                  use_graph, latent_dim, hw)
+                  use_graph, latent_dim, hw, prediction)
     while run.remaining():
         run.step()
         if trace is not None:

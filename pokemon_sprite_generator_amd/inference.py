@@ -23,6 +23,7 @@ import torch
 from . import _lib
 from ._lib import check, ptr, stream_ptr
 from .guidance import expand_null_text, guided_eps
+from .objective import EPSILON, PRED_EPS, pred_to_eps, prediction_code, prediction_name
 
 
 def _lib_for(t):
@@ -35,13 +36,34 @@ def load_unet_state(checkpoint, use_ema: bool = False, map_location="cpu"):
     """The U-Net weights of a stage-2 checkpoint (a path, or the loaded dict): 'unet_state_dict' - or, with `use_ema`, the
     averaged weights 'ema_unet_state_dict' that a trainer with `training.ema_decay` writes next to it (same keys and shapes).
     Asking for the EMA of a checkpoint that has none is an error, never a silent fall-back to the raw weights."""
+    return load_unet_checkpoint(checkpoint, use_ema, map_location)[0]
+
+
+def checkpoint_prediction_type(ckpt) -> str:
+    """What the U-Net of a loaded stage-2 checkpoint predicts: its 'prediction_type' key, which a trainer writes only when it
+    is not "epsilon" (training.prediction_type)."""
+    return prediction_name(ckpt.get("prediction_type") or EPSILON)
+
+
+def load_unet_checkpoint(checkpoint, use_ema: bool = False, map_location="cpu"):
+    """(load_unet_state's weights, checkpoint_prediction_type) from one read of the file."""
     ckpt = checkpoint if isinstance(checkpoint, dict) else torch.load(checkpoint, map_location=map_location)
+    pred = checkpoint_prediction_type(ckpt)
     if not use_ema:
-        return ckpt["unet_state_dict"]
+        return ckpt["unet_state_dict"], pred
     if "ema_unet_state_dict" not in ckpt:
         where = "the checkpoint" if isinstance(checkpoint, dict) else str(checkpoint)
         raise _lib.PsgError(f"use_ema=True, but {where} has no 'ema_unet_state_dict' (it was trained without training.ema_decay)")
-    return ckpt["ema_unet_state_dict"]
+    return ckpt["ema_unet_state_dict"], pred
+
+
+def refuse_v_prediction(prediction, who: str):
+    """Stage 3's sampler subtracts the U-Net's output as noise (final_trainer.py:186-204); on a v-predicting U-Net that is
+    garbage, so it is refused."""
+    if prediction_code(prediction) != PRED_EPS:
+        raise _lib.PsgError(f"{who}: the U-Net was trained with prediction_type={prediction_name(prediction)!r}; stage 3's sampler reads its "
+                            "output as eps and has no v-prediction form (use DiffusionStepper.sample, ddim_sample or gradio_ddpm_sample "
+                            "with prediction=)")
 
 
 def _f32(v):
@@ -122,7 +144,8 @@ class LatentGenerator:
     `pokemon_sprite_generator_amd.UNet` (weights: a stage-2 checkpoint's 'unet_state_dict', loaded as is)."""
 
     def __init__(self, unet, noise_scheduler: Optional[LinearNoiseScheduler] = None, latent_dim: int = 8,
-                 vae_decoder: Optional[Callable] = None):
+                 vae_decoder: Optional[Callable] = None, prediction=None):
+        refuse_v_prediction(prediction, "LatentGenerator")       # (`prediction`: the checkpoint's type; only eps is sampled here)
         self.unet, self.latent_dim, self.vae_decoder = unet, latent_dim, vae_decoder
         self.noise_scheduler = noise_scheduler or LinearNoiseScheduler()
 
@@ -158,15 +181,22 @@ class LatentGenerator:
 @torch.no_grad()
 def gradio_ddpm_sample(unet, text_emb: torch.Tensor, num_inference_steps: int = 50, initial_latent: Optional[torch.Tensor] = None,
                        num_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02, latent_dim: int = 8,
-                       noise_fn=None, trace=None, guidance_scale=None, null_text=None) -> torch.Tensor:
+                       noise_fn=None, trace=None, guidance_scale=None, null_text=None, prediction=None) -> torch.Tensor:
     """PokemonGradioGenerator.ddpm_sample (gradio_app.py:297-361) with its own linear schedule (:279-288).
     Opt-in: `guidance_scale` with `null_text` [S, text_dim] runs each forward at batch 2n on [x; x] with [text; null_text] and
-    feeds eps_u + w (eps_c - eps_u) (psg_cfg_combine_f32) to the same update."""
+    feeds eps_u + w (eps_c - eps_u) (psg_cfg_combine_f32) to the same update.  prediction="v_prediction": the U-Net returns v;
+    one psg_pred_to_eps_f32 launch (the guidance combine included) turns it into eps = sqrt(1 - abar_t) x + sqrt(abar_t) v, with
+    the square roots of this schedule rounded once from fp64, and the same update follows."""
     unet.eval()
     dev = next(unet.parameters()).device
     betas = torch.linspace(beta_start, beta_end, num_timesteps)
     alphas = 1.0 - betas
     alphas_cumprod = torch.cumprod(alphas, dim=0)
+    pred = prediction_code(prediction)
+    if pred != PRED_EPS:
+        ac64 = alphas_cumprod.double()
+        tabs = (torch.sqrt(ac64).float().to(dev).contiguous(), torch.sqrt(1.0 - ac64).float().to(dev).contiguous())
+        t_dev = torch.zeros(1, dtype=torch.int32, device=dev)
     text_emb = text_emb.to(dev)
     B = text_emb.shape[0]
     rnd = noise_fn if noise_fn is not None else (lambda i, shape: torch.randn(shape, device=dev))
@@ -185,7 +215,15 @@ def gradio_ddpm_sample(unet, text_emb: torch.Tensor, num_inference_steps: int = 
     draws = 0
     for i, t in enumerate(timesteps):
         tv = torch.full((2 * B if guided else B,), t.item(), dtype=torch.long, device=dev)
-        eps = guided_eps(unet, xin, tv, text2, float(guidance_scale), B) if guided else unet(latent, tv, text_emb)
+        if pred == PRED_EPS:
+            eps = guided_eps(unet, xin, tv, text2, float(guidance_scale), B) if guided else unet(latent, tv, text_emb)
+        else:
+            t_dev.fill_(int(t))
+            if guided:
+                eps = guided_eps(unet, xin, tv, text2, float(guidance_scale), B, pred, tabs, t_dev)
+            else:
+                v = unet(latent, tv, text_emb).detach().contiguous().float()
+                eps = pred_to_eps(latent, v, None, 0.0, tabs, t_dev, pred, out=v)
         one = np.float32(1.0)                                   # fp32 scalar arithmetic, as the reference's 0-d tensors
         a_t, ac_t = _f32(alphas[t]), _f32(alphas_cumprod[t])
         k0 = float((one - a_t) / _sqrt32(one - ac_t))

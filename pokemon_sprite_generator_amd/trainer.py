@@ -35,6 +35,7 @@ from . import _lib
 from . import ops as ops_mod
 from ._lib import FLAG_INPUT_BAD, FLAG_LOSS_BAD, FLAG_NOISY_BAD, FLAG_PRED_BAD, FLAG_SKIP_MASK, FLAG_T_RANGE, check, ptr, stream_ptr
 from .guidance import DdimRun, encode_null_text, expand_null_text, guided_eps, text_cond_drop
+from .objective import EPSILON, PRED_EPS, diffusion_loss, min_snr_weights, pred_to_eps, prediction_code, prediction_name
 from .ddp import BucketedAllReduce, ShardedLoader, dist_info, rank_generator
 from .optim import FusedAdamW, GradArena, ParamArena
 from .scheduler import NoiseScheduler
@@ -66,8 +67,17 @@ class DiffusionStepper:
 
     def __init__(self, unet: UNet, noise_scheduler: NoiseScheduler, lr=1e-4, betas=(0.9, 0.999), weight_decay=0.01,
                  eps=1e-6, max_grad_norm=1.0, optimizer_type="adamw", distributed=None, bucket_bytes=64 << 20,
-                 grad_bucket_dtype=torch.float32, ddp_cu_reserve=None, ema_decay=None, ema_warmup=True, cond_drop_prob=None):
+                 grad_bucket_dtype=torch.float32, ddp_cu_reserve=None, ema_decay=None, ema_warmup=True, cond_drop_prob=None,
+                 prediction_type=EPSILON, min_snr_gamma=None):
         self.unet, self.noise_scheduler = unet, noise_scheduler
+        # the objective (opt-in, objective.py; the defaults make exactly the psg_smooth_l1_f32 call of the reference's loss):
+        # what the U-Net regresses - "epsilon" or "v_prediction" - and the Min-SNR-gamma weight of each timestep
+        self.prediction_type = prediction_name(prediction_type)
+        self.prediction = prediction_code(prediction_type)
+        self.min_snr_gamma = float(min_snr_gamma) if min_snr_gamma is not None else None
+        if self.min_snr_gamma is not None and not self.min_snr_gamma > 0:
+            raise ValueError(f"min_snr_gamma={min_snr_gamma} must be > 0 (None: uniform weights)")
+        self.loss_weights = None                   # [T] fp32 on the device, read by the loss kernel at t[b]
         # classifier-free guidance training (opt-in; None or 0: nothing is launched and no seed is drawn): each sample's text is
         # replaced by the null text with this probability before the U-Net (psg_text_cond_drop_f32)
         if cond_drop_prob is not None and not 0.0 <= float(cond_drop_prob) < 1.0:
@@ -115,6 +125,8 @@ class DiffusionStepper:
                                          cu_reserve=ddp_cu_reserve) if distributed else None
         if hasattr(unet, "bind_proj_group"):
             unet.bind_proj_group(self.params, self.arena)       # (after enable_shadow: the group's bf16 operand is a run of it)
+        if self.min_snr_gamma is not None:
+            self.loss_weights = min_snr_weights(noise_scheduler.alphas_cumprod, self.min_snr_gamma, self.prediction).to(self.device).contiguous()
         self.flag = torch.zeros(1, dtype=torch.int32, device=self.device)      # bits: enum psg_flag (include/psg_hip.h)
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.criterion_beta = 0.1                                               # nn.SmoothL1Loss(beta=0.1) :300
@@ -206,6 +218,19 @@ class DiffusionStepper:
                                          pred_c.numel(), ptr(ws), stream_ptr()), "psg_smooth_l1_f32")
         return self.loss, grad
 
+    @property
+    def objective_enabled(self) -> bool:
+        return self.prediction != PRED_EPS or self.loss_weights is not None
+
+    def objective_loss(self, pred, latents, noise, t, want_grad=True):
+        """The step's loss and dL/dpred: psg_smooth_l1_f32 against the noise (today's call) unless v-prediction or Min-SNR is on;
+        then ONE psg_diffusion_loss_f32 launch, which builds the target from the UN-clamped latents, the noise and t - the
+        same clamp and tables as add_noise - and reads the weight at t[b].  No launch and no tensor more than today's."""
+        if not self.objective_enabled:
+            return self.smooth_l1(pred, noise, want_grad)
+        return diffusion_loss(pred, latents, noise, t, self.noise_scheduler, self.prediction, self.loss_weights, self.criterion_beta,
+                              clamp=True, want_grad=want_grad, flag=self.flag, loss_out=self.loss)
+
     def _reduce_flag(self):
         """All ranks must skip together: if ANY rank has a skip bit, every rank ends up with a non-zero skip field
         (RCCL has no bitwise-OR reduction: MAX of the masked field keeps 'non-zero'; the local informational bits stay)."""
@@ -245,7 +270,7 @@ class DiffusionStepper:
         noisy = self.noise_scheduler.add_noise(latents, noise, t, clamp=True, flag=self.flag)     # :363, :374
         self.arena.zero()                                                                           # :380
         eps_hat = self.unet(noisy, t, text_emb)                                                     # :381
-        loss, dpred = self.smooth_l1(eps_hat, noise)                                                # :388
+        loss, dpred = self.objective_loss(eps_hat, latents, noise, t)                               # :388
         eps_hat.backward(dpred)                                                                     # :396
         self.arena.finalize()                      # (joins the weight-gradient side stream)
         if self.reducer is not None:
@@ -327,7 +352,7 @@ class DiffusionStepper:
         self.flag.zero_()
         noisy = self.noise_scheduler.add_noise(latents, noise, t, clamp=True, flag=self.flag)
         eps_hat = self.unet(noisy, t, text_emb)
-        loss, _ = self.smooth_l1(eps_hat, noise, want_grad=False)
+        loss, _ = self.objective_loss(eps_hat, latents, noise, t, want_grad=False)       # the objective and weights of training
         return loss.clone(), self.flag.clone()
 
     @staticmethod
@@ -340,16 +365,19 @@ class DiffusionStepper:
 
     @torch.no_grad()
     def sample(self, text_emb, num_samples, fast_sampling=True, noise_fn=None, latent_dim=8, hw=27, trace=None, use_graph=None,
-               max_steps=None, sampler="ddpm", num_steps=None, eta=0.0, guidance_scale=None, null_text=None, clip=3.0):
+               max_steps=None, sampler="ddpm", num_steps=None, eta=0.0, guidance_scale=None, null_text=None, clip=3.0, prediction=None):
         """ddpm_sample (:508-569): x <- (x - c2*eps)/sqrt(alpha_t) [+ sqrt(beta_t)*z if t>0], t strided by 50 when fast.
         noise_fn(i, shape) -> tensor supplies x_T (i = -1) and the per-step z (tests inject it); default torch.randn.
         `max_steps` runs only the first that many steps of the chain (benchmarks / property tests of the 1000-step loop).
         See SamplerRun for the hipGraph form (use_graph=True or PSG_GRAPH=1; bit-identical to the eager loop).
         Opt-in (guidance.py; the defaults are the chain above, untouched): sampler="ddim" runs `ddim_sample` over this
         scheduler's alphas_cumprod with `num_steps` (default 50) forwards, `eta` and `clip`; `guidance_scale` with `null_text`
-        guides either chain - "ddpm" then runs one forward at batch 2n, psg_cfg_combine_f32 and the same update."""
+        guides either chain - "ddpm" then runs one forward at batch 2n, psg_cfg_combine_f32 and the same update.
+        `prediction` (default: this stepper's prediction_type) says what the U-Net returns; "v_prediction" turns it into eps
+        (psg_pred_to_eps_f32, which then also does the guidance combine) before the ddpm update, and takes the v form of the
+        DDIM step."""
         run = self.sampler(text_emb, num_samples, fast_sampling, noise_fn, latent_dim, hw, use_graph, max_steps, sampler, num_steps,
-                           eta, guidance_scale, null_text, clip)
+                           eta, guidance_scale, null_text, clip, prediction)
         while run.remaining():
             run.step()
             if trace is not None:
@@ -357,15 +385,16 @@ class DiffusionStepper:
         return run.x if type(run) is SamplerRun else run.x.clone()     # (guided: x is a view of the 2n input buffer)
 
     def sampler(self, text_emb, num_samples, fast_sampling=True, noise_fn=None, latent_dim=8, hw=27, use_graph=None, max_steps=None,
-                sampler="ddpm", num_steps=None, eta=0.0, guidance_scale=None, null_text=None, clip=3.0):
+                sampler="ddpm", num_steps=None, eta=0.0, guidance_scale=None, null_text=None, clip=3.0, prediction=None):
         """The same chain, one `step()` at a time (bench.py times single denoising steps)."""
+        prediction = self.prediction if prediction is None else prediction_code(prediction)
         if sampler == "ddpm" and guidance_scale is None:
-            return SamplerRun(self, text_emb, num_samples, fast_sampling, noise_fn, latent_dim, hw, use_graph, max_steps)
+            return SamplerRun(self, text_emb, num_samples, fast_sampling, noise_fn, latent_dim, hw, use_graph, max_steps, prediction)
         if guidance_scale is not None and null_text is None:
             raise ValueError("sample: guidance_scale needs null_text")
         if sampler == "ddpm":
             return GuidedSamplerRun(self, text_emb, num_samples, fast_sampling, noise_fn, latent_dim, hw, use_graph, max_steps,
-                                    guidance_scale=guidance_scale, null_text=null_text)
+                                    guidance_scale=guidance_scale, null_text=null_text, prediction=prediction)
         if sampler != "ddim":
             raise ValueError(f"sample: sampler={sampler!r} (\"ddpm\" or \"ddim\")")
         if max_steps is not None:
@@ -373,7 +402,7 @@ class DiffusionStepper:
         if text_emb.shape[0] != num_samples:
             raise ValueError(f"sample: {num_samples} samples for {text_emb.shape[0]} texts")
         return DdimRun(self.unet, text_emb, self.noise_scheduler.alphas_cumprod, 50 if num_steps is None else num_steps, eta,
-                       guidance_scale, null_text, clip, None, noise_fn, use_graph, latent_dim, hw)
+                       guidance_scale, null_text, clip, None, noise_fn, use_graph, latent_dim, hw, prediction)
 
 
 class GraphedTrainStep:
@@ -455,8 +484,11 @@ class SamplerRun:
 
     @torch.no_grad()
     def __init__(self, stepper, text_emb, num_samples, fast_sampling=True, noise_fn=None, latent_dim=8, hw=27, use_graph=None,
-                 max_steps=None):
+                 max_steps=None, prediction=None):
         self.st = stepper
+        # what the U-Net returns (default: what the stepper trains); anything but eps becomes eps in one more launch
+        # (psg_pred_to_eps_f32, t read on the device) in front of the reference's update
+        self.prediction = stepper.prediction if prediction is None else prediction_code(prediction)
         stepper.unet.eval()
         dev = stepper.device
         self.rnd = noise_fn if noise_fn is not None else (lambda i, shape: torch.randn(shape, device=dev))
@@ -503,6 +535,9 @@ class SamplerRun:
     def _body(self):
         st = self.st
         eps = st.unet(self.x, self.tv, self.text).contiguous()
+        if self.prediction != PRED_EPS:
+            eps = eps if eps.dtype == torch.float32 else eps.float()
+            pred_to_eps(self.x, eps, None, 0.0, st.noise_scheduler, self.t_dev, self.prediction, out=eps)
         check(st.lib.psg_ddpm_update_f32(ptr(self.x), ptr(eps), ptr(self.z), ptr(self.c1), ptr(self.c2), ptr(self.sg), ptr(self.t_dev),
                                          self.x.numel(), stream_ptr()), "psg_ddpm_update_f32")
 
@@ -555,8 +590,8 @@ class GuidedSamplerRun(SamplerRun):
 
     @torch.no_grad()
     def __init__(self, stepper, text_emb, num_samples, fast_sampling=True, noise_fn=None, latent_dim=8, hw=27, use_graph=None,
-                 max_steps=None, guidance_scale=1.0, null_text=None):
-        super().__init__(stepper, text_emb, num_samples, fast_sampling, noise_fn, latent_dim, hw, use_graph, max_steps)
+                 max_steps=None, guidance_scale=1.0, null_text=None, prediction=None):
+        super().__init__(stepper, text_emb, num_samples, fast_sampling, noise_fn, latent_dim, hw, use_graph, max_steps, prediction)
         if self.text.shape[0] != num_samples:
             raise ValueError(f"sample: {num_samples} samples for {self.text.shape[0]} texts")
         n = num_samples
@@ -568,7 +603,7 @@ class GuidedSamplerRun(SamplerRun):
 
     def _body(self):
         st, n = self.st, self.x.shape[0]
-        eps = guided_eps(st.unet, self.xin, self.tv, self.text, self.w, n)
+        eps = guided_eps(st.unet, self.xin, self.tv, self.text, self.w, n, self.prediction, st.noise_scheduler, self.t_dev)
         check(st.lib.psg_ddpm_update_f32(ptr(self.x), ptr(eps), ptr(self.z), ptr(self.c1), ptr(self.c2), ptr(self.sg), ptr(self.t_dev),
                                          self.x.numel(), stream_ptr()), "psg_ddpm_update_f32")
         self.xin[n:].copy_(self.x)
@@ -793,13 +828,18 @@ class ImprovedDiffusionTrainer(TrainerBase):
                             "eta": float(tc.get("ddim_eta", 0.0))}
         if self.sample_opts["sampler"] not in ("ddpm", "ddim"):
             raise ValueError(f"training.sampler={self.sample_opts['sampler']!r} (\"ddpm\" or \"ddim\")")
+        # opt-in objective (objective.py; absent: uniform eps regression, the reference's): `training.prediction_type`
+        # ("epsilon" / "v_prediction") and `training.min_snr_gamma` (Min-SNR-gamma loss weights; absent, None or 0: uniform)
+        self.prediction_type = prediction_name(tc.get("prediction_type") or EPSILON)
+        self.min_snr_gamma = float(tc["min_snr_gamma"]) if tc.get("min_snr_gamma") else None
         self._null_cache = {}
         self._betas = (get("beta1", 0.9), get("beta2", 0.999))
         self.stepper = DiffusionStepper(self.unet, self.noise_scheduler, lr=lr, betas=self._betas,
                                         weight_decay=get("weight_decay"), eps=1e-6, max_grad_norm=self.max_grad_norm,
                                         optimizer_type=get("optimizer", "adamw"), grad_bucket_dtype=self._grad_bucket_dtype,
                                         ema_decay=self.ema_decay, ema_warmup=bool(tc.get("ema_warmup", True)),
-                                        cond_drop_prob=self.cond_drop_prob)
+                                        cond_drop_prob=self.cond_drop_prob, prediction_type=self.prediction_type,
+                                        min_snr_gamma=self.min_snr_gamma)
         self.optimizer = self.stepper.optimizer
         self.scheduler_config = {"type": uc.get("scheduler", oc.get("scheduler", "cosine")), "lr": lr}
         self.logger.info(f"Using U-Net optimization: {get('optimizer', 'adamw')}, lr={lr}, wd={get('weight_decay')}, clip={self.max_grad_norm}")
@@ -807,6 +847,8 @@ class ImprovedDiffusionTrainer(TrainerBase):
             self.logger.info(f"EMA of the U-Net weights: decay={self.ema_decay}, warmup={bool(tc.get('ema_warmup', True))}")
         if self.cond_drop_prob:
             self.logger.info(f"Classifier-free guidance training: the text is dropped with probability {self.cond_drop_prob}")
+        if self.stepper.objective_enabled:
+            self.logger.info(f"Objective: {self.prediction_type}, Min-SNR gamma={self.min_snr_gamma}")
 
     def _make_scheduler(self, optimizer):
         if self.scheduler_config["type"] == "cosine":
@@ -1023,6 +1065,10 @@ class ImprovedDiffusionTrainer(TrainerBase):
                 "best_val_loss": self.best_val_loss, "config": self.config}
         if self.cond_drop_prob:                    # tells a loader that guidance means something on these weights
             ckpt["cond_drop_prob"] = self.cond_drop_prob
+        if self.prediction_type != EPSILON:        # a sampler must know what these weights predict
+            ckpt["prediction_type"] = self.prediction_type
+        if self.min_snr_gamma is not None:
+            ckpt["min_snr_gamma"] = self.min_snr_gamma
         if self.stepper.ema_enabled:               # next to the reference's keys, none of which changes
             ckpt["ema_unet_state_dict"], ckpt["ema_decay"] = self.stepper.ema_state_dict(), self.ema_decay
         if is_best:
@@ -1031,6 +1077,10 @@ class ImprovedDiffusionTrainer(TrainerBase):
 
     def load_checkpoint(self, checkpoint_path: str):
         ckpt = torch.load(checkpoint_path, map_location=self.device)
+        have = prediction_name(ckpt.get("prediction_type") or EPSILON)
+        if have != self.prediction_type:           # (before anything is loaded: the trainer stays as it was)
+            raise _lib.PsgError(f"{checkpoint_path} holds a U-Net trained with prediction_type={have!r}, but training.prediction_type is "
+                                f"{self.prediction_type!r}: its outputs mean something else")
         self.current_epoch, self.best_val_loss = ckpt["epoch"], ckpt["best_val_loss"]
         self.unet.load_state_dict(ckpt["unet_state_dict"])
         self.optimizer.load_state_dict(ckpt["optimizer_state_dict"])
